@@ -17,9 +17,14 @@ K5) fused in.  Workloads (--workload; BASELINE.json configs):
 Multi-GPU (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N): one process
 per GPU.  Rank 0 builds the cost raster (K1) and broadcasts it once with libuampath's RCCL
 broadcast over xGMI (uam_bcast_raster; timed separately, outside the step); each rank derives
-the gather-skip bitmap locally; pairs are sharded with no collective in the hot loop.  Every
-rank checks the first pairs of its shard bit for bit against the CPU oracle; the mismatch
-counts are summed over ranks into the line's "parity".
+the gather-skip bitmap locally; pairs are sharded with no collective in the hot loop.  With
+--full every rank checks the first pairs of its shard bit for bit against the CPU oracle; the
+mismatch counts are summed over ranks into the line's "parity".
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs DIR is given, and prints the line.  --full adds what takes runs of its own: K1
+timed alone (setup.raster_build), the library's own per-call events
+(roofline.sequence_ms_library_events), cpu_baseline and parity.
 
 Prints ONE JSON line (rank 0).  roofline: algorithmic bytes per launch of the dominant kernel
 (16 B per waypoint gather + 16 B of outputs per path = 16 W + 16 B/path) / its
@@ -69,6 +74,14 @@ def parse():
     ap.add_argument("--pairs", type=int, default=None,
                     help="override the pair count (per GPU, or in total for cfg4)")
     ap.add_argument("--R", type=int, default=None, help="override raster size")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: "
+                         "K1 timed alone, the library's own per-call events, the CPU baseline "
+                         "and the bit-exact parity checks against the CPU oracle")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step (what a caller of "
+                         "eval_generated receives) as DIR/<name>.npy, float64, at most 64 MB in "
+                         "all (a fixed seeded sample of the paths beyond that)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads for the CPU baseline (0: the box's CPU share, "
@@ -198,26 +211,9 @@ def main():
             raster = eng.raster_build(geo, dem_dev, summary=False)
             torch.cuda.synchronize()
             setup["raster_build_ms"] = round((time.perf_counter() - t1) * 1e3, 3)
-            # K1 alone, warm (5 more builds into the same records, the median), HIP events on
-            # its stream: 4 B of DEM read + 16 B of record written per cell
-            k1_runs = []
-            for _ in range(5):
-                e0 = torch.cuda.Event(enable_timing=True)
-                e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                eng.raster_build(geo, dem_dev, out=raster.rec, summary=False)
-                e1.record()
-                torch.cuda.synchronize()
-                k1_runs.append(e0.elapsed_time(e1))
-            k1_ms = sorted(k1_runs)[len(k1_runs) // 2]
-            cells = geo.nx * geo.ny
-            setup["raster_build"] = {
-                "cells": cells, "k1_ms": round(k1_ms, 4),
-                "cells_per_s": round(cells / (k1_ms * 1e-3), 1), "bytes_per_cell": 20,
-                "k1_frac_of_hbm": round(20 * cells / (k1_ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4)}
-            if "tiles_ingest_s" in setup:
-                setup["raster_build"]["tiles_ingest_plus_k1_ms"] = round(
-                    setup["tiles_ingest_s"] * 1e3 + k1_ms, 3)
+            if args.full:
+                setup["raster_build"] = time_k1(eng, geo, dem_dev, raster,
+                                                setup.get("tiles_ingest_s"))
             if volume_mode:
                 t2 = time.perf_counter()
                 volume = eng.volume_build(raster, cfg["nz"], cfg["z0"], cfg["dz"],
@@ -274,6 +270,11 @@ def main():
     P = Q * D
     outs = eng.outputs(P, W, n_pairs=Q, want_cells=args.cells and not volume_mode)
     o = outs[0]
+    if args.dump_outputs:
+        # outputs the mode does not write (below_terrain outside volume mode, ...) are dumped
+        # as zeros, not as whatever the allocation held
+        for t in o.values():
+            t.zero_()
     if args.group is not None:
         eng.set_option("group", args.group)
     for kv in args.opt:
@@ -308,13 +309,19 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     kern_ms = ev0.elapsed_time(ev1) / args.steps
-    # cross-check after the timed region: the library's own HIP-event pair around each call's
-    # launch sequence (uam_kernel_timing), same steps
-    eng.kernel_timing(True)
-    run_steps(args.steps)
-    k_total, k_launches = eng.kernel_time()
-    eng.kernel_timing(False)
-    seq_ms = k_total / k_launches if k_launches == args.steps else None
+    if args.dump_outputs:
+        # what the last timed step left in the caller's outputs (ranks of an N-rank run apart)
+        dump_outputs(o, args.dump_outputs if world == 1 else
+                     os.path.join(args.dump_outputs, f"rank{rank}"))
+    seq_ms = None
+    if args.full:
+        # cross-check after the timed region: the library's own HIP-event pair around each
+        # call's launch sequence (uam_kernel_timing), same steps
+        eng.kernel_timing(True)
+        run_steps(args.steps)
+        k_total, k_launches = eng.kernel_time()
+        eng.kernel_timing(False)
+        seq_ms = k_total / k_launches if k_launches == args.steps else None
     if world > 1:
         elapsed, kern_ms = udist.max_over_ranks([elapsed, kern_ms], device=eng.torch_device)
 
@@ -413,7 +420,7 @@ def main():
         result["ranks"] = world
 
     # ---- parity at N > 1: every rank checks the first pairs of its shard --------------------
-    if world > 1:
+    if world > 1 and args.full:
         mism = rank_parity(eng, spec, params, mode, geo, raster, volume, pairs_host, ut_host, o,
                            D, N, group)
         t = torch.tensor(mism, dtype=torch.float64,
@@ -427,7 +434,7 @@ def main():
                                     f"{PARITY_PAIRS_PER_RANK} pairs of every rank's shard"}
 
     # ---- CPU baseline + parity sample (rank 0, N=1 only) ----------------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         O.build()
         orc = O.Oracle(O.compile_spec(spec), N, spec["options"], spec["maxratio"],
@@ -527,6 +534,61 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def time_k1(eng, geo, dem_dev, raster, tiles_ingest_s=None):
+    """K1 alone, warm (5 more builds into the same records, the median), HIP events on its
+    stream: 4 B of DEM read + 16 B of record written per cell."""
+    k1_runs = []
+    for _ in range(5):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        eng.raster_build(geo, dem_dev, out=raster.rec, summary=False)
+        e1.record()
+        torch.cuda.synchronize()
+        k1_runs.append(e0.elapsed_time(e1))
+    k1_ms = sorted(k1_runs)[len(k1_runs) // 2]
+    cells = geo.nx * geo.ny
+    r = {"cells": cells, "k1_ms": round(k1_ms, 4),
+         "cells_per_s": round(cells / (k1_ms * 1e-3), 1), "bytes_per_cell": 20,
+         "k1_frac_of_hbm": round(20 * cells / (k1_ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4)}
+    if tiles_ingest_s is not None:
+        r["tiles_ingest_plus_k1_ms"] = round(tiles_ingest_s * 1e3 + k1_ms, 3)
+    return r
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6   # every .npy of one --dump-outputs, headers included
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(o, out_dir):
+    """Write the output arrays o (name -> tensor, first axis = path or pair) as
+    out_dir/<name>.npy in float64 (the int32 counts and indices are exact in it).  Outputs
+    beyond DUMP_BUDGET_BYTES in all are cut to one seeded sample of rows per array, the same
+    share of each, in ascending row order; manifest.json names every array's shape and rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in o.items()}
+    budget = DUMP_BUDGET_BYTES - 256 * len(arrays)   # .npy headers
+    total = sum(a.size * 8 for a in arrays.values())
+    share = min(1.0, budget / total) if total else 1.0
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    manifest = {}
+    for name in sorted(arrays):
+        a = arrays[name]
+        n = a.shape[0]
+        rows = None
+        if share < 1.0:
+            rows = np.sort(rng.choice(n, size=int(n * share), replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        manifest[name] = {"shape": list(arrays[name].shape), "rows_written": int(a.shape[0]),
+                          "sample": None if rows is None else
+                          f"np.sort(default_rng({DUMP_SAMPLE_SEED}).choice({n}, {len(rows)}, "
+                          f"replace=False)), arrays drawn in name order"}
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+    return manifest
 
 
 def gather_roofline(prof, P, W, kern_ms, kernel_name, packed=False, volume=False, cells=False,

@@ -288,6 +288,59 @@ def test_bench_roofline_bookkeeping():
     assert bench.analytic_roofline({}, 1, 1.0, "k")["frac"] is None
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every output array as <name>.npy in float64 with the int32
+    values exact; over the byte budget every array keeps the same share of its rows, a seeded
+    sample in ascending order that is the same from call to call, and the files fit the
+    budget."""
+    import torch
+
+    import bench
+
+    o = {"cost": torch.arange(1000, dtype=torch.float64) * 0.1,
+         "nfz_hits": torch.arange(1000, dtype=torch.int32),
+         "cells": torch.arange(3000, dtype=torch.int32).reshape(1000, 3) + (1 << 25),
+         "best_fval_idx": torch.arange(200, dtype=torch.int32) % 5}
+    m = bench.dump_outputs(o, str(tmp_path / "a"))
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(
+        [k + ".npy" for k in o] + ["manifest.json"])
+    for k, v in o.items():
+        a = np.load(tmp_path / "a" / (k + ".npy"))
+        assert a.dtype == np.float64 and a.shape == tuple(v.shape)
+        assert np.array_equal(a, v.numpy().astype(np.float64))
+        assert m[k]["sample"] is None and m[k]["rows_written"] == v.shape[0]
+    # a budget the whole does not fit: 5200 values x 8 B against 256 B x 4 headers + 20800 B
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 256 * 4 + 20800)
+    bench.dump_outputs(o, str(tmp_path / "b"))
+    bench.dump_outputs(o, str(tmp_path / "c"))
+    size = 0
+    for k, v in o.items():
+        b = np.load(tmp_path / "b" / (k + ".npy"))
+        assert np.array_equal(b, np.load(tmp_path / "c" / (k + ".npy")))
+        assert b.shape == (v.shape[0] // 2,) + tuple(v.shape[1:])
+        full = v.numpy().astype(np.float64)
+        if k != "best_fval_idx":   # strictly increasing first column: the rows can be read back
+            rows = np.searchsorted(full.reshape(len(full), -1)[:, 0],
+                                   b.reshape(len(b), -1)[:, 0])
+            assert np.all(np.diff(rows) > 0) and np.array_equal(full[rows], b)
+        size += os.path.getsize(tmp_path / "b" / (k + ".npy"))
+    assert size <= 256 * 4 + 20800
+
+
+def test_bench_options(monkeypatch):
+    """--full and --dump-outputs are off by default; --steps / --warmup are the counts given."""
+    import sys
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
 DIV_CHECK_C = r"""
 #include <math.h>
 #include <stdint.h>

@@ -11,7 +11,7 @@ out=$1
 shift
 mkdir -p "$out"
 export TMPDIR=/tmp
-bench="python3 bench.py --no-cpu-baseline $*"
+bench="python3 bench.py --full --no-cpu-baseline $*"
 passes=${PASSES:-"trace fetch write tcc sq f64"}
 for p in $passes; do
     case $p in

@@ -1,7 +1,8 @@
 """GPU refinement (uam_refine) against the oracle's orc_refine: the
 refined waypoints, final cost, final infeasibility and step counts are compared with exact
 equality (tolerance 0: same float64 operation order, no FMA contraction).  The reference's
-OpEn solve itself is absent (parity unpinned vs the reference, see test_refine_cpu.py)."""
+OpEn solve itself is absent; the gradient and the contract are pinned independently of the
+oracle in test_refine_cpu.py / test_gpu_refine_grad.py / test_gpu_refine_fuzz.py."""
 import dataclasses
 
 import numpy as np

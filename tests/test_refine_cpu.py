@@ -1,13 +1,20 @@
 """Refinement oracle (oracle/uam_oracle.c orc_refine) on the CPU.
 The reference's own optimiser (OpEn/CasADi, solver.py:82-93) is a Rust build that is absent
-here, so the refinement result is parity unpinned against the reference; what is pinned is
-(a) its objective -- get_cost of the refined path is the golden-pinned cost function -- and
-(b) GPU == oracle bit for bit (tests/test_gpu_refine.py).  These tests hold the optimiser's
-own contract: endpoints fixed, cost and the augmented objective go down, determinism."""
+here, so the refined waypoints have no reference counterpart.  What is pinned instead:
+(a) its objective -- get_cost of the refined path is the golden-pinned cost function;
+(b) the gradient the optimiser descends along, read back through one step of known length,
+    against central differences of the augmented Lagrangian rebuilt from the golden-pinned
+    eval_paths(want_g=True) (tests/refine_ref.py), at y = 0 and at y != 0;
+(c) the optimiser's contract: endpoints fixed, cost goes down, the independent augmented
+    objective does not go up within an outer iteration, the reported cost / infeas are those of
+    the returned path, the step count stays within its budget, determinism;
+(d) GPU == oracle bit for bit (tests/test_gpu_refine.py, test_gpu_refine_grad.py,
+    test_gpu_refine_fuzz.py)."""
 import numpy as np
 import pytest
 
 import golden_io as G
+import refine_ref as R
 
 
 def _canonical(oracle_mod, options=None):
@@ -90,3 +97,95 @@ def test_refine_restart_never_worse(oracle_mod):
     c = orc.refine(wp, oracle_mod.refine_params(n_outer=3, n_inner=8, n_restart=2))
     assert (c["infeas"] <= a["infeas"]).all()
     assert (c["iters"] >= a["iters"]).all()
+
+
+# ---- the gradient and the contract, against the independent Lagrangian (refine_ref.py) ------
+OPTS = {"length_smooth": True, "penalty_smooth": True, "obstacle_smooth": True,
+        "maxratio_smooth": False}
+
+
+def _refine_fn(oracle_mod, orc):
+    return lambda z, rp: orc.refine(z, oracle_mod.refine_params(**rp))
+
+
+def _generated(oracle_mod, nfz, N, opts, enl, anchored, pairs, seed, map_seed=2):
+    from uam_path_planning_amd.arcs import arc_table
+    from uam_path_planning_amd.scenario import canonical_spec, displacements
+    from uam_path_planning_amd.synthetic import random_pairs
+
+    spec = canonical_spec(nfz_polygons=nfz, seed=map_seed)
+    orc = oracle_mod.Oracle(oracle_mod.compile_spec(spec), N, opts, spec["maxratio"],
+                            spec["maxalpha"], enl, spec["weights"],
+                            anchor=tuple(spec["x_start"]) if anchored else None)
+    wp = oracle_mod.gen_paths(random_pairs(pairs, seed=seed),
+                              arc_table(N, displacements(5))).reshape(-1, N + 2, 2)
+    return orc, R.jitter(wp, seed)
+
+
+def _assert_gradients(oracle_mod, orc, wp, need_second):
+    return R.assert_gradients(_refine_fn(oracle_mod, orc), R.oracle_eval(orc), wp, need_second)
+
+
+@pytest.mark.parametrize("ls", [False, True])
+@pytest.mark.parametrize("ms", [False, True])
+@pytest.mark.parametrize("enl", [0.0, 0.3])
+@pytest.mark.parametrize("anchored", [False, True])
+def test_refine_gradient_options(oracle_mod, ls, ms, enl, anchored):
+    """The optimiser's gradient == the gradient of the independent L, every option combination
+    (generated candidates, every second one jittered, N = 20, the 16-polygon map).  The
+    allowance is refine_ref.grad_check's: 10 x the finite difference's own error + the read-back
+    rounding.  Measured over this file's gradient tests: error / allowance <= 0.41, error /
+    the path's largest component <= 1.1e-7, no coordinate excluded."""
+    opts = dict(OPTS, length_smooth=ls, maxratio_smooth=ms)
+    orc, wp = _generated(oracle_mod, 16, 20, opts, enl, anchored, 2, seed=21)
+    _assert_gradients(oracle_mod, orc, wp, True)
+
+
+@pytest.mark.parametrize("N", [1, 2, 3, 62, 63, 80])
+@pytest.mark.parametrize("nfz", [0, 16, 100])
+def test_refine_gradient_sizes_and_maps(oracle_mod, N, nfz):
+    """... over N (1..3: kinematic rows clipped at both ends; 62 / 63: W = 64 / 65, the first
+    lane of the lane-tree sums that owns a second waypoint) and maps with 5, 22 and 106 no-fly
+    shapes (gradients up to 1e21 inside a polygon: alpha0 per path).  The options alternate
+    with the case.  Straight candidates under length_smooth have an exactly zero gradient at
+    small N: the allowance's absolute terms carry them."""
+    k = N + nfz
+    opts = dict(OPTS, length_smooth=bool(k & 1), maxratio_smooth=bool(k & 2))
+    orc, wp = _generated(oracle_mod, nfz, N, opts, 0.3 if k % 3 == 0 else 0.0, bool(k % 5),
+                         2 if N <= 63 and nfz < 100 else 1, seed=22 + N)
+    _assert_gradients(oracle_mod, orc, wp, N >= 62)
+
+
+@pytest.mark.parametrize("variant", [{}, {"maxratio_smooth": True}, {"length_smooth": False}])
+def test_refine_gradient_canonical(oracle_mod, variant):
+    """... on the five canonical fixture candidates (N = 80)."""
+    orc, wp, _ = _canonical(oracle_mod, variant)
+    _assert_gradients(oracle_mod, orc, wp, True)
+
+
+@pytest.mark.parametrize("memory", [0, 3, 8])
+def test_refine_augmented_objective_descends(oracle_mod, memory):
+    """Within one outer iteration (y = 0, c = c0) the independent augmented objective of every
+    path does not go up, for steepest descent and both L-BFGS ring lengths."""
+    orc, wp, _ = _canonical(oracle_mod)
+    rp = dict(n_outer=1, n_inner=10, memory=memory)
+    out = orc.refine(wp, oracle_mod.refine_params(**rp))
+    assert (R.check_descent(wp, out["wp"], R.oracle_eval(orc)) < 0.0).all()
+    orc, wp = _generated(oracle_mod, 16, 24, OPTS, 0.3, True, 4, seed=8)
+    out = orc.refine(wp, oracle_mod.refine_params(**rp))
+    R.check_descent(wp, out["wp"], R.oracle_eval(orc))
+    R.check_contract(out, R.oracle_eval(orc), rp)
+
+
+@pytest.mark.parametrize("n_outer,n_restart", [(1, 0), (3, 0), (1, 2), (3, 2)])
+def test_refine_reports_the_returned_path(oracle_mod, n_outer, n_restart):
+    """infeas == sum g^2 and cost == cost of eval_paths(returned wp), rtol 1e-12 (measured
+    <= 7e-16 / 2e-14: the two sides differ by summation order), with and without restarts;
+    iters <= n_outer n_inner (1 + n_restart)."""
+    rp = dict(n_outer=n_outer, n_inner=8, n_restart=n_restart)
+    orc, wp, _ = _canonical(oracle_mod)
+    R.check_contract(orc.refine(wp, oracle_mod.refine_params(**rp)), R.oracle_eval(orc), rp)
+    orc, wp = _generated(oracle_mod, 16, 24, OPTS, 0.0, True, 6, seed=8)
+    out = orc.refine(wp, oracle_mod.refine_params(**rp))
+    R.check_contract(out, R.oracle_eval(orc), rp)
+    assert (out["infeas"] > 0).any()

@@ -522,7 +522,10 @@ int32_t uam_last_group(const uam_ctx* ctx);
  *   UAM_OPT_K4H_TERRAIN          K4h's likewise: 0 (default) by bounds (4-B risk / 8-B
  *                                {risk, psi|nfz} voxels, the column terrain only where it could
  *                                still decide an output), 1 in the entry (8-B {risk, terrain}
- *                                voxels, 16-B voxels in no-fly / psi columns).  Same outputs. */
+ *                                voxels, 16-B voxels in no-fly / psi columns).  Same outputs.
+ *   UAM_OPT_EXACT_SUM            0 (default): K2h's raster sums in float64, in group order;
+ *                                1: as exact integers, independent of every option above (the
+ *                                section "Exact, order-independent raster sums" below) */
 enum {
     UAM_OPT_GROUP = 1,
     UAM_OPT_SORTED_MIN_PATHS = 2,
@@ -543,11 +546,64 @@ enum {
     UAM_OPT_K2H_LB_STRIDE = 19,
     UAM_OPT_K2H_TERRAIN = 20,
     UAM_OPT_K4H_TERRAIN = 21,
-    UAM_OPT_TEST_SORT_FAULT = 22  /* tests only: 1 makes the next sorted calls flag their sort as
+    UAM_OPT_TEST_SORT_FAULT = 22, /* tests only: 1 makes the next sorted calls flag their sort as
                                      inconsistent (the uam_device_status path); 0 (default) off */
+    UAM_OPT_EXACT_SUM = 23        /* 0 (default) / 1: exact, order-independent raster sums (below) */
 };
 int uam_set_option(uam_ctx* ctx, int32_t option, int64_t value);
 int uam_get_option(const uam_ctx* ctx, int32_t option, int64_t* value);
+
+/* ---- Exact, order-independent raster sums (UAM_OPT_EXACT_SUM = 1; off by default) ----------
+ * K2h's default sums add each path's Phi / N and psi_nfz terms as float64 in group order, so
+ * the bits of cost, nfz_sum and best_fval_idx depend on UAM_OPT_GROUP.  With the option on, the
+ * raster terms are added as integers: the result depends on the path and the raster only -- not
+ * on the group length, the chunk, the sort key, the terrain form, the batch size or the
+ * sharding -- so every rank may run its own fastest G and still agree bit for bit.
+ * Definition, for one float32 field of the record raster (phi, and separately psi_nfz):
+ *   exponent  e = max(1, largest biased exponent field among the finite cells) - 126, so every
+ *             finite |v| < 2^e; a raster with no finite nonzero cell gives e = -125
+ *   quantum   q = 2^(e - 96)
+ *   term      a finite v with sign s, 24-bit significand M (no hidden bit when the biased
+ *             exponent field b is 0) gives t = s (sh >= 0 ? M << sh : M >> -sh) with
+ *             sh = max(b, 1) - 54 - e <= 72, so |t| < 2^96.  A right shift truncates the
+ *             magnitude toward zero: only values more than 72 binades below the raster's
+ *             largest lose bits, deterministically and at most one quantum each
+ *   sum       S = the sum of the terms in 128-bit two's complement (no overflow below 2^31
+ *             terms)
+ *   result    fl(S) = S 2^(e - 96) rounded once to float64, to nearest even; S = 0 gives +0.0
+ *   non-finite records are not added; they set side flags (NaN, +inf, -inf per field) and the
+ *             result follows IEEE: NaN if any NaN or both infinities, else the infinity, else
+ *             fl(S)
+ *   off-raster waypoints, code-0 blocks and padding slots contribute 0.
+ * Path outputs with the option on: nfz_sum = fl(S_psi); cost = (double)(N+1) L + fl(S_phi) /
+ * (double)N (a true division); best_fval_idx = the selection rule on that cost; L, length_q,
+ * length, kin_sum, nfz_hits, offmap, min_clearance, cells and best_length_idx are exactly
+ * K2h's.  Against the default sums: rounding only, |cost_on - cost_off| <=
+ * 2 W 2^-53 (sum |phi_j| / N + (N+1) L).
+ * Dispatch: a raster-mode uam_eval_generated batch runs K2h's exact form at every size
+ * (uam_last_kernel "K2hx+pack"; UAM_OPT_SORTED_MIN_PATHS and UAM_OPT_WAVE_MAX_PATHS do not
+ * apply; uam_last_group reports G as usual) and never falls back to ordered sums: UAM_E_STATE
+ * when no sum scale is set, UAM_E_INVALID (reason in uam_last_error) for a batch K2h does not
+ * take -- no packed_dev, maxratio_smooth, UAM_OPT_K2G_SIM = 0, UAM_OPT_GROUP = 0, D > 16,
+ * N > 4096, a packed copy of 4 GiB or more.  Analytic mode, uam_eval_waypoints, the volume
+ * (K4h) and uam_refine ignore the option.
+ *
+ * uam_raster_sum_scale writes the raster's 16-byte scale {e_phi, e_psi, flags, 0} to the
+ * caller's device buffer scale_dev (flags: bits 0-2 = a phi cell holds NaN / +inf / -inf, bits
+ * 3-5 = a psi_nfz cell does), asynchronously on stream, no host sync.  The exponents are integer
+ * maxima: the words do not depend on the reduction's order.  Like the summary and the packed
+ * copy it is a derived, untracked copy of rec: rebuild it whenever rec changes.
+ * uam_set_sum_scale: the context keeps the pointer (not the words) for the uam_eval_generated
+ * calls that follow; NULL clears it.
+ * uam_exact_sum_host (host only, no GPU): the definition applied to values[n] by the same
+ * inline functions the kernels run; e = INT32_MIN derives the exponent from values, any other
+ * e must be at least that and at most 128 (UAM_E_INVALID otherwise); *e_out (optional) is the
+ * exponent used. */
+int uam_raster_sum_scale(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec_dev,
+                         int32_t* scale_dev, uam_stream stream);
+int uam_set_sum_scale(uam_ctx* ctx, const int32_t* scale_dev);
+int uam_exact_sum_host(const float* values, int64_t n, int32_t e, double* sum_out,
+                       int32_t* e_out);
 
 /* Workspace bytes uam_refine needs for n_paths (after uam_set_geometry/uam_set_params). */
 int64_t uam_refine_workspace_bytes(uam_ctx* ctx, int64_t n_paths,

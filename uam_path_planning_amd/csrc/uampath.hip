@@ -5817,6 +5817,107 @@ struct alignas(8) HSlot {  // 24 B per (path, group), written by one lane
     uint32_t cnt;  // nfz hits | off-raster << 8
 };
 
+// ---- exact raster sums (UAM_OPT_EXACT_SUM; the definition: include/uampath.h) ---------------
+// A field's float32 words are added as integers in units of the raster's quantum
+// q = 2^(e - 96), e = max(1, largest biased exponent field among the finite cells) - 126: a
+// word is a signed 24-bit significand shifted by sh = max(b, 1) - 54 - e <= 72 (a right shift
+// truncates the magnitude), so |term| < 2^96 and a 128-bit two's-complement sum holds 2^31 of
+// them.  Integer addition is associative: the sum does not depend on the group length, on the
+// order of the groups or on which lane adds what.  One rounding, to float64, at the end.
+// The same functions run on the host (uam_exact_sum_host) and in the kernels.
+struct X128 {  // two's complement, two 64-bit limbs
+    uint64_t lo, hi;
+};
+enum : uint32_t { XF_NAN = 1u, XF_PINF = 2u, XF_NINF = 4u };  // a field's side flags
+constexpr int X_E_MIN = -125, X_E_MAX = 128;                  // the exponents a raster can give
+
+__host__ __device__ __forceinline__ X128 x_add(X128 a, X128 b) {
+    X128 r;
+    r.lo = a.lo + b.lo;
+    r.hi = a.hi + b.hi + (r.lo < a.lo ? 1u : 0u);  // the low limb's carry
+    return r;
+}
+__host__ __device__ __forceinline__ X128 x_neg(X128 a) {
+    X128 r;
+    r.lo = ~a.lo + 1u;
+    r.hi = ~a.hi + (r.lo == 0 ? 1u : 0u);
+    return r;
+}
+// the exponent a word asks of its raster: max(b, 1) - 126 for a finite word, X_E_MIN otherwise
+__host__ __device__ __forceinline__ int32_t x_word_exp(uint32_t w) {
+    const int32_t b = (int32_t)((w >> 23) & 255u);
+    return b == 255 ? X_E_MIN : (b > 1 ? b : 1) - 126;
+}
+// a word's side flags (0 for a finite word)
+__host__ __device__ __forceinline__ uint32_t x_word_flags(uint32_t w) {
+    const uint32_t f = (w & 0x7fffffu) ? XF_NAN : (w >> 31) ? XF_NINF : XF_PINF;
+    return ((w >> 23) & 255u) == 255u ? f : 0u;
+}
+// a word's term at the exponent e >= x_word_exp(w) (0 for a non-finite word): selects and masks
+// only, so the kernels' consume loops stay straight-line code
+__host__ __device__ __forceinline__ X128 x_term(uint32_t w, int32_t e) {
+    const uint32_t b = (w >> 23) & 255u;
+    // the 24-bit significand: no hidden bit in a denormal, nothing from a non-finite word
+    const uint32_t m = b == 255u ? 0u : (w & 0x7fffffu) | (b ? 0x800000u : 0u);
+    const int sh = (int)(b ? b : 1u) - 54 - e;  // <= 72
+    const int rs = sh < 0 ? (-sh < 24 ? -sh : 24) : 0;  // a right shift of >= 24 leaves nothing
+    const int ls = sh > 0 ? sh : 0;
+    const int s = ls & 63;
+    const uint64_t a = (uint64_t)(m >> rs) << s;
+    const uint64_t c = ((uint64_t)m >> 1) >> (63 - s);  // the bits shifted past the low limb
+    const uint64_t lo = ls < 64 ? a : 0u;
+    const uint64_t hi = ls < 64 ? c : a;  // (ls >= 64: s <= 8, so a holds every bit)
+    // the sign: -t = ~t + 1 through a mask (the low limb carries only when it is 0)
+    const uint64_t sg = w >> 31, mk = 0u - sg;
+    X128 t;
+    t.lo = (lo ^ mk) + sg;
+    t.hi = (hi ^ mk) + (sg & (lo == 0 ? 1u : 0u));
+    return t;
+}
+// S 2^(e - 96) rounded once to float64, to nearest even: the magnitude normalised by its
+// leading zeros, its top 53 bits, a guard bit and the sticky rest (no int128 -> double
+// conversion: the device has none).  e in [X_E_MIN, X_E_MAX] keeps the result a normal double.
+__host__ __device__ __forceinline__ double x_to_double(X128 s, int32_t e) {
+    const bool neg = (s.hi >> 63) != 0;
+    if (neg) s = x_neg(s);
+    if ((s.lo | s.hi) == 0) return 0.0;
+    const int lz = s.hi ? __builtin_clzll(s.hi) : 64 + __builtin_clzll(s.lo);
+    X128 n;  // s << lz: bit 127 set
+    if (lz >= 64) {
+        n.hi = s.lo << (lz - 64);
+        n.lo = 0;
+    } else if (lz) {
+        n.hi = (s.hi << lz) | (s.lo >> (64 - lz));
+        n.lo = s.lo << lz;
+    } else {
+        n = s;
+    }
+    const uint64_t mant = n.hi >> 11;  // in [2^52, 2^53)
+    const bool guard = (n.hi >> 10) & 1u, sticky = ((n.hi & 0x3ffu) | n.lo) != 0;
+    const uint64_t inc = (guard && (sticky || (mant & 1u))) ? 1u : 0u;
+    const int ex = 127 - lz + e - 96;  // the leading bit's binade
+    // (a carry out of the fraction steps the exponent field: the next power of two)
+    uint64_t bits = ((uint64_t)(ex + 1023) << 52) + (mant - ((uint64_t)1 << 52)) + inc;
+    bits |= neg ? (uint64_t)1 << 63 : 0u;
+    double r;
+    __builtin_memcpy(&r, &bits, 8);
+    return r;
+}
+// a field's result: IEEE's for the non-finite words that were left out of S
+__host__ __device__ __forceinline__ double x_result(X128 s, uint32_t flags, int32_t e) {
+    if ((flags & XF_NAN) || ((flags & XF_PINF) && (flags & XF_NINF))) return __builtin_nan("");
+    if (flags & XF_PINF) return __builtin_inf();
+    if (flags & XF_NINF) return -__builtin_inf();
+    return x_to_double(s, e);
+}
+
+struct alignas(8) HSlotX {  // the exact form's slot: 40 B per (path, group)
+    uint64_t c_lo, c_hi;  // the sum of the group's phi terms
+    uint64_t n_lo, n_hi;  // the sum of its psi terms
+    float hmax;           // as HSlot's
+    uint32_t cnt;         // as HSlot's | phi flags << 16 | psi flags << 19
+};
+
 // every (path, group) item in K2g's sorted order: the group's points, cells and packed entries
 // only.  Every chunk is straight-line, in three phases so the LDS and memory round trips of its
 // CH slots overlap: the CH cells (the arc formula; p_0 / p_{W-1} from the pair's cells), the CH
@@ -5845,12 +5946,14 @@ struct alignas(8) HSlot {  // 24 B per (path, group), written by one lane
 // alone and chunks issued one ahead, tools/k2h_counts.py.)
 // K2h workgroup: 256 items (cfg3 0.297 ms against 0.306 at 512, profiles/r05/k2h12)
 constexpr int H_BS = UAM_K2H_BS;
-template <int CH, bool TE>  // TE: the terrain in the entry (UAM_OPT_K2H_TERRAIN 1)
+// EX (UAM_OPT_EXACT_SUM): the phi and psi words added as 128-bit integer terms at the raster's
+// exponents e_phi / e_psi (x_term) into an HSlotX, the non-finite ones as side flags
+template <int CH, bool TE, bool EX = false>  // TE: the terrain in the entry (UAM_OPT_K2H_TERRAIN 1)
 __device__ __forceinline__ void h_item(const KParams& p, const KRaster& rs, const KGrp& kg,
                                        const uint32_t* __restrict__ s_hdr,
                                        const double2* __restrict__ s_u, bool live, int32_t item,
                                        int32_t path, int32_t q, const double4& pr,
-                                       float seed) {
+                                       float seed, int32_t e_phi = 0, int32_t e_psi = 0) {
     // a lane past the last item evaluates nothing and writes nothing
     const int s = item - path * kg.nseg;
     const int32_t d = path - q * kg.D;
@@ -5886,6 +5989,14 @@ __device__ __forceinline__ void h_item(const KParams& p, const KRaster& rs, cons
     const uint32_t ot4 = __builtin_amdgcn_readfirstlane(rs.ot4);
     const uint32_t op8 = __builtin_amdgcn_readfirstlane(rs.op8);
     double gc = 0.0, gn = 0.0;
+    X128 xc = {0, 0}, xn = {0, 0};  // EX: the group's phi and psi terms
+    uint32_t xf = 0;                // EX: their side flags (phi | psi << 3)
+    // EX: one word into its field's sum (straight-line: wave-uniform skips of all-zero slots
+    // and of the flags, and slots split into aligned planes, gained nothing at cfg3)
+    auto x_take = [&](X128& acc, uint32_t w, int32_t e, int fs) {
+        acc = x_add(acc, x_term(w, e));
+        xf |= x_word_flags(w) << fs;
+    };
     float Lb = seed, E = seed;  // the path's seed: an exact terrain value of the path
     uint32_t nh = 0, off = 0;
     // one chunk ahead: chunk c + 1's loads are issued before chunk c is consumed (the fetch
@@ -6002,8 +6113,13 @@ __device__ __forceinline__ void h_item(const KParams& p, const KRaster& rs, cons
                     const uint32_t tb = rec ? ((r.w & UAM_FLAG_NODATA) ? 0u : r.z) : hi;
                     nh += (rec && (r.w & UAM_FLAG_NFZ)) ? 1u : 0u;
                     off += (vl && !in) ? 1u : 0u;
-                    gc = gc + over_n((double)__uint_as_float(phi));
-                    gn = gn + (rec ? (double)__uint_as_float(r.y) : 0.0);
+                    if constexpr (EX) {
+                        x_take(xc, phi, e_phi, 0);
+                        x_take(xn, rec ? r.y : 0u, e_psi, 3);
+                    } else {
+                        gc = gc + over_n((double)__uint_as_float(phi));
+                        gn = gn + (rec ? (double)__uint_as_float(r.y) : 0.0);
+                    }
                     // (off the raster, or code 0: +0.0 exactly)
                     E = fmaxf(E, code ? __uint_as_float(tb) : vl ? 0.0f : -INFINITY);
                     continue;
@@ -6013,8 +6129,13 @@ __device__ __forceinline__ void h_item(const KParams& p, const KRaster& rs, cons
                 pk_terms_k(rA[t], kcA[t], phi, psi, hit, rter);
                 nh += hit;
                 off += (vl && !in) ? 1u : 0u;
-                gc = gc + over_n((double)__uint_as_float(phi));
-                gn = gn + (double)__uint_as_float(psi);
+                if constexpr (EX) {
+                    x_take(xc, phi, e_phi, 0);
+                    x_take(xn, psi, e_psi, 3);
+                } else {
+                    gc = gc + over_n((double)__uint_as_float(phi));
+                    gn = gn + (double)__uint_as_float(psi);
+                }
                 const float ter = (kcA[t] & 3u) == 3u ? rter : ((tkA >> t) & 1u) ? tvA[t] : -INFINITY;
                 E = fmaxf(E, ter);
             }
@@ -6024,6 +6145,15 @@ __device__ __forceinline__ void h_item(const KParams& p, const KRaster& rs, cons
             for (int t = 0; t < CH; ++t) rA[t] = rB[t], tvA[t] = tvB[t], kcA[t] = kcB[t];
             vinA = vinB, tkA = tkB, nvA = nvB;
         }
+    }
+    if constexpr (EX) {
+        HSlotX o;
+        o.c_lo = xc.lo, o.c_hi = xc.hi;
+        o.n_lo = xn.lo, o.n_hi = xn.hi;
+        o.hmax = E;
+        o.cnt = nh | (off << 8) | (xf << 16);
+        if (live) reinterpret_cast<HSlotX*>(kg.slot)[(int64_t)s * kg.P + path] = o;
+        return;
     }
     HSlot o;
     o.cost = gc;
@@ -6036,8 +6166,9 @@ __device__ __forceinline__ void h_item(const KParams& p, const KRaster& rs, cons
 // K2h evaluation: workgroups of H_BS items (xcd_chunk), the packed raster's header (codes,
 // bounds, superblocks) and the unit-arc rows (+ G + CH padding slots) staged in LDS, then one item
 // per lane (h_item)
-template <int CH, bool TE>
-__global__ __launch_bounds__(H_BS, UAM_K2H_MINW) void k_h_eval(KParams p, KRaster rs, KGrp kg) {
+template <int CH, bool TE, bool EX>
+__device__ __forceinline__ void h_eval_wg(KParams p, KRaster rs, KGrp kg, int32_t e_phi,
+                                          int32_t e_psi) {
     PK_CODES_CHECK(CH);
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
     uint32_t* s_hdr = s_dyn;
@@ -6080,7 +6211,20 @@ __global__ __launch_bounds__(H_BS, UAM_K2H_MINW) void k_h_eval(KParams p, KRaste
     // waypoint in a wave of full ones)
     if ((int)threadIdx.x < kg.G + CH) s_u[nu + threadIdx.x] = make_double2(0.0, 0.0);
     __syncthreads();
-    h_item<CH, TE>(p, rs, kg, s_hdr, s_u, live, item, path, q, pr, seed);
+    h_item<CH, TE, EX>(p, rs, kg, s_hdr, s_u, live, item, path, q, pr, seed, e_phi, e_psi);
+}
+template <int CH, bool TE>
+__global__ __launch_bounds__(H_BS, UAM_K2H_MINW) void k_h_eval(KParams p, KRaster rs, KGrp kg) {
+    h_eval_wg<CH, TE, false>(p, rs, kg, 0, 0);
+}
+// the exact form (UAM_OPT_EXACT_SUM): the raster's exponents scale = {e_phi, e_psi, ...}
+// (uam_raster_sum_scale) read once per workgroup at a uniform address
+template <int CH, bool TE>
+__global__ __launch_bounds__(H_BS, UAM_K2H_MINW) void k_h_eval_x(
+    KParams p, KRaster rs, KGrp kg, const int32_t* __restrict__ scale) {
+    const int32_t e_phi = __builtin_amdgcn_readfirstlane(scale[0]);
+    const int32_t e_psi = __builtin_amdgcn_readfirstlane(scale[1]);
+    h_eval_wg<CH, TE, true>(p, rs, kg, e_phi, e_psi);
 }
 
 // The waypoint cells (the reference's returned waypoints as raster cells, solver.py:49,
@@ -6185,10 +6329,14 @@ __global__ __launch_bounds__(256) void k_cells(KParams p, KGrp kg) {
 // outputs of every path (block = 64 pairs x D, k_g_final's layout): the geometry terms from
 // the pair's scale and the displacement's unit sums (oracle sim_geo), cost = (N+1) L + the
 // Phi / N partials in group order, and the main.py:175-180 selection
-template <int NR>  // slots per path held in registers (0: a loop for long paths)
-__global__ __launch_bounds__(1024) void k_h_final(KParams p, KGrp kg, KOut out,
-                                                  int32_t* __restrict__ best_f,
-                                                  int32_t* __restrict__ best_l) {
+// EX (UAM_OPT_EXACT_SUM): a path's HSlotX sums added as integers and their flags ORed, each
+// field rounded once (x_result), cost = (N+1) L + fl(S_phi) / N, nfz_sum = fl(S_psi)
+template <int NR, bool EX>  // slots per path held in registers (0: a loop for long paths)
+__device__ __forceinline__ void h_final_wg(KParams p, KGrp kg, KOut out,
+                                           int32_t* __restrict__ best_f,
+                                           int32_t* __restrict__ best_l, int32_t e_phi,
+                                           int32_t e_psi) {
+    using Slot = std::conditional_t<EX, HSlotX, HSlot>;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int D = kg.D, t = threadIdx.x;
     double* s_cost = smem;
@@ -6196,10 +6344,10 @@ __global__ __launch_bounds__(1024) void k_h_final(KParams p, KGrp kg, KOut out,
     const int64_t q0 = (int64_t)blockIdx.x * 64;
     const int qi = t / D, di = t - qi * D;
     const bool bad = *kg.err != 0;  // an inconsistent sort (k_g_scatter / k_v_hist)
-    const HSlot* slot = reinterpret_cast<const HSlot*>(kg.slot);
+    const Slot* slot = reinterpret_cast<const Slot*>(kg.slot);
     if (q0 + qi < kg.n_pairs) {
         const int64_t gp = (q0 + qi) * D + di;
-        HSlot g[NR > 0 ? NR : 1];
+        Slot g[NR > 0 ? NR : 1];
         if (NR > 0) {
 #pragma unroll
             for (int s = 0; s < NR; ++s) g[s] = slot[(int64_t)min(s, kg.nseg - 1) * kg.P + gp];
@@ -6226,25 +6374,36 @@ __global__ __launch_bounds__(1024) void k_h_final(KParams p, KGrp kg, KOut out,
         double nsum = 0.0, hmax = -INFINITY;
         int32_t nh = 0, off = 0;
         double cost = (double)(p.N + 1) * L;
+        X128 xc = {0, 0}, xn = {0, 0};
+        uint32_t xf = 0;
+        auto take = [&](const Slot& gs) {
+            if constexpr (EX) {
+                xc = x_add(xc, X128{gs.c_lo, gs.c_hi});
+                xn = x_add(xn, X128{gs.n_lo, gs.n_hi});
+                xf |= gs.cnt >> 16;
+            } else {
+                cost = cost + gs.cost;
+                nsum = nsum + gs.psi;
+            }
+            hmax = fmax(hmax, (double)gs.hmax);
+            nh += (int32_t)(gs.cnt & 255u);
+            off += (int32_t)((gs.cnt >> 8) & 255u);
+        };
         if (NR > 0) {
 #pragma unroll
             for (int s = 0; s < NR; ++s) {
                 if (s >= kg.nseg) break;
-                cost = cost + g[s].cost;
-                nsum = nsum + g[s].psi;
-                hmax = fmax(hmax, (double)g[s].hmax);
-                nh += (int32_t)(g[s].cnt & 255u);
-                off += (int32_t)((g[s].cnt >> 8) & 255u);
+                take(g[s]);
             }
         } else {
             for (int s = 0; s < kg.nseg; ++s) {
-                const HSlot gs = slot[(int64_t)s * kg.P + gp];
-                cost = cost + gs.cost;
-                nsum = nsum + gs.psi;
-                hmax = fmax(hmax, (double)gs.hmax);
-                nh += (int32_t)(gs.cnt & 255u);
-                off += (int32_t)((gs.cnt >> 8) & 255u);
+                const Slot gs = slot[(int64_t)s * kg.P + gp];
+                take(gs);
             }
+        }
+        if constexpr (EX) {  // one rounding per field, a true division
+            cost = cost + x_result(xc, xf & 7u, e_phi) / (double)p.N;
+            nsum = x_result(xn, (xf >> 3) & 7u, e_psi);
         }
         put_outputs(out, gp, bad, cost, L, len, ksum, nsum, p.altitude - hmax, nh, off, 0);
         s_cost[di * 64 + qi] = cost;
@@ -6252,6 +6411,58 @@ __global__ __launch_bounds__(1024) void k_h_final(KParams p, KGrp kg, KOut out,
     }
     __syncthreads();
     put_selection(kg, bad, q0, t, s_cost, s_len, best_f, best_l);
+}
+template <int NR>
+__global__ __launch_bounds__(1024) void k_h_final(KParams p, KGrp kg, KOut out,
+                                                  int32_t* __restrict__ best_f,
+                                                  int32_t* __restrict__ best_l) {
+    h_final_wg<NR, false>(p, kg, out, best_f, best_l, 0, 0);
+}
+template <int NR>
+__global__ __launch_bounds__(1024) void k_h_final_x(KParams p, KGrp kg, KOut out,
+                                                    int32_t* __restrict__ best_f,
+                                                    int32_t* __restrict__ best_l,
+                                                    const int32_t* __restrict__ scale) {
+    const int32_t e_phi = __builtin_amdgcn_readfirstlane(scale[0]);
+    const int32_t e_psi = __builtin_amdgcn_readfirstlane(scale[1]);
+    h_final_wg<NR, true>(p, kg, out, best_f, best_l, e_phi, e_psi);
+}
+
+// uam_raster_sum_scale: scale = {e_phi, e_psi, flags, 0} of a record raster, flags = the phi
+// words' side flags | the psi words' << 3.  Integer maxima and ORs only, so the words do not
+// depend on the reduction's order: k_sum_scale_init writes the neutral words, then every wave
+// of k_sum_scale folds its cells (a grid-stride loop) and issues one atomic per word.
+__global__ void k_sum_scale_init(int32_t* __restrict__ scale) {
+    if (threadIdx.x < 4) scale[threadIdx.x] = threadIdx.x < 2 ? X_E_MIN : 0;
+}
+__global__ __launch_bounds__(256) void k_sum_scale(const uint4* __restrict__ rec, int64_t cells,
+                                                   int32_t* __restrict__ scale) {
+    int32_t ec = X_E_MIN, en = X_E_MIN;
+    uint32_t fl = 0;
+    constexpr int U = 4;  // loads in flight per lane (past the end: the last cell again)
+    const int64_t step = (int64_t)gridDim.x * 256;
+    for (int64_t c0 = (int64_t)blockIdx.x * 256 + threadIdx.x; c0 < cells; c0 += step * U) {
+        uint4 r[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) r[k] = rec[min(c0 + k * step, cells - 1)];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            ec = max(ec, x_word_exp(r[k].x));
+            en = max(en, x_word_exp(r[k].y));
+            fl |= x_word_flags(r[k].x) | (x_word_flags(r[k].y) << 3);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ec = max(ec, __shfl_xor(ec, o));
+        en = max(en, __shfl_xor(en, o));
+        fl |= (uint32_t)__shfl_xor((int32_t)fl, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (ec > X_E_MIN) atomicMax(scale + 0, ec);
+        if (en > X_E_MIN) atomicMax(scale + 1, en);
+        if (fl) atomicOr(scale + 2, (int32_t)fl);
+    }
 }
 
 // ---- K4h: the volume (config 5) in K2h's form -------------------------------------------------
@@ -6949,6 +7160,8 @@ struct uam_ctx {
     int32_t* h_err = nullptr;   // page-locked, device-mapped word the sorted forms' output
     int32_t* d_err = nullptr;   // launches set on a failed sort check (uam_device_status)
     int test_sort_fault = 0;    // UAM_OPT_TEST_SORT_FAULT (tests only)
+    int exact_sum = 0;          // UAM_OPT_EXACT_SUM: K2h's raster sums as exact integers
+    const int32_t* sum_scale = nullptr;  // uam_set_sum_scale: the caller's device words
 
 };
 
@@ -7734,6 +7947,12 @@ int uam_set_option(uam_ctx* ctx, int32_t option, int64_t value) {
                             (long long)value);
             ctx->test_sort_fault = (int)value;
             return UAM_OK;
+        case UAM_OPT_EXACT_SUM:
+            if (value != 0 && value != 1)
+                return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM %lld is not 0 or 1",
+                            (long long)value);
+            ctx->exact_sum = (int)value;
+            return UAM_OK;
         case UAM_OPT_K2H_LB_STRIDE:
             if (value < 0 || value > 1024)
                 return fail(UAM_E_INVALID, "UAM_OPT_K2H_LB_STRIDE %lld outside [0, 1024]",
@@ -7777,6 +7996,7 @@ int uam_get_option(const uam_ctx* ctx, int32_t option, int64_t* value) {
         case UAM_OPT_K2H_TERRAIN: *value = ctx->k2h_te; return UAM_OK;
         case UAM_OPT_K4H_TERRAIN: *value = ctx->k4h_te; return UAM_OK;
         case UAM_OPT_TEST_SORT_FAULT: *value = ctx->test_sort_fault; return UAM_OK;
+        case UAM_OPT_EXACT_SUM: *value = ctx->exact_sum; return UAM_OK;
         case UAM_OPT_K4H_BAND: *value = ctx->k4h_band; return UAM_OK;
         case UAM_OPT_K2G_CURVE: *value = ctx->k2g_curve; return UAM_OK;
 
@@ -8091,9 +8311,14 @@ static void magic_div(uint32_t D, uint64_t* m, int32_t* sh) {
 using GEvalFn = void (*)(KParams, KRaster, KGrp, const uint4*);
 using HEvalFn = void (*)(KParams, KRaster, KGrp);
 using GFinalFn = void (*)(KParams, KGrp, KOut, int32_t*, int32_t*);
+using HEvalXFn = void (*)(KParams, KRaster, KGrp, const int32_t*);
+using HFinalXFn = void (*)(KParams, KGrp, KOut, int32_t*, int32_t*, const int32_t*);
 struct GPlan {
     KGrp kg;
     bool sim;                 // K2h (the similarity form); K2g otherwise
+    bool exact;               // K2h's exact form (UAM_OPT_EXACT_SUM): hevx / finx, 40-B slots
+    HEvalXFn hevx;
+    HFinalXFn finx;
     int64_t ncnt, nsb;        // counts ([bins][G_NBK]) and scan blocks
     size_t lds, hist_dyn, ubytes, bytes;  // eval / histogram dynamic LDS, arc rows, scratch
     size_t b_key, b_cnt, b_tot, b_ord, b_slot, b_ug, b_err, b_lbp;
@@ -8108,14 +8333,30 @@ struct GPlan {
 static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, int64_t n_pairs,
                         const double* utab, int32_t D, const KOut& ko, GPlan* pl) {
     const int G = ctx->k2g_group;
-    if (G < 1 || G > G_MAXLEN || !kr.pmap || ko.g_rows || D > 16) return 0;
+    // the exact form never stands aside for another sum order: a batch K2h does not take is an
+    // error with its reason (at every size: UAM_OPT_SORTED_MIN_PATHS does not apply)
+    const bool exact = ctx->exact_sum != 0;
+    auto no = [&](const char* why) {
+        return exact ? fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM needs K2h: %s", why) : 0;
+    };
+    if (G < 1 || G > G_MAXLEN) return no("UAM_OPT_GROUP is 0");
+    if (!kr.pmap) return no("no packed_dev");
+    if (ko.g_rows) return no("g_rows requested");
+    if (D > 16) return no("D > 16");
     const int64_t W = ctx->kp.N + 2, P = n_pairs * D;
-    if (P < ctx->k2s_min || n_pairs > INT32_MAX / D) return 0;
+    if (!exact && P < ctx->k2s_min) return 0;
+    if (n_pairs > INT32_MAX / D) return no("more than 2^31 paths");
+    if (exact) {
+        if (!ctx->k2g_sim) return no("UAM_OPT_K2G_SIM is 0");
+        if (ctx->kp.maxratio_smooth) return no("maxratio_smooth is set");
+        if (!kr.pk) return no("the packed copy is 4 GiB or larger");
+        if (ctx->kp.N > 4096) return no("N > 4096");
+    }
     const size_t ubytes = (size_t)D * ctx->kp.N * 16;  // the unit-arc rows, staged in LDS
-    if (ubytes > (size_t)G_UTAB_LDS) return 0;
+    if (ubytes > (size_t)G_UTAB_LDS) return no("the unit-arc table exceeds its LDS share");
     const int nseg = (int)((W + G - 1) / G);
     const int64_t n_items = P * nseg;
-    if (n_items >= INT32_MAX) return 0;
+    if (n_items >= INT32_MAX) return no("more than 2^31 (path, group) items");
     int tbits = ctx->k2g_tbits;
     if (tbits == 0) {  // tiles of ~256 x 256 cells ...
         tbits = 3;
@@ -8132,16 +8373,20 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     pl->ncnt = (int64_t)bins * G_NBK;
     pl->nsb = (pl->ncnt + 256 * SCAN_ITEMS - 1) / (256 * SCAN_ITEMS);
-    if (pl->nsb > 4096) return 0;
+    if (pl->nsb > 4096) return no("the sort's counts exceed 4096 scan blocks");
     // K2h (the similarity form) unless disabled or maxratio_smooth (its turn rows are not
     // scale-free): 24-B slots, the geometry in the output launch
     // and its 32-bit offsets reach the whole packed copy; N <= 4096 (Phi / N by the reciprocal)
     const bool sim = ctx->k2g_sim && !ctx->kp.maxratio_smooth && kr.pk && ctx->kp.N <= 4096;
     pl->sim = sim;
+    pl->exact = exact;  // (sim holds: checked above)
+    pl->hevx = nullptr;
+    pl->finx = nullptr;
     pl->ubytes = ubytes;
     pl->b_key = al((size_t)n_items * 2), pl->b_cnt = al((size_t)pl->ncnt * 4);
     pl->b_tot = al(4096 * 4), pl->b_ord = al((size_t)n_items * 4);
-    pl->b_slot = al((size_t)n_items * (sim ? sizeof(HSlot) : sizeof(GSlot)));
+    pl->b_slot = al((size_t)n_items *
+                    (exact ? sizeof(HSlotX) : sim ? sizeof(HSlot) : sizeof(GSlot)));
     pl->b_ug = al((size_t)D * sizeof(UGeo)), pl->b_err = 256;
     pl->b_lbp = sim ? al((size_t)P * 4) : 0;
     pl->bytes = pl->b_key + pl->b_cnt + pl->b_tot + pl->b_ord + pl->b_slot + pl->b_ug +
@@ -8186,15 +8431,24 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
                                           k_h_eval<8, false>, k_h_eval<11, false>,
                                           k_h_eval<6, true>,  k_h_eval<7, true>,
                                           k_h_eval<8, true>,  k_h_eval<11, true>};
-        pl->hev = hevals[(chl <= 6 ? 0 : chl == 7 ? 1 : chl == 8 ? 2 : 3) + (ctx->k2h_te ? 4 : 0)];
+        static const HEvalXFn hevalsx[8] = {k_h_eval_x<6, false>, k_h_eval_x<7, false>,
+                                            k_h_eval_x<8, false>, k_h_eval_x<11, false>,
+                                            k_h_eval_x<6, true>,  k_h_eval_x<7, true>,
+                                            k_h_eval_x<8, true>,  k_h_eval_x<11, true>};
+        const int hi = (chl <= 6 ? 0 : chl == 7 ? 1 : chl == 8 ? 2 : 3) + (ctx->k2h_te ? 4 : 0);
+        pl->hev = hevals[hi];
+        pl->hevx = exact ? hevalsx[hi] : nullptr;
         pl->bs = H_BS;
         const size_t hw = ctx->k2h_te ? (size_t)kr.bnd_off : (size_t)kr.hwords;
         const size_t need = hw * 4 + ubytes + (size_t)16 * (G + 16);  // + padding
         const int floor_lds = ctx->k2g_lds ? ctx->k2g_lds : big ? 54000 : 0;
         pl->lds = std::max(need, (size_t)std::min(floor_lds, 160 * 1024));
-        if (pl->lds > 160 * 1024) return 0;
+        if (pl->lds > 160 * 1024) return no("the packed header and arc rows exceed the LDS");
         if (!ctx->k2h_attrs) {  // per context = per device (DeviceGuard active)
             for (HEvalFn f : hevals)
+                HIP_TRY(hipFuncSetAttribute((const void*)f,
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            for (HEvalXFn f : hevalsx)
                 HIP_TRY(hipFuncSetAttribute((const void*)f,
                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             HIP_TRY(hipFuncSetAttribute((const void*)k_g_hist,
@@ -8223,6 +8477,8 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
     // the output launch holds a path's slots in registers up to 8 groups
     pl->fin = sim ? (nseg <= 4 ? k_h_final<4> : nseg <= 8 ? k_h_final<8> : k_h_final<0>)
                   : nseg <= 4 ? k_g_final<4> : nseg <= 8 ? k_g_final<8> : k_g_final<0>;
+    if (exact)
+        pl->finx = nseg <= 4 ? k_h_final_x<4> : nseg <= 8 ? k_h_final_x<8> : k_h_final_x<0>;
     const int st = err_word(ctx, &kg);  // (kg.tkey: the launchers, after tile_keys)
     return st ? st : 1;
 }
@@ -8258,7 +8514,10 @@ static void grouped_sort(uam_ctx* ctx, const GPlan& pl, const KRaster& kr, hipSt
 static void grouped_eval(uam_ctx* ctx, const GPlan& pl, const KRaster& kr, const void* rec,
                          hipStream_t s) {
     const dim3 grid((unsigned)((pl.kg.n_items + pl.bs - 1) / pl.bs));
-    if (pl.hev)
+    if (pl.hevx)
+        hipLaunchKernelGGL(pl.hevx, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kr, pl.kg,
+                           ctx->sum_scale);
+    else if (pl.hev)
         hipLaunchKernelGGL(pl.hev, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kr, pl.kg);
     else
         hipLaunchKernelGGL(pl.ev, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kr, pl.kg,
@@ -8268,9 +8527,13 @@ static void grouped_eval(uam_ctx* ctx, const GPlan& pl, const KRaster& kr, const
 static void grouped_final(uam_ctx* ctx, const GPlan& pl, const KOut& ko, int32_t* best_f,
                           int32_t* best_l, hipStream_t s) {
     const int D = pl.kg.D;
-    hipLaunchKernelGGL(pl.fin, dim3((unsigned)((pl.kg.n_pairs + 63) / 64)), dim3(64 * D),
-                       (size_t)2 * 64 * D * sizeof(double), s, ctx->kp, pl.kg, ko, best_f,
-                       best_l);
+    const dim3 grid((unsigned)((pl.kg.n_pairs + 63) / 64));
+    const size_t lds = (size_t)2 * 64 * D * sizeof(double);
+    if (pl.finx)
+        hipLaunchKernelGGL(pl.finx, grid, dim3(64 * D), lds, s, ctx->kp, pl.kg, ko, best_f, best_l,
+                           ctx->sum_scale);
+    else
+        hipLaunchKernelGGL(pl.fin, grid, dim3(64 * D), lds, s, ctx->kp, pl.kg, ko, best_f, best_l);
 }
 
 // K2g launch (segment-grouped raster evaluation); returns 1 if launched, 0 if the batch is not
@@ -8282,6 +8545,9 @@ static int launch_grouped(uam_ctx* ctx, const KRaster& kr, const void* rec, cons
     GPlan pl;
     int st = grouped_plan(ctx, kr, pairs, n_pairs, utab, D, ko, &pl);
     if (st <= 0) return st;
+    if (pl.exact && !ctx->sum_scale)
+        return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM is on and no sum scale is set "
+                                 "(uam_raster_sum_scale, uam_set_sum_scale)");
     char* w = nullptr;
     st = order_scratch(ctx, pl.bytes, s, &w);
     if (st) return st;
@@ -8341,7 +8607,7 @@ static int launch_grouped(uam_ctx* ctx, const KRaster& kr, const void* rec, cons
     st = ktime_end(ctx, s);
     if (st) return st;
     ctx->last_group = pl.kg.G;
-    ctx->last_kernel = pl.sim ? "K2h+pack" : "K2g+pack";
+    ctx->last_kernel = pl.exact ? "K2hx+pack" : pl.sim ? "K2h+pack" : "K2g+pack";
     st = order_done(ctx, s);
     return st ? st : 1;
 }
@@ -8625,6 +8891,15 @@ static int eval_generated(uam_ctx* ctx, int32_t mode, const uam_raster_desc* des
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     ctx->last_group = 0;  // sequential sums unless K2g runs
+    // UAM_OPT_EXACT_SUM: the raster batch runs K2h's exact form at every size or fails (no wave
+    // or lane form, whose ordered sums would make the bits depend on the batch size)
+    const bool exact = mode == UAM_MODE_RASTER && ctx->exact_sum;
+    if (exact) {
+        st = launch_grouped(ctx, kr, rec, pairs, n_pairs, utab, D, ko, best_f, best_l, s);
+        if (st < 0) return st;
+        if (st == 1) return UAM_OK;  // last_kernel: "K2hx+pack"
+        return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM: the batch did not run K2h");
+    }
     if (mode == UAM_MODE_RASTER && n_pairs <= INT64_MAX / D && want_wave(ctx, n_pairs * D)) {
         const KVolume kv{};
         st = launch_wave(ctx, mode, true, kr, kv, rec, nullptr, pairs, utab, D, n_pairs * D, ko,
@@ -8848,6 +9123,59 @@ int uam_raster_summary(uam_ctx* ctx, const uam_raster_desc* desc, const void* re
                            summary);
     }
     HIP_TRY(hipGetLastError());
+    return UAM_OK;
+}
+
+int uam_raster_sum_scale(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
+                         int32_t* scale, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    KRaster kr{};
+    const int st = make_kraster(desc, &kr);
+    if (st) return st;
+    if (!rec || !scale) return fail(UAM_E_INVALID, "rec/scale is NULL");
+    DeviceGuard dg(ctx->device);
+    const int64_t cells = (int64_t)kr.nx * kr.ny;
+    hipLaunchKernelGGL(k_sum_scale_init, dim3(1), dim3(64), 0, (hipStream_t)stream, scale);
+    // 8 cells a lane at least, 2048 workgroups at most (the atomics: one per wave and word)
+    const unsigned grid = (unsigned)std::min<int64_t>((cells + 2047) / 2048, 2048);
+    hipLaunchKernelGGL(k_sum_scale, dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                       (const uint4*)rec, cells, scale);
+    HIP_TRY(hipGetLastError());
+    return UAM_OK;
+}
+
+int uam_set_sum_scale(uam_ctx* ctx, const int32_t* scale) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    ctx->sum_scale = scale;
+    return UAM_OK;
+}
+
+int uam_exact_sum_host(const float* values, int64_t n, int32_t e, double* sum_out,
+                       int32_t* e_out) {
+    if (n < 0 || (n > 0 && !values) || !sum_out)
+        return fail(UAM_E_INVALID, "uam_exact_sum_host: NULL argument or n < 0");
+    if (n >= ((int64_t)1 << 31))
+        return fail(UAM_E_INVALID, "uam_exact_sum_host: 2^31 or more terms");
+    int32_t need = X_E_MIN;
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t w;
+        memcpy(&w, values + i, 4);
+        need = std::max(need, x_word_exp(w));
+    }
+    if (e == INT32_MIN) e = need;
+    if (e < need || e > X_E_MAX)
+        return fail(UAM_E_INVALID, "uam_exact_sum_host: exponent %d outside [%d, %d]", e, need,
+                    X_E_MAX);
+    X128 s = {0, 0};
+    uint32_t fl = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t w;
+        memcpy(&w, values + i, 4);
+        s = x_add(s, x_term(w, e));
+        fl |= x_word_flags(w);
+    }
+    *sum_out = x_result(s, fl, e);
+    if (e_out) *e_out = e;
     return UAM_OK;
 }
 

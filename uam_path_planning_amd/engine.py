@@ -81,12 +81,15 @@ class CostRaster:
     summary: the K2 gather-skip bitmap of rec (uam_raster_summary, one bit per block x block
     cells; None = K2 gathers every waypoint); packed: the K2s packed copy of rec
     (uam_raster_pack, 8-B planes in 4 x 4-cell blocks; None = K2s gathers rec).  Rebuild both
-    (Engine.raster_summary) after rec changes."""
+    (Engine.raster_summary) after rec changes.  sum_scale: the raster's exponents and flags for
+    the exact sums (Engine.raster_sum_scale: [4] int32 {e_phi, e_psi, flags, 0}; None until an
+    evaluation with the "exact_sum" option needs it; raster_summary resets it)."""
     geo: RasterGeo
     rec: object = field(repr=False)
     summary: object = field(default=None, repr=False)
     block: int = 0
     packed: object = field(default=None, repr=False)  # uam_raster_pack copy for K2s (or None)
+    sum_scale: object = field(default=None, repr=False)  # uam_raster_sum_scale words (or None)
 
     @property
     def nbytes(self):
@@ -163,6 +166,7 @@ class Engine:
         _lib.check(self.lib.uam_ctx_create(self.device, ctypes.byref(h)), "uam_ctx_create")
         self._ctx = h
         self._geom_sig = None
+        self._exact_sum = False   # the "exact_sum" option as set_option last set it
         self.geometry = None
         self.params = None
 
@@ -261,6 +265,7 @@ class Engine:
                                                b.value, _ptr(sm), self.stream),
                    "uam_raster_summary")
         raster.summary, raster.block, raster.packed = sm, b.value, None
+        raster.sum_scale = None   # rec changed: the exponents are derived from it too
         if packed:
             nbytes = ctypes.c_int64()
             _lib.check(self.lib.uam_raster_pack_shape(ctypes.byref(g), b.value, None,
@@ -272,6 +277,31 @@ class Engine:
                        "uam_raster_pack")
             raster.packed = pk
         return raster
+
+    def raster_sum_scale(self, raster):
+        """Fill raster.sum_scale, the exact sums' scale of raster.rec (uam_raster_sum_scale:
+        [4] int32 {e_phi, e_psi, flags, 0} on the device, no host sync); returns raster.  A
+        derived, untracked copy like the summary: raster_summary resets it, and eval_generated
+        computes it when the "exact_sum" option is on and it is None."""
+        torch = _torch()
+        sc = self.empty((4,), torch.int32)
+        _lib.check(self.lib.uam_raster_sum_scale(self._ctx, ctypes.byref(raster.geo.as_struct()),
+                                                 _ptr(raster.rec), _ptr(sc), self.stream),
+                   "uam_raster_sum_scale")
+        raster.sum_scale = sc
+        return raster
+
+    @staticmethod
+    def exact_sum_host(values, e=None):
+        """The exact sum's definition (include/uampath.h) applied to float32 values on the host
+        by the functions the kernels run (uam_exact_sum_host; needs no GPU): (sum, e) with e
+        the exponent used -- derived from values when e is None."""
+        v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        out, eo = ctypes.c_double(), ctypes.c_int32()
+        _lib.check(_lib.load().uam_exact_sum_host(
+            v.ctypes.data, v.size, -2 ** 31 if e is None else int(e), ctypes.byref(out),
+            ctypes.byref(eo)), "uam_exact_sum_host")
+        return out.value, eo.value
 
     def read_tiles(self, paths, th, tw, n_threads=0, pinned=False):
         """GeoTIFF tiles -> host float32 [T, th, tw] (uam_read_tiles: parallel native reader;
@@ -330,20 +360,29 @@ class Engine:
 
     def last_kernel(self):
         """Which path evaluation the last eval_generated / eval_generated3d ran (uam_last_kernel:
-        "K2g+pack", "K2s+pack", "K2+skip", "K2w", "K3b", ...)."""
+        "K2h+pack", "K2hx+pack" (the exact sums), "K2g+pack", "K4h+pack", "K2s+pack", "K2+skip",
+        "K2w", "K3b", ...)."""
         return self.lib.uam_last_kernel(self._ctx).decode()
 
     def last_group(self):
-        """Waypoint-group length of the last eval_generated's sums (uam_last_group): G > 0 when
-        the segment-grouped K2g ran (the oracle's orc_eval_paths_g order), 0 = sequential."""
+        """Waypoint-group length of the last eval_generated / eval_generated3d's sums
+        (uam_last_group): G > 0 when a segment-grouped evaluation ran -- K2h / K4h (the oracle's
+        orc_eval_generated_h order) or K2g (orc_eval_paths_g) -- 0 = sequential.  With the
+        "exact_sum" option G is still reported, but the raster sums do not depend on it."""
         return int(self.lib.uam_last_group(self._ctx))
 
     def set_option(self, name, value):
-        """uam_set_option (include/uampath.h UAM_OPT_*): "group" (K2g waypoints per group,
-        0 = K2s), "sorted_min_paths", "k2s_segments", "wave_max_paths", "pair_order",
-        "k1_rows", "k3b_segment", "k3b_points_per_lane", "k8_tiled", "k8_streams"."""
+        """uam_set_option (include/uampath.h UAM_OPT_*; the names are _lib.OPTIONS' keys):
+        "group" (K2h / K2g / K4h waypoints per group, 0 = K2s / K4), "sorted_min_paths",
+        "k2s_segments", "wave_max_paths", "pair_order", "k1_rows", "k3b_segment",
+        "k3b_points_per_lane", "k8_tiled", "k8_streams", "k2g_tile_bits", "k2g_lds_floor",
+        "k2g_chunk", "k2g_curve", "k2g_sim", "k4h_band", "k2h_lb_stride", "k2h_terrain",
+        "k4h_terrain", "test_sort_fault" (tests only) and "exact_sum" (1: K2h's raster sums as
+        exact integers, independent of the group length -- "K2hx+pack")."""
         _lib.check(self.lib.uam_set_option(self._ctx, _lib.OPTIONS[name], int(value)),
                    "uam_set_option")
+        if name == "exact_sum":
+            self._exact_sum = bool(int(value))
 
     def get_option(self, name):
         v = ctypes.c_int64()
@@ -408,6 +447,11 @@ class Engine:
         block = 0
         if raster is not None:
             rec, summary, packed, block = raster.rec, raster.summary, raster.packed, raster.block
+            if self._exact_sum:   # the exact sums' scale: computed once per rec, then handed over
+                if raster.sum_scale is None:
+                    self.raster_sum_scale(raster)
+                _lib.check(self.lib.uam_set_sum_scale(self._ctx, _ptr(raster.sum_scale)),
+                           "uam_set_sum_scale")
         _lib.check(self.lib.uam_eval_generated(
             self._ctx, self._mode(raster), geo, _ptr(rec), _ptr(summary), int(block or 0),
             _ptr(packed), _ptr(pr), Q, _ptr(ut), D, ctypes.byref(s), self.stream),

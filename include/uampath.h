@@ -449,6 +449,7 @@ int uam_kernel_time(uam_ctx* ctx, double* ms_total, int64_t* launches);
  * raster with the similarity-form geometry, the default for packed rasters and batches >=
  * UAM_OPT_SORTED_MIN_PATHS paths), "K2g+pack" (the same with per-segment geometry:
  * UAM_OPT_K2G_SIM = 0 or maxratio_smooth), "K4h+pack" (the packed volume, K2h's form),
+ * "K2hx+pack" / "K4hx+pack" (their exact-sum forms, UAM_OPT_EXACT_SUM / _VOLUME),
  * "K2s+pack" / "K2s+skip" / "K2s" (segment-sorted raster, sequential sums), "K2+skip" / "K2"
  * (lane per path), "K2w" (wave per path), "K2d" (D > 16), "K3b", "K3", "K3d", "K4", "K4w";
  * "" before the first call.  The string is static (never freed).  For benchmarks and tests:
@@ -525,7 +526,10 @@ int32_t uam_last_group(const uam_ctx* ctx);
  *                                voxels, 16-B voxels in no-fly / psi columns).  Same outputs.
  *   UAM_OPT_EXACT_SUM            0 (default): K2h's raster sums in float64, in group order;
  *                                1: as exact integers, independent of every option above (the
- *                                section "Exact, order-independent raster sums" below) */
+ *                                section "Exact, order-independent raster sums" below)
+ *   UAM_OPT_EXACT_SUM_VOLUME     0 (default): K4h's voxel sums in float64, in group order;
+ *                                1: as exact integers, independent of every option above (the
+ *                                section "Exact, order-independent volume sums" below) */
 enum {
     UAM_OPT_GROUP = 1,
     UAM_OPT_SORTED_MIN_PATHS = 2,
@@ -548,7 +552,8 @@ enum {
     UAM_OPT_K4H_TERRAIN = 21,
     UAM_OPT_TEST_SORT_FAULT = 22, /* tests only: 1 makes the next sorted calls flag their sort as
                                      inconsistent (the uam_device_status path); 0 (default) off */
-    UAM_OPT_EXACT_SUM = 23        /* 0 (default) / 1: exact, order-independent raster sums (below) */
+    UAM_OPT_EXACT_SUM = 23,       /* 0 (default) / 1: exact, order-independent raster sums (below) */
+    UAM_OPT_EXACT_SUM_VOLUME = 24 /* 0 (default) / 1: the same for the volume, K4h (below) */
 };
 int uam_set_option(uam_ctx* ctx, int32_t option, int64_t value);
 int uam_get_option(const uam_ctx* ctx, int32_t option, int64_t* value);
@@ -585,8 +590,9 @@ int uam_get_option(const uam_ctx* ctx, int32_t option, int64_t* value);
  * apply; uam_last_group reports G as usual) and never falls back to ordered sums: UAM_E_STATE
  * when no sum scale is set, UAM_E_INVALID (reason in uam_last_error) for a batch K2h does not
  * take -- no packed_dev, maxratio_smooth, UAM_OPT_K2G_SIM = 0, UAM_OPT_GROUP = 0, D > 16,
- * N > 4096, a packed copy of 4 GiB or more.  Analytic mode, uam_eval_waypoints, the volume
- * (K4h) and uam_refine ignore the option.
+ * N > 4096, a packed copy of 4 GiB or more.  Analytic mode, uam_eval_waypoints and uam_refine
+ * ignore the option, and so does the volume: uam_eval_generated3d ignores UAM_OPT_EXACT_SUM,
+ * and UAM_OPT_EXACT_SUM_VOLUME is its own option (the next section).
  *
  * uam_raster_sum_scale writes the raster's 16-byte scale {e_phi, e_psi, flags, 0} to the
  * caller's device buffer scale_dev (flags: bits 0-2 = a phi cell holds NaN / +inf / -inf, bits
@@ -604,6 +610,52 @@ int uam_raster_sum_scale(uam_ctx* ctx, const uam_raster_desc* desc, const void* 
 int uam_set_sum_scale(uam_ctx* ctx, const int32_t* scale_dev);
 int uam_exact_sum_host(const float* values, int64_t n, int32_t e, double* sum_out,
                        int32_t* e_out);
+
+/* ---- Exact, order-independent volume sums (UAM_OPT_EXACT_SUM_VOLUME = 1; off by default) -----
+ * K4h's default sums add each path's risk / N and psi_nfz terms as float64 in group order, and
+ * a batch K4h does not take runs K4 / K4w with sequential sums, so the bits of cost, nfz_sum and
+ * best_fval_idx depend on UAM_OPT_GROUP and on the batch size.  With the option on they depend
+ * on the path and the volume only -- not on the group length, the chunk, the sort key (tiles,
+ * bands, curve), the terrain form, the batch size or the sharding.  A separate option:
+ * UAM_OPT_EXACT_SUM keeps its meaning (the raster only), and with this one off every call gives
+ * the bits it gave before.
+ * Definition: the raster section's, applied to the two float32 fields of the volume's voxels
+ * (risk, and separately psi_nfz):
+ *   scale     e_risk and e_psi = max(1, largest biased exponent field among the finite words)
+ *             - 126, taken over all ny nx nz voxels of vol_dev's voxel section {risk, psi_nfz};
+ *             the column plane is not included; a field with no finite nonzero voxel gives -125
+ *   term, truncation rule, 128-bit sum, single rounding fl(S) and side flags: exactly as the
+ *             raster section states them (the same inline functions)
+ *   a path adds the words of the voxel under each of its W waypoints that lies inside the
+ *             volume (x, y and z); waypoints outside the volume, code-0 column blocks and
+ *             padding slots add 0.  The psi_nfz word of a code-2 block is the packed |psi| word:
+ *             code 2 holds no negative psi, so the term is the voxel's own, and a positive NaN
+ *             or +inf still raises its flag
+ * Path outputs with the option on: nfz_sum = fl(S_psi); cost = (double)(N+1) L + fl(S_risk) /
+ * (double)N (a true division); best_fval_idx = the selection rule on that cost; length_q,
+ * length, kin_sum, nfz_hits, offmap, min_clearance, below_terrain and best_length_idx are
+ * exactly K4h's.  Against the default sums: rounding only, |cost_on - cost_off| <=
+ * 2 W 2^-53 (sum |risk_j| / N + (N+1) L), |nfz_on - nfz_off| <= 2 W 2^-53 sum |psi_j|.
+ * Dispatch: uam_eval_generated3d runs K4h's exact form at every batch size (uam_last_kernel
+ * "K4hx+pack"; UAM_OPT_SORTED_MIN_PATHS and UAM_OPT_WAVE_MAX_PATHS do not apply; uam_last_group
+ * reports G as usual) and never falls back to K4 / K4w or to ordered sums: UAM_E_STATE when no
+ * volume sum scale is set, UAM_E_INVALID (reason in uam_last_error) for a batch K4h does not
+ * take -- no packed_dev, maxratio_smooth, UAM_OPT_K2G_SIM = 0, UAM_OPT_GROUP = 0, D > 16,
+ * N > 4096, a unit-arc table or packed header too large for LDS, more (tile, band) bins than
+ * the sort holds, 2^31 or more paths or (path, group) items, a packed copy K4h stands aside for
+ * (4 GiB or more, 2^24 entries a layer or columns a side).  The errors are raised on the host
+ * before any launch; the context stays usable.
+ *
+ * uam_volume_sum_scale writes the volume's 16-byte scale {e_risk, e_psi, flags, 0} to the
+ * caller's device buffer scale_dev (flags: bits 0-2 = a risk word holds NaN / +inf / -inf, bits
+ * 3-5 = a psi_nfz word does -- the raster word's layout), asynchronously on stream, no host
+ * sync.  Integer maxima and ORs: the words do not depend on the reduction's order.  Like the
+ * packed copy it is a derived, untracked copy of vol_dev: rebuild it whenever the voxels change.
+ * uam_set_volume_sum_scale: the context keeps the pointer (not the words) for the
+ * uam_eval_generated3d calls that follow; NULL clears it.  Independent of uam_set_sum_scale. */
+int uam_volume_sum_scale(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol_dev,
+                         int32_t* scale_dev, uam_stream stream);
+int uam_set_volume_sum_scale(uam_ctx* ctx, const int32_t* scale_dev);
 
 /* Workspace bytes uam_refine needs for n_paths (after uam_set_geometry/uam_set_params). */
 int64_t uam_refine_workspace_bytes(uam_ctx* ctx, int64_t n_paths,

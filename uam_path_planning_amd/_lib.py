@@ -25,7 +25,7 @@ OPTIONS = {"group": 1, "sorted_min_paths": 2, "k2s_segments": 3, "wave_max_paths
            "k8_tiled": 9, "k8_streams": 10, "k2g_tile_bits": 11, "k2g_lds_floor": 12,
            "k2g_chunk": 13, "k2g_curve": 14, "k2g_sim": 15, "k4h_band": 17,
            "k2h_lb_stride": 19, "k2h_terrain": 20, "k4h_terrain": 21,
-           "test_sort_fault": 22, "exact_sum": 23}
+           "test_sort_fault": 22, "exact_sum": 23, "exact_sum_volume": 24}
 INEQ_HALFPLANE, INEQ_ELLIPSE, INEQ_AXIS = 0, 1, 2
 MODE_ANALYTIC, MODE_RASTER, MODE_VOLUME = 0, 1, 2
 FLAG_NFZ, FLAG_MASK, FLAG_NODATA = 1, 2, 4
@@ -129,6 +129,8 @@ SIGNATURES = {
                                        _vp, _vp]),
     "uam_raster_sum_scale": (ctypes.c_int, [_vp, ctypes.POINTER(RasterDesc), _vp, _vp, _vp]),
     "uam_set_sum_scale": (ctypes.c_int, [_vp, _vp]),
+    "uam_volume_sum_scale": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp, _vp]),
+    "uam_set_volume_sum_scale": (ctypes.c_int, [_vp, _vp]),
     "uam_exact_sum_host": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int32, _f64p, _i32p]),
     "uam_argmin": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _vp,
                                   _vp]),

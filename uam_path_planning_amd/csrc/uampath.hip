@@ -6432,17 +6432,21 @@ __global__ __launch_bounds__(1024) void k_h_final_x(KParams p, KGrp kg, KOut out
 // words' side flags | the psi words' << 3.  Integer maxima and ORs only, so the words do not
 // depend on the reduction's order: k_sum_scale_init writes the neutral words, then every wave
 // of k_sum_scale folds its cells (a grid-stride loop) and issues one atomic per word.
+// V: the cell -- a raster's 16-B record {phi, psi_nfz, ...} (uint4) or a volume's 8-B voxel
+// {risk, psi_nfz} (uint2, uam_volume_sum_scale); the two fields are its first two words.
 __global__ void k_sum_scale_init(int32_t* __restrict__ scale) {
     if (threadIdx.x < 4) scale[threadIdx.x] = threadIdx.x < 2 ? X_E_MIN : 0;
 }
-__global__ __launch_bounds__(256) void k_sum_scale(const uint4* __restrict__ rec, int64_t cells,
+template <typename V>
+__global__ __launch_bounds__(256) void k_sum_scale(const V* __restrict__ rec, int64_t cells,
                                                    int32_t* __restrict__ scale) {
     int32_t ec = X_E_MIN, en = X_E_MIN;
     uint32_t fl = 0;
-    constexpr int U = 4;  // loads in flight per lane (past the end: the last cell again)
+    // 64 B of loads in flight per lane (past the end: the last cell again)
+    constexpr int U = 64 / (int)sizeof(V);
     const int64_t step = (int64_t)gridDim.x * 256;
     for (int64_t c0 = (int64_t)blockIdx.x * 256 + threadIdx.x; c0 < cells; c0 += step * U) {
-        uint4 r[U];
+        V r[U];
 #pragma unroll
         for (int k = 0; k < U; ++k) r[k] = rec[min(c0 + k * step, cells - 1)];
 #pragma unroll
@@ -6487,6 +6491,14 @@ struct alignas(16) VSlot {  // 32 B per (path, group)
     uint32_t pad;
 };
 
+struct alignas(16) VSlotX {  // the exact form's slot (UAM_OPT_EXACT_SUM_VOLUME): 48 B
+    uint64_t c_lo, c_hi;  // the sum of the group's risk terms
+    uint64_t n_lo, n_hi;  // the sum of its psi terms
+    double cm;            // as VSlot's
+    uint32_t cnt;         // as VSlot's | risk flags << 24 | psi flags << 27
+    uint32_t pad;
+};
+
 struct KVol4 {
     int32_t nx, ny, nz;
     double x0, y_top, z0, dz, inv_dx, inv_dy, inv_dz;
@@ -6507,6 +6519,9 @@ struct KVol4 {
     // layer42 entries a layer
     uint32_t layer42;
     int32_t nbx4;
+    // the exact form's scale words {e_risk, e_psi, flags, 0} (uam_volume_sum_scale; read by the
+    // EX kernels only, null otherwise)
+    const int32_t* __restrict__ xscale;
 };
 
 constexpr int VPK_CSHIFT = 3;           // code blocks of 8 x 8 columns
@@ -6782,7 +6797,12 @@ __global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
 //       !(z_w - ub_w >= E) && !(z_w - ub_w > Ub).  If w* holds M and is not taken: z - ub >= E
 //       gives M >= E >= M, and z - ub > Ub >= M is impossible.  NaN bounds (no bound) always
 //       fetch.
-template <int CH, bool TE>  // TE: the terrain in the entry (UAM_OPT_K2H_TERRAIN 1)
+// EX (UAM_OPT_EXACT_SUM_VOLUME; k_v_eval_x below): the risk and psi words added as 128-bit
+// integer terms at the volume's exponents e_risk / e_psi (x_term) into a VSlotX, the non-finite
+// ones as side flags.  One body for both forms, in the kernel itself: moved into an inlined
+// function, the EX = false instantiations no longer allocated the registers they had (DESIGN
+// §10), so the exact form is this kernel's third template flag and vs.xscale its scale.
+template <int CH, bool TE, bool EX = false>  // TE: the terrain in the entry (UAM_OPT_K4H_TERRAIN 1)
 __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(KParams p, KVol4 vs,
                                                                               KGrp kg) {
     PK_CODES_CHECK(CH);
@@ -6852,6 +6872,19 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
     const uint32_t layer42 = __builtin_amdgcn_readfirstlane(vs.layer42);
     double gc = 0.0, gn = 0.0, E = seed;
     uint32_t nh = 0, off = 0, bel = 0;
+    X128 xc = {0, 0}, xn = {0, 0};  // EX: the group's risk and psi terms
+    uint32_t xf = 0;                // EX: their side flags (risk | psi << 3)
+    // EX: the volume's exponents, read once per workgroup at a uniform address
+    int32_t e_risk = 0, e_psi = 0;
+    if constexpr (EX) {
+        e_risk = __builtin_amdgcn_readfirstlane(vs.xscale[0]);
+        e_psi = __builtin_amdgcn_readfirstlane(vs.xscale[1]);
+    }
+    // EX: one word into its field's sum (straight-line, as h_item's)
+    auto x_take = [&](X128& acc, uint32_t w, int32_t e, int fs) {
+        acc = x_add(acc, x_term(w, e));
+        xf |= x_word_flags(w) << fs;
+    };
     // one chunk ahead, as h_item: iteration c issues chunk c + 1 (B arrays) and consumes chunk
     // c (A arrays)
     // (the slot's layer rides in its kind word's high bits; consume recomputes its altitude)
@@ -6969,8 +7002,13 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
                     const float ter = __uint_as_float(rec ? r.z : hi);  // (+0 on nodata)
                     nh += (rec && (r.w & UAM_FLAG_NFZ)) ? 1u : 0u;
                     off += (vl && !in) ? 1u : 0u;
-                    gc = gc + over_n((double)__uint_as_float(risk));
-                    gn = gn + (rec ? (double)__uint_as_float(r.y) : 0.0);
+                    if constexpr (EX) {
+                        x_take(xc, risk, e_risk, 0);
+                        x_take(xn, rec ? r.y : 0u, e_psi, 3);
+                    } else {
+                        gc = gc + over_n((double)__uint_as_float(risk));
+                        gn = gn + (rec ? (double)__uint_as_float(r.y) : 0.0);
+                    }
                     const double z = vz_at(za, zb, s_jw[jcA + t]);
                     bel += (in && zc_of((int32_t)(kcA[t] >> 8)) < (double)ter) ? 1u : 0u;
                     E = in ? fmin(E, z - (double)ter) : E;
@@ -6980,8 +7018,13 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
                 float rter;
                 pk_terms_k(rA[t], kcA[t], risk, psi, hit, rter);
                 const bool c3 = (kcA[t] & 3u) == 3u;
-                gc = gc + over_n((double)__uint_as_float(risk));
-                gn = gn + (double)__uint_as_float(psi);
+                if constexpr (EX) {
+                    x_take(xc, risk, e_risk, 0);
+                    x_take(xn, psi, e_psi, 3);
+                } else {
+                    gc = gc + over_n((double)__uint_as_float(risk));
+                    gn = gn + (double)__uint_as_float(psi);
+                }
                 nh += hit;
                 off += (vl && !in) ? 1u : 0u;
                 // the exact terrain, where taken: v16's (code 3) or the fetched one
@@ -7000,6 +7043,16 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
             vinA = vinB, tkA = tkB, bvA = bvB, nvA = nvB, jcA = jc;
         }
     }
+    if constexpr (EX) {
+        VSlotX o;
+        o.c_lo = xc.lo, o.c_hi = xc.hi;
+        o.n_lo = xn.lo, o.n_hi = xn.hi;
+        o.cm = E;
+        o.cnt = nh | (off << 8) | (bel << 16) | (xf << 24);
+        o.pad = 0;
+        if (live) reinterpret_cast<VSlotX*>(kg.slot)[(int64_t)s * kg.P + path] = o;
+        return;
+    }
     VSlot o;
     o.cost = gc;
     o.psi = gn;
@@ -7008,13 +7061,21 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
     o.pad = 0;
     if (live) reinterpret_cast<VSlot*>(kg.slot)[(int64_t)s * kg.P + path] = o;
 }
+// the exact form (UAM_OPT_EXACT_SUM_VOLUME), k_v_eval's sibling: the same body with EX set
+template <int CH, bool TE>
+constexpr auto k_v_eval_x = k_v_eval<CH, TE, true>;
 
 // outputs of every path (block = 64 pairs x D): the similarity-form geometry (oracle sim_geo on
 // the pair's x/y), cost = (N+1) L + the risk / N partials in group order, min clearance, the
 // counts, and the main.py:175-180 selection
-__global__ __launch_bounds__(1024) void k_v_final(KParams p, KGrp kg, KOut out,
-                                                  int32_t* __restrict__ best_f,
-                                                  int32_t* __restrict__ best_l) {
+// EX (UAM_OPT_EXACT_SUM_VOLUME): a path's VSlotX sums added as integers and their flags ORed,
+// each field rounded once (x_result), cost = (N+1) L + fl(S_risk) / N, nfz_sum = fl(S_psi)
+template <bool EX>
+__device__ __forceinline__ void v_final_wg(KParams p, KGrp kg, KOut out,
+                                           int32_t* __restrict__ best_f,
+                                           int32_t* __restrict__ best_l, int32_t e_risk,
+                                           int32_t e_psi) {
+    using Slot = std::conditional_t<EX, VSlotX, VSlot>;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int D = kg.D, t = threadIdx.x;
     double* s_cost = smem;
@@ -7022,7 +7083,7 @@ __global__ __launch_bounds__(1024) void k_v_final(KParams p, KGrp kg, KOut out,
     const int64_t q0 = (int64_t)blockIdx.x * 64;
     const int qi = t / D, di = t - qi * D;
     const bool bad = *kg.err != 0;  // an inconsistent sort (k_g_scatter / k_v_hist)
-    const VSlot* slot = reinterpret_cast<const VSlot*>(kg.slot);
+    const Slot* slot = reinterpret_cast<const Slot*>(kg.slot);
     if (q0 + qi < kg.n_pairs) {
         const int64_t gp = (q0 + qi) * D + di;
         const double* pr = kg.pairs + (q0 + qi) * 6;
@@ -7046,14 +7107,26 @@ __global__ __launch_bounds__(1024) void k_v_final(KParams p, KGrp kg, KOut out,
         const double ksum = (h > 0.0 && h < INFINITY) ? h * u.e12 + u.e3 : 0.0;
         double cost = (double)(p.N + 1) * L, nsum = 0.0, cm = INFINITY;
         int32_t nh = 0, off = 0, bel = 0;
+        X128 xc = {0, 0}, xn = {0, 0};
+        uint32_t xfl = 0;
         for (int s = 0; s < kg.nseg; ++s) {
-            const VSlot g = slot[(int64_t)s * kg.P + gp];
-            cost = cost + g.cost;
-            nsum = nsum + g.psi;
+            const Slot g = slot[(int64_t)s * kg.P + gp];
+            if constexpr (EX) {
+                xc = x_add(xc, X128{g.c_lo, g.c_hi});
+                xn = x_add(xn, X128{g.n_lo, g.n_hi});
+                xfl |= g.cnt >> 24;
+            } else {
+                cost = cost + g.cost;
+                nsum = nsum + g.psi;
+            }
             cm = fmin(cm, g.cm);
             nh += (int32_t)(g.cnt & 255u);
             off += (int32_t)((g.cnt >> 8) & 255u);
             bel += (int32_t)((g.cnt >> 16) & 255u);
+        }
+        if constexpr (EX) {  // one rounding per field, a true division
+            cost = cost + x_result(xc, xfl & 7u, e_risk) / (double)p.N;
+            nsum = x_result(xn, (xfl >> 3) & 7u, e_psi);
         }
         put_outputs(out, gp, bad, cost, L, len, ksum, nsum, cm, nh, off, bel);
         s_cost[di * 64 + qi] = cost;
@@ -7061,6 +7134,19 @@ __global__ __launch_bounds__(1024) void k_v_final(KParams p, KGrp kg, KOut out,
     }
     __syncthreads();
     put_selection(kg, bad, q0, t, s_cost, s_len, best_f, best_l);
+}
+__global__ __launch_bounds__(1024) void k_v_final(KParams p, KGrp kg, KOut out,
+                                                  int32_t* __restrict__ best_f,
+                                                  int32_t* __restrict__ best_l) {
+    v_final_wg<false>(p, kg, out, best_f, best_l, 0, 0);
+}
+__global__ __launch_bounds__(1024) void k_v_final_x(KParams p, KGrp kg, KOut out,
+                                                    int32_t* __restrict__ best_f,
+                                                    int32_t* __restrict__ best_l,
+                                                    const int32_t* __restrict__ scale) {
+    const int32_t e_risk = __builtin_amdgcn_readfirstlane(scale[0]);
+    const int32_t e_psi = __builtin_amdgcn_readfirstlane(scale[1]);
+    v_final_wg<true>(p, kg, out, best_f, best_l, e_risk, e_psi);
 }
 
 }  // namespace
@@ -7162,6 +7248,8 @@ struct uam_ctx {
     int test_sort_fault = 0;    // UAM_OPT_TEST_SORT_FAULT (tests only)
     int exact_sum = 0;          // UAM_OPT_EXACT_SUM: K2h's raster sums as exact integers
     const int32_t* sum_scale = nullptr;  // uam_set_sum_scale: the caller's device words
+    int exact_sum_vol = 0;      // UAM_OPT_EXACT_SUM_VOLUME: K4h's voxel sums as exact integers
+    const int32_t* vol_sum_scale = nullptr;  // uam_set_volume_sum_scale: the caller's words
 
 };
 
@@ -7953,6 +8041,12 @@ int uam_set_option(uam_ctx* ctx, int32_t option, int64_t value) {
                             (long long)value);
             ctx->exact_sum = (int)value;
             return UAM_OK;
+        case UAM_OPT_EXACT_SUM_VOLUME:
+            if (value != 0 && value != 1)
+                return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME %lld is not 0 or 1",
+                            (long long)value);
+            ctx->exact_sum_vol = (int)value;
+            return UAM_OK;
         case UAM_OPT_K2H_LB_STRIDE:
             if (value < 0 || value > 1024)
                 return fail(UAM_E_INVALID, "UAM_OPT_K2H_LB_STRIDE %lld outside [0, 1024]",
@@ -7997,6 +8091,7 @@ int uam_get_option(const uam_ctx* ctx, int32_t option, int64_t* value) {
         case UAM_OPT_K4H_TERRAIN: *value = ctx->k4h_te; return UAM_OK;
         case UAM_OPT_TEST_SORT_FAULT: *value = ctx->test_sort_fault; return UAM_OK;
         case UAM_OPT_EXACT_SUM: *value = ctx->exact_sum; return UAM_OK;
+        case UAM_OPT_EXACT_SUM_VOLUME: *value = ctx->exact_sum_vol; return UAM_OK;
         case UAM_OPT_K4H_BAND: *value = ctx->k4h_band; return UAM_OK;
         case UAM_OPT_K2G_CURVE: *value = ctx->k2g_curve; return UAM_OK;
 
@@ -8614,17 +8709,32 @@ static int launch_grouped(uam_ctx* ctx, const KRaster& kr, const void* rec, cons
 
 // K4h launch (the packed volume in K2h's form); returns 1 if launched, 0 if the batch is not
 // one it takes (the caller runs K4).  Scratch: the pair-order scratch (order_scratch).
+// UAM_OPT_EXACT_SUM_VOLUME: the exact form (k_v_eval_x / k_v_final_x, 48-B slots) at every batch
+// size; it never stands aside for another sum order, so a batch K4h does not take is an error
+// with its reason, raised before any launch.
 static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
                             const double* utab, int32_t D, const KOut& ko, int32_t* best_f,
                             int32_t* best_l, hipStream_t s) {
     const int G = ctx->k2g_group;
-    if (G < 1 || G > G_MAXLEN || ko.cells || ko.g_rows || D > 16 || ctx->kp.maxratio_smooth ||
-        !ctx->k2g_sim || !kv.pk || ctx->kp.N > 4096)
-        return 0;
+    const bool exact = ctx->exact_sum_vol != 0;
+    auto no = [&](const char* why) {
+        return exact ? fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME needs K4h: %s", why) : 0;
+    };
+    if (G < 1 || G > G_MAXLEN) return no("UAM_OPT_GROUP is 0");
+    if (ko.cells || ko.g_rows) return no("cells or g_rows requested");
+    if (D > 16) return no("D > 16");
+    if (ctx->kp.maxratio_smooth) return no("maxratio_smooth is set");
+    if (!ctx->k2g_sim) return no("UAM_OPT_K2G_SIM is 0");
+    if (!kv.pk)
+        return no("the packed copy is 4 GiB or larger, or a layer or side holds 2^24 entries");
+    if (ctx->kp.N > 4096) return no("N > 4096");
     const int64_t W = ctx->kp.N + 2, P = n_pairs * D;
-    if (P < ctx->k2s_min || n_pairs > INT32_MAX / D) return 0;
-    if ((size_t)D * ctx->kp.N * 16 > (size_t)G_UTAB_LDS) return 0;
-    if ((size_t)kv.hwords * 4 > (size_t)VPK_HDR_LDS) return 0;
+    if (!exact && P < ctx->k2s_min) return 0;
+    if (n_pairs > INT32_MAX / D) return no("more than 2^31 paths");
+    if ((size_t)D * ctx->kp.N * 16 > (size_t)G_UTAB_LDS)
+        return no("the unit-arc table exceeds its LDS share");
+    if ((size_t)kv.hwords * 4 > (size_t)VPK_HDR_LDS)
+        return no("the packed header exceeds its LDS share");
     // workgroups per CU: 3 by default through an LDS floor of 40 000 B (UAM_OPT_K2G_LDS_FLOOR
     // sets another): fewer items resident per XCD, so fewer of their lines miss L2 -- round 5's
     // bound form, cfg5: 0.394 ms at 3 with 7 in flight, 0.397 at 5 (28 000 B), 0.428 at 2
@@ -8636,7 +8746,7 @@ static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6,
                                 (size_t)std::min(ctx->k2g_lds ? ctx->k2g_lds : 40000, 160 * 1024));
     const int nseg = (int)((W + G - 1) / G);
     const int64_t n_items = P * nseg;
-    if (n_items >= INT32_MAX) return 0;
+    if (n_items >= INT32_MAX) return no("more than 2^31 (path, group) items");
     // tiles: 8 x 8 by default (128^2 columns at 1024^2: cfg5 0.461 vs 0.491 ms at 16 x 16,
     // profiles/r04/vol2), UAM_OPT_K2G_TILE_BITS otherwise
     // (a tile-bits setting made for 2-D rasters may give more (tile, band) bins than the sort
@@ -8644,15 +8754,20 @@ static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6,
     int tbits = ctx->k2g_tbits ? ctx->k2g_tbits : 3;
     while (tbits > 1 && (2 << (2 * tbits)) * kv.nbands + 1 > G_BINS_MAX) --tbits;
     const int tiles = 1 << (2 * tbits);
-    if (tiles * kv.nbands * 2 + 1 > G_BINS_MAX) return 0;  // (more bands than bins: K4)
+    if (tiles * kv.nbands * 2 + 1 > G_BINS_MAX)  // (more bands than bins: K4)
+        return no("more (tile, band) bins than the sort holds");
     const int last_bin = (W % G) ? tiles * kv.nbands : 0;
     const int bins = tiles * kv.nbands + last_bin + 1;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const int64_t ncnt = (int64_t)bins * G_NBK;
     const int64_t nsb = (ncnt + 256 * SCAN_ITEMS - 1) / (256 * SCAN_ITEMS);
-    if (nsb > 4096) return 0;
+    if (nsb > 4096) return no("the sort's counts exceed 4096 scan blocks");
+    if (exact && !ctx->vol_sum_scale)
+        return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM_VOLUME is on and no volume sum scale is set "
+                                 "(uam_volume_sum_scale, uam_set_volume_sum_scale)");
     const size_t b_key = al((size_t)n_items * 2), b_cnt = al((size_t)ncnt * 4),
-                 b_ord = al((size_t)n_items * 4), b_slot = al((size_t)n_items * sizeof(VSlot)),
+                 b_ord = al((size_t)n_items * 4),
+                 b_slot = al((size_t)n_items * (exact ? sizeof(VSlotX) : sizeof(VSlot))),
                  b_ug = al((size_t)D * sizeof(UGeo)), b_tot = al(4096 * 4), b_err = 256,
                  b_ubp = al((size_t)P * 8);
     char* w = nullptr;
@@ -8683,7 +8798,7 @@ static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6,
     kg.lb_stride = ctx->k2h_lbs;
     kg.n_items = n_items;
     size_t o = 0;
-    kg.slot = (GSlot*)(w + o), o += b_slot;  // VSlot
+    kg.slot = (GSlot*)(w + o), o += b_slot;  // VSlot / VSlotX
     kg.ugeo = (UGeo*)(w + o), o += b_ug;
     kg.order = (int32_t*)(w + o), o += b_ord;
     kg.cnt = (int32_t*)(w + o), o += b_cnt;
@@ -8721,22 +8836,40 @@ static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6,
                                        k_v_eval<16, false>, k_v_eval<6, true>,
                                        k_v_eval<7, true>,   k_v_eval<8, true>,
                                        k_v_eval<11, true>,  k_v_eval<16, true>};
-    const VEvalFn ev = vevals[(chl <= 6 ? 0 : chl == 7 ? 1 : chl <= 8 ? 2 : chl == 11 ? 3 : 4) +
-                              (ctx->k4h_te ? 5 : 0)];
+    static const VEvalFn vevalsx[10] = {k_v_eval_x<6, false>, k_v_eval_x<7, false>,
+                                         k_v_eval_x<8, false>,  k_v_eval_x<11, false>,
+                                         k_v_eval_x<16, false>, k_v_eval_x<6, true>,
+                                         k_v_eval_x<7, true>,   k_v_eval_x<8, true>,
+                                         k_v_eval_x<11, true>,  k_v_eval_x<16, true>};
+    const int vi = (chl <= 6 ? 0 : chl == 7 ? 1 : chl <= 8 ? 2 : chl == 11 ? 3 : 4) +
+                   (ctx->k4h_te ? 5 : 0);
+    const VEvalFn ev = vevals[vi];
     if (lds > 64 * 1024 && !ctx->k4h_attrs) {
         for (VEvalFn f : vevals)
             HIP_TRY(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         160 * 1024));
+        for (VEvalFn f : vevalsx)
+            HIP_TRY(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        160 * 1024));
         ctx->k4h_attrs = true;
     }
-    hipLaunchKernelGGL(ev, ge, dim3(256), lds, s, ctx->kp, kv, kg);
-    hipLaunchKernelGGL(k_v_final, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64 * D),
-                       (size_t)2 * 64 * D * sizeof(double), s, ctx->kp, kg, ko, best_f, best_l);
+    const dim3 gf((unsigned)((n_pairs + 63) / 64));
+    const size_t lds_f = (size_t)2 * 64 * D * sizeof(double);
+    if (exact) {
+        KVol4 kvx = kv;
+        kvx.xscale = ctx->vol_sum_scale;
+        hipLaunchKernelGGL(vevalsx[vi], ge, dim3(256), lds, s, ctx->kp, kvx, kg);
+        hipLaunchKernelGGL(k_v_final_x, gf, dim3(64 * D), lds_f, s, ctx->kp, kg, ko, best_f,
+                           best_l, ctx->vol_sum_scale);
+    } else {
+        hipLaunchKernelGGL(ev, ge, dim3(256), lds, s, ctx->kp, kv, kg);
+        hipLaunchKernelGGL(k_v_final, gf, dim3(64 * D), lds_f, s, ctx->kp, kg, ko, best_f, best_l);
+    }
     if (hipGetLastError() != hipSuccess) return fail(UAM_E_HIP, "grouped volume evaluation launch");
     st = ktime_end(ctx, s);
     if (st) return st;
     ctx->last_group = G;
-    ctx->last_kernel = "K4h+pack";
+    ctx->last_kernel = exact ? "K4hx+pack" : "K4h+pack";
     st = order_done(ctx, s);
     return st ? st : 1;
 }
@@ -9138,7 +9271,7 @@ int uam_raster_sum_scale(uam_ctx* ctx, const uam_raster_desc* desc, const void* 
     hipLaunchKernelGGL(k_sum_scale_init, dim3(1), dim3(64), 0, (hipStream_t)stream, scale);
     // 8 cells a lane at least, 2048 workgroups at most (the atomics: one per wave and word)
     const unsigned grid = (unsigned)std::min<int64_t>((cells + 2047) / 2048, 2048);
-    hipLaunchKernelGGL(k_sum_scale, dim3(grid), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_sum_scale<uint4>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
                        (const uint4*)rec, cells, scale);
     HIP_TRY(hipGetLastError());
     return UAM_OK;
@@ -9147,6 +9280,12 @@ int uam_raster_sum_scale(uam_ctx* ctx, const uam_raster_desc* desc, const void* 
 int uam_set_sum_scale(uam_ctx* ctx, const int32_t* scale) {
     if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
     ctx->sum_scale = scale;
+    return UAM_OK;
+}
+
+int uam_set_volume_sum_scale(uam_ctx* ctx, const int32_t* scale) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    ctx->vol_sum_scale = scale;
     return UAM_OK;
 }
 
@@ -9247,6 +9386,25 @@ int uam_volume_build(uam_ctx* ctx, const uam_volume_desc* vd, const void* rec2d,
                        (hipStream_t)stream, (const uint2*)((char*)vol + vol_col_offset(vd)),
                        vd->nx, vd->ny, kv.cshift, kv.cnbx, nreal, kv.cwords,
                        (uint32_t*)((char*)vol + vol_bits_offset(vd)));
+    HIP_TRY(hipGetLastError());
+    return UAM_OK;
+}
+
+// the exact sums' scale of a volume's voxel section (the column plane holds neither field)
+int uam_volume_sum_scale(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                         int32_t* scale, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    KVolume kv;
+    const int st = make_kvolume(vd, &kv);
+    if (st) return st;
+    if (!vol || !scale) return fail(UAM_E_INVALID, "vol/scale is NULL");
+    DeviceGuard dg(ctx->device);
+    const int64_t voxels = (int64_t)vd->nx * vd->ny * vd->nz;
+    hipLaunchKernelGGL(k_sum_scale_init, dim3(1), dim3(64), 0, (hipStream_t)stream, scale);
+    // 16 voxels a lane at least, 2048 workgroups at most (the atomics: one per wave and word)
+    const unsigned grid = (unsigned)std::min<int64_t>((voxels + 4095) / 4096, 2048);
+    hipLaunchKernelGGL(k_sum_scale<uint2>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                       (const uint2*)vol, voxels, scale);
     HIP_TRY(hipGetLastError());
     return UAM_OK;
 }
@@ -9394,6 +9552,14 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
         const int st = device_status(ctx);
         if (st) return st;
     }
+    // UAM_OPT_EXACT_SUM_VOLUME: K4h's exact form at every batch size or an error (no K4 / K4w,
+    // whose ordered sums would make the bits depend on the batch size)
+    const bool exact = ctx && ctx->exact_sum_vol;
+    if (exact && !packed) {
+        const int st = check_ctx(ctx, true);
+        if (st) return st;
+        return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME needs K4h: no packed_dev");
+    }
     if (packed) {
         int st = check_ctx(ctx, true);
         if (st) return st;
@@ -9418,12 +9584,14 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
         kv.nbands = ((vd->nz - 1) >> zs) + 1;
         const KOut ko = make_kout(out);
         DeviceGuard dg(ctx->device);
-        if (!want_wave(ctx, n_pairs * D)) {
+        if (exact || !want_wave(ctx, n_pairs * D)) {
             st = launch_grouped3d(ctx, kv, pairs6, n_pairs, utab, D, ko,
                                   out ? out->best_fval_idx : nullptr,
                                   out ? out->best_length_idx : nullptr, (hipStream_t)stream);
             if (st < 0) return st;
-            if (st == 1) return UAM_OK;
+            if (st == 1) return UAM_OK;  // last_kernel: "K4h+pack" / "K4hx+pack"
+            if (exact)
+                return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME: the batch did not run K4h");
         }
     }
     return eval_generated3d_vol(ctx, vd, vol, pairs6, n_pairs, utab, D, out, stream);

@@ -104,7 +104,8 @@ def broadcast_raster(raster, src=0, group=None, engine=None, rebuild=None):
     receiver's OLD records, so they are rebuilt from the broadcast records with `rebuild`
     (default: `engine`) or, with no engine at hand, dropped (the evaluation then gathers rec);
     a RiskVolume, whose buffer is broadcast and whose packed copy (K4h) is rebuilt
-    (`volume_pack`) or dropped the same way; or a bare tensor (rec of a CostRaster, a volume's
+    (`volume_pack`) or dropped the same way and whose exact-sum scale (sum_scale) is reset on
+    every path; or a bare tensor (rec of a CostRaster, a volume's
     buffer), broadcast as is -- its caller owns any derived copy.  With an engine whose communicator init_raster_comm set up, the
     bytes move by libuampath's RCCL broadcast (uam_bcast_raster, xGMI on the GPU node), whose
     ranks are the process group's ranks (src is converted); without one (CPU tensors: the gloo
@@ -128,6 +129,9 @@ def broadcast_raster(raster, src=0, group=None, engine=None, rebuild=None):
     secs = time.perf_counter() - t0
     eng = rebuild if rebuild is not None else engine
     if volume:
+        # the exact sums' scale was derived from the old voxels (packed copy or not)
+        if hasattr(raster, "sum_scale"):
+            raster.sum_scale = None
         if raster.packed is not None:
             if eng is not None:
                 eng.volume_pack(raster)

@@ -127,6 +127,11 @@ class RiskVolume:
     # when buf (or a view of it: vox, cols) was written in place since (torch's version counter)
     packed: object = field(repr=False, default=None)
     packed_version: int = field(repr=False, default=-1)
+    # the voxels' exponents and flags for the exact sums (Engine.volume_sum_scale: [4] int32
+    # {e_risk, e_psi, flags, 0}); None until an evaluation with the "exact_sum_volume" option
+    # needs it, recomputed by the rule that repacks the packed copy; volume_pack resets it
+    sum_scale: object = field(repr=False, default=None)
+    sum_scale_version: int = field(repr=False, default=-1)
 
 
 def _ptr(t):
@@ -167,6 +172,7 @@ class Engine:
         self._ctx = h
         self._geom_sig = None
         self._exact_sum = False   # the "exact_sum" option as set_option last set it
+        self._exact_sum_volume = False   # "exact_sum_volume" likewise
         self.geometry = None
         self.params = None
 
@@ -360,15 +366,16 @@ class Engine:
 
     def last_kernel(self):
         """Which path evaluation the last eval_generated / eval_generated3d ran (uam_last_kernel:
-        "K2h+pack", "K2hx+pack" (the exact sums), "K2g+pack", "K4h+pack", "K2s+pack", "K2+skip",
-        "K2w", "K3b", ...)."""
+        "K2h+pack", "K2hx+pack" (the exact sums), "K2g+pack", "K4h+pack", "K4hx+pack" (the
+        volume's exact sums), "K2s+pack", "K2+skip", "K2w", "K3b", ...)."""
         return self.lib.uam_last_kernel(self._ctx).decode()
 
     def last_group(self):
         """Waypoint-group length of the last eval_generated / eval_generated3d's sums
         (uam_last_group): G > 0 when a segment-grouped evaluation ran -- K2h / K4h (the oracle's
         orc_eval_generated_h order) or K2g (orc_eval_paths_g) -- 0 = sequential.  With the
-        "exact_sum" option G is still reported, but the raster sums do not depend on it."""
+        "exact_sum" option G is still reported, but the raster sums do not depend on it
+        ("exact_sum_volume": the volume's likewise)."""
         return int(self.lib.uam_last_group(self._ctx))
 
     def set_option(self, name, value):
@@ -377,12 +384,15 @@ class Engine:
         "k2s_segments", "wave_max_paths", "pair_order", "k1_rows", "k3b_segment",
         "k3b_points_per_lane", "k8_tiled", "k8_streams", "k2g_tile_bits", "k2g_lds_floor",
         "k2g_chunk", "k2g_curve", "k2g_sim", "k4h_band", "k2h_lb_stride", "k2h_terrain",
-        "k4h_terrain", "test_sort_fault" (tests only) and "exact_sum" (1: K2h's raster sums as
-        exact integers, independent of the group length -- "K2hx+pack")."""
+        "k4h_terrain", "test_sort_fault" (tests only), "exact_sum" (1: K2h's raster sums as
+        exact integers, independent of the group length -- "K2hx+pack") and "exact_sum_volume"
+        (1: the same for K4h's voxel sums in eval_generated3d -- "K4hx+pack")."""
         _lib.check(self.lib.uam_set_option(self._ctx, _lib.OPTIONS[name], int(value)),
                    "uam_set_option")
         if name == "exact_sum":
             self._exact_sum = bool(int(value))
+        elif name == "exact_sum_volume":
+            self._exact_sum_volume = bool(int(value))
 
     def get_option(self, name):
         v = ctypes.c_int64()
@@ -503,7 +513,24 @@ class Engine:
                    "uam_volume_pack")
         volume.packed = packed
         volume.packed_version = volume.buf._version
+        volume.sum_scale = None   # the voxels changed: the exponents are derived from them too
         return packed
+
+    def volume_sum_scale(self, volume):
+        """Fill volume.sum_scale, the exact sums' scale of the volume's voxels
+        (uam_volume_sum_scale: [4] int32 {e_risk, e_psi, flags, 0} on the device, no host sync);
+        returns volume.  A derived copy like the packed one: eval_generated3d computes it when
+        the "exact_sum_volume" option is on and it is None or torch's version counter of
+        volume.buf moved since; volume_pack -- the call after a write that bypasses torch --
+        resets it."""
+        torch = _torch()
+        sc = self.empty((4,), torch.int32)
+        _lib.check(self.lib.uam_volume_sum_scale(self._ctx, ctypes.byref(volume.geo.as_struct()),
+                                                 _ptr(volume.buf), _ptr(sc), self.stream),
+                   "uam_volume_sum_scale")
+        volume.sum_scale = sc
+        volume.sum_scale_version = volume.buf._version
+        return volume
 
     def eval_generated3d(self, pairs6, utab, volume, outputs=None):
         """pairs6 [Q, 6] = (x0, y0, z0, xf, yf, zf) (km, km, m); path p = q*D + d."""
@@ -522,6 +549,11 @@ class Engine:
                                  n_pairs=Q)
         if volume.packed is not None and volume.buf._version != volume.packed_version:
             self.volume_pack(volume)   # the voxels changed since the copy: K4h reads only it
+        if self._exact_sum_volume:   # the exact sums' scale: computed once per voxel state
+            if volume.sum_scale is None or volume.buf._version != volume.sum_scale_version:
+                self.volume_sum_scale(volume)
+            _lib.check(self.lib.uam_set_volume_sum_scale(self._ctx, _ptr(volume.sum_scale)),
+                       "uam_set_volume_sum_scale")
         _lib.check(self.lib.uam_eval_generated3d(
             self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf),
             _ptr(volume.packed), _ptr(pr), Q, _ptr(ut), D, ctypes.byref(s), self.stream),

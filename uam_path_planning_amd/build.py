@@ -8,7 +8,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "uampath.hip")
 SRCS = [SRC, os.path.join(HERE, "csrc", "polyproc.cpp"), os.path.join(HERE, "csrc", "tiles.cpp")]
-DEPS = SRCS + [os.path.join(HERE, "csrc", "polyproc.h"), os.path.join(HERE, "csrc", "ccl_tile.inc")]
+# every source under csrc/ (the headers and the .inc pieces uampath.hip includes too): a touched
+# one must rebuild the library
+DEPS = sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))
+              if f.endswith((".hip", ".inc", ".cpp", ".h")))
 HEADER = os.path.join(ROOT, "include", "uampath.h")
 OUT = os.path.join(HERE, "lib", "libuampath.so")
 ARCH = os.environ.get("UAM_OFFLOAD_ARCH", "gfx950")

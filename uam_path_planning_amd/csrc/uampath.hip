@@ -7202,7 +7202,7 @@ struct uam_ctx {
     int64_t k2s_min = 65536;    // K2g / K2s: smallest batch in paths (UAM_OPT_SORTED_MIN_PATHS)
     bool k2s_attrs = false;     // K2s dynamic-LDS attributes raised on this context's device
     bool k2h_attrs = false;     // K2h's dynamic-LDS attributes raised on this context's device
-    bool k4h_hist_attr = false;  // k_v_hist's, likewise
+    bool k2h_hist_attr = false, k4h_hist_attr = false;  // k_g_hist's and k_v_hist's, likewise
     bool k2g_attrs = false;     // K2g dynamic-LDS attributes raised on this context's device
     bool k4h_attrs = false;     // the same for K4h
     void* d_ord = nullptr;      // pair_order scratch (grow-only)
@@ -7317,6 +7317,24 @@ int err_word(uam_ctx* ctx, KGrp* kg) {
     kg->herr = ctx->d_err;
     kg->test_fault = ctx->test_sort_fault;
     return UAM_OK;
+}
+
+// The dynamic-LDS limit of every kernel in the tables raised to `limit` bytes, once per context
+// = per device (the caller's DeviceGuard is active): *done is the context's flag of the tables.
+template <class Tab>
+int raise_lds_table(const Tab& fns, int limit) {
+    for (auto f : fns)
+        HIP_TRY(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    limit));
+    return UAM_OK;
+}
+template <class... Tab>
+int raise_lds(bool* done, int limit, const Tab&... tabs) {
+    if (*done) return UAM_OK;
+    int st = UAM_OK;
+    ((st = st ? st : raise_lds_table(tabs, limit)), ...);
+    *done = !st;
+    return st;
 }
 
 int device_status(uam_ctx* ctx) {
@@ -7946,157 +7964,97 @@ const char* uam_last_kernel(const uam_ctx* ctx) { return ctx ? ctx->last_kernel 
 
 int32_t uam_last_group(const uam_ctx* ctx) { return ctx ? ctx->last_group : 0; }
 
+// The options (include/uampath.h UAM_OPT_*), one entry each: the key, the context member both
+// uam_set_option and uam_get_option go through, the accept rule (null: any value, stored as
+// != 0) and the refusal's text.  The text is fail()'s format with the arguments (long long
+// value, int bound) in that order: a %lld, if any, comes before a %d, if any, and nothing else
+// converts (no compiler format check covers a table entry).
+struct OptDef {
+    int32_t key;
+    void (*set)(uam_ctx*, int64_t);
+    int64_t (*get)(const uam_ctx*);
+    bool (*ok)(int64_t);
+    const char* bad;
+    int bound;
+};
+#define UAM_OPT_MEMBER(M_)                                                          \
+    [](uam_ctx* c, int64_t v) { c->M_ = static_cast<decltype(c->M_)>(v); },         \
+        [](const uam_ctx* c) -> int64_t { return c->M_; }
+static bool opt_01(int64_t v) { return v == 0 || v == 1; }
+static bool opt_nonneg(int64_t v) { return v >= 0; }
+static const OptDef kOptions[] = {
+    {UAM_OPT_GROUP, UAM_OPT_MEMBER(k2g_group), [](int64_t v) { return v >= 0 && v <= G_MAXLEN; },
+     "UAM_OPT_GROUP %lld outside [0, %d]", G_MAXLEN},
+    {UAM_OPT_SORTED_MIN_PATHS, UAM_OPT_MEMBER(k2s_min), opt_nonneg, "UAM_OPT_SORTED_MIN_PATHS < 0"},
+    {UAM_OPT_K2S_SEGMENTS, UAM_OPT_MEMBER(k2s_segs),
+     [](int64_t v) { return v >= 2 && v <= SEG_MAX; }, "UAM_OPT_K2S_SEGMENTS %lld outside [2, %d]",
+     SEG_MAX},
+    {UAM_OPT_WAVE_MAX_PATHS, UAM_OPT_MEMBER(wave_max), opt_nonneg, "UAM_OPT_WAVE_MAX_PATHS < 0"},
+    {UAM_OPT_PAIR_ORDER, UAM_OPT_MEMBER(pair_order), nullptr, nullptr},
+    {UAM_OPT_K1_ROWS, UAM_OPT_MEMBER(k1_cpl),
+     [](int64_t v) { return v == 1 || v == 2 || v == 4 || v == 8; },
+     "UAM_OPT_K1_ROWS %lld not 1, 2, 4 or 8"},
+    {UAM_OPT_K3B_SEGMENT, UAM_OPT_MEMBER(k3b_seg),
+     [](int64_t v) { return v == 0 || v == 2 || v == 4 || v == 6 || v == 8 || v == 16; },
+     "UAM_OPT_K3B_SEGMENT %lld not 0, 2, 4, 6, 8 or 16"},
+    {UAM_OPT_K3B_POINTS_PER_LANE, UAM_OPT_MEMBER(k3b_cpl),
+     [](int64_t v) { return v == 1 || v == 2; }, "UAM_OPT_K3B_POINTS_PER_LANE %lld not 1 or 2"},
+    {UAM_OPT_K8_TILED, UAM_OPT_MEMBER(k8_tiled), nullptr, nullptr},
+    {UAM_OPT_K8_STREAMS, UAM_OPT_MEMBER(k8_nstreams), [](int64_t v) { return v >= 1 && v <= 8; },
+     "UAM_OPT_K8_STREAMS %lld outside [1, 8]"},
+    {UAM_OPT_K2G_TILE_BITS, UAM_OPT_MEMBER(k2g_tbits),
+     [](int64_t v) { return v == 0 || (v >= 3 && v <= G_TBITS_MAX); },
+     "UAM_OPT_K2G_TILE_BITS %lld not 0 or in [3, %d]", G_TBITS_MAX},
+    {UAM_OPT_K2G_LDS_FLOOR, UAM_OPT_MEMBER(k2g_lds),
+     [](int64_t v) { return v >= 0 && v <= 160 * 1024; },
+     "UAM_OPT_K2G_LDS_FLOOR outside [0, 163840]"},
+    {UAM_OPT_K2G_CHUNK, UAM_OPT_MEMBER(k2g_chunk),
+     [](int64_t v) {
+         return v == 0 || v == 6 || v == 7 || v == 8 || v == 11 || v == 16 || v == 21;
+     },
+     "UAM_OPT_K2G_CHUNK %lld not 0, 6, 7, 8, 11, 16 or 21"},
+    {UAM_OPT_K2G_CURVE, UAM_OPT_MEMBER(k2g_curve), opt_01, "UAM_OPT_K2G_CURVE %lld not 0 or 1"},
+    {UAM_OPT_K2G_SIM, UAM_OPT_MEMBER(k2g_sim), opt_01, "UAM_OPT_K2G_SIM %lld not 0 or 1"},
+    {UAM_OPT_K4H_BAND, UAM_OPT_MEMBER(k4h_band),
+     [](int64_t v) { return v >= 0 && v <= 64 && !(v & (v - 1)); },
+     "UAM_OPT_K4H_BAND %lld not 0 or a power of two <= 64"},
+    {UAM_OPT_K2H_LB_STRIDE, UAM_OPT_MEMBER(k2h_lbs),
+     [](int64_t v) { return v >= 0 && v <= 1024; },
+     "UAM_OPT_K2H_LB_STRIDE %lld outside [0, 1024]"},
+    {UAM_OPT_K2H_TERRAIN, UAM_OPT_MEMBER(k2h_te), opt_01,
+     "UAM_OPT_K2H_TERRAIN %lld is not 0 or 1"},
+    {UAM_OPT_K4H_TERRAIN, UAM_OPT_MEMBER(k4h_te), opt_01,
+     "UAM_OPT_K4H_TERRAIN %lld is not 0 or 1"},
+    {UAM_OPT_TEST_SORT_FAULT, UAM_OPT_MEMBER(test_sort_fault), opt_01,
+     "UAM_OPT_TEST_SORT_FAULT %lld is not 0 or 1"},
+    {UAM_OPT_EXACT_SUM, UAM_OPT_MEMBER(exact_sum), opt_01, "UAM_OPT_EXACT_SUM %lld is not 0 or 1"},
+    {UAM_OPT_EXACT_SUM_VOLUME, UAM_OPT_MEMBER(exact_sum_vol), opt_01,
+     "UAM_OPT_EXACT_SUM_VOLUME %lld is not 0 or 1"},
+};
+#undef UAM_OPT_MEMBER
+
+static const OptDef* find_option(int32_t option) {
+    for (const OptDef& d : kOptions)
+        if (d.key == option) return &d;
+    fail(UAM_E_INVALID, "unknown option %d", option);
+    return nullptr;
+}
+
 int uam_set_option(uam_ctx* ctx, int32_t option, int64_t value) {
     if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
-    switch (option) {
-        case UAM_OPT_GROUP:
-            if (value < 0 || value > G_MAXLEN)
-                return fail(UAM_E_INVALID, "UAM_OPT_GROUP %lld outside [0, %d]", (long long)value,
-                            G_MAXLEN);
-            ctx->k2g_group = (int)value;
-            return UAM_OK;
-        case UAM_OPT_SORTED_MIN_PATHS:
-            if (value < 0) return fail(UAM_E_INVALID, "UAM_OPT_SORTED_MIN_PATHS < 0");
-            ctx->k2s_min = value;
-            return UAM_OK;
-        case UAM_OPT_K2S_SEGMENTS:
-            if (value < 2 || value > SEG_MAX)
-                return fail(UAM_E_INVALID, "UAM_OPT_K2S_SEGMENTS %lld outside [2, %d]",
-                            (long long)value, SEG_MAX);
-            ctx->k2s_segs = (int)value;
-            return UAM_OK;
-        case UAM_OPT_WAVE_MAX_PATHS:
-            if (value < 0) return fail(UAM_E_INVALID, "UAM_OPT_WAVE_MAX_PATHS < 0");
-            ctx->wave_max = value;
-            return UAM_OK;
-        case UAM_OPT_PAIR_ORDER:
-            ctx->pair_order = value != 0;
-            return UAM_OK;
-        case UAM_OPT_K1_ROWS:
-            if (value != 1 && value != 2 && value != 4 && value != 8)
-                return fail(UAM_E_INVALID, "UAM_OPT_K1_ROWS %lld not 1, 2, 4 or 8",
-                            (long long)value);
-            ctx->k1_cpl = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K3B_SEGMENT:
-            if (value != 0 && value != 2 && value != 4 && value != 6 && value != 8 && value != 16)
-                return fail(UAM_E_INVALID, "UAM_OPT_K3B_SEGMENT %lld not 0, 2, 4, 6, 8 or 16",
-                            (long long)value);
-            ctx->k3b_seg = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K3B_POINTS_PER_LANE:
-            if (value != 1 && value != 2)
-                return fail(UAM_E_INVALID, "UAM_OPT_K3B_POINTS_PER_LANE %lld not 1 or 2",
-                            (long long)value);
-            ctx->k3b_cpl = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K8_TILED:
-            ctx->k8_tiled = value != 0;
-            return UAM_OK;
-        case UAM_OPT_K2G_TILE_BITS:
-            if (value != 0 && (value < 3 || value > G_TBITS_MAX))
-                return fail(UAM_E_INVALID, "UAM_OPT_K2G_TILE_BITS %lld not 0 or in [3, %d]",
-                            (long long)value, G_TBITS_MAX);
-            ctx->k2g_tbits = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K2G_LDS_FLOOR:
-            if (value < 0 || value > 160 * 1024)
-                return fail(UAM_E_INVALID, "UAM_OPT_K2G_LDS_FLOOR outside [0, 163840]");
-            ctx->k2g_lds = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K2G_CURVE:
-            if (value != 0 && value != 1)
-                return fail(UAM_E_INVALID, "UAM_OPT_K2G_CURVE %lld not 0 or 1", (long long)value);
-            ctx->k2g_curve = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K2G_CHUNK:
-            if (value != 0 && value != 6 && value != 7 && value != 8 && value != 11 &&
-                value != 16 && value != 21)
-                return fail(UAM_E_INVALID, "UAM_OPT_K2G_CHUNK %lld not 0, 6, 7, 8, 11, 16 or 21",
-                            (long long)value);
-            ctx->k2g_chunk = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K4H_BAND:
-            if (value < 0 || value > 64 || (value & (value - 1)))
-                return fail(UAM_E_INVALID, "UAM_OPT_K4H_BAND %lld not 0 or a power of two <= 64",
-                            (long long)value);
-            ctx->k4h_band = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K2H_TERRAIN:
-        case UAM_OPT_K4H_TERRAIN:
-            if (value != 0 && value != 1)
-                return fail(UAM_E_INVALID, "UAM_OPT_K%cH_TERRAIN %lld is not 0 or 1",
-                            option == UAM_OPT_K2H_TERRAIN ? '2' : '4', (long long)value);
-            (option == UAM_OPT_K2H_TERRAIN ? ctx->k2h_te : ctx->k4h_te) = (int)value;
-            return UAM_OK;
-        case UAM_OPT_TEST_SORT_FAULT:
-            if (value != 0 && value != 1)
-                return fail(UAM_E_INVALID, "UAM_OPT_TEST_SORT_FAULT %lld is not 0 or 1",
-                            (long long)value);
-            ctx->test_sort_fault = (int)value;
-            return UAM_OK;
-        case UAM_OPT_EXACT_SUM:
-            if (value != 0 && value != 1)
-                return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM %lld is not 0 or 1",
-                            (long long)value);
-            ctx->exact_sum = (int)value;
-            return UAM_OK;
-        case UAM_OPT_EXACT_SUM_VOLUME:
-            if (value != 0 && value != 1)
-                return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME %lld is not 0 or 1",
-                            (long long)value);
-            ctx->exact_sum_vol = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K2H_LB_STRIDE:
-            if (value < 0 || value > 1024)
-                return fail(UAM_E_INVALID, "UAM_OPT_K2H_LB_STRIDE %lld outside [0, 1024]",
-                            (long long)value);
-            ctx->k2h_lbs = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K2G_SIM:
-            if (value != 0 && value != 1)
-                return fail(UAM_E_INVALID, "UAM_OPT_K2G_SIM %lld not 0 or 1", (long long)value);
-            ctx->k2g_sim = (int)value;
-            return UAM_OK;
-        case UAM_OPT_K8_STREAMS:
-            if (value < 1 || value > 8)
-                return fail(UAM_E_INVALID, "UAM_OPT_K8_STREAMS %lld outside [1, 8]",
-                            (long long)value);
-            ctx->k8_nstreams = (int)value;
-            return UAM_OK;
-        default:
-            return fail(UAM_E_INVALID, "unknown option %d", option);
-    }
+    const OptDef* d = find_option(option);
+    if (!d) return UAM_E_INVALID;
+    if (d->ok && !d->ok(value)) return fail(UAM_E_INVALID, d->bad, (long long)value, d->bound);
+    d->set(ctx, d->ok ? value : (int64_t)(value != 0));
+    return UAM_OK;
 }
 
 int uam_get_option(const uam_ctx* ctx, int32_t option, int64_t* value) {
     if (!ctx || !value) return fail(UAM_E_INVALID, "NULL argument");
-    switch (option) {
-        case UAM_OPT_GROUP: *value = ctx->k2g_group; return UAM_OK;
-        case UAM_OPT_SORTED_MIN_PATHS: *value = ctx->k2s_min; return UAM_OK;
-        case UAM_OPT_K2S_SEGMENTS: *value = ctx->k2s_segs; return UAM_OK;
-        case UAM_OPT_WAVE_MAX_PATHS: *value = ctx->wave_max; return UAM_OK;
-        case UAM_OPT_PAIR_ORDER: *value = ctx->pair_order ? 1 : 0; return UAM_OK;
-        case UAM_OPT_K1_ROWS: *value = ctx->k1_cpl; return UAM_OK;
-        case UAM_OPT_K3B_SEGMENT: *value = ctx->k3b_seg; return UAM_OK;
-        case UAM_OPT_K3B_POINTS_PER_LANE: *value = ctx->k3b_cpl; return UAM_OK;
-        case UAM_OPT_K8_TILED: *value = ctx->k8_tiled ? 1 : 0; return UAM_OK;
-        case UAM_OPT_K8_STREAMS: *value = ctx->k8_nstreams; return UAM_OK;
-        case UAM_OPT_K2G_TILE_BITS: *value = ctx->k2g_tbits; return UAM_OK;
-        case UAM_OPT_K2G_LDS_FLOOR: *value = ctx->k2g_lds; return UAM_OK;
-        case UAM_OPT_K2G_CHUNK: *value = ctx->k2g_chunk; return UAM_OK;
-        case UAM_OPT_K2G_SIM: *value = ctx->k2g_sim; return UAM_OK;
-        case UAM_OPT_K2H_LB_STRIDE: *value = ctx->k2h_lbs; return UAM_OK;
-        case UAM_OPT_K2H_TERRAIN: *value = ctx->k2h_te; return UAM_OK;
-        case UAM_OPT_K4H_TERRAIN: *value = ctx->k4h_te; return UAM_OK;
-        case UAM_OPT_TEST_SORT_FAULT: *value = ctx->test_sort_fault; return UAM_OK;
-        case UAM_OPT_EXACT_SUM: *value = ctx->exact_sum; return UAM_OK;
-        case UAM_OPT_EXACT_SUM_VOLUME: *value = ctx->exact_sum_vol; return UAM_OK;
-        case UAM_OPT_K4H_BAND: *value = ctx->k4h_band; return UAM_OK;
-        case UAM_OPT_K2G_CURVE: *value = ctx->k2g_curve; return UAM_OK;
-
-        default: return fail(UAM_E_INVALID, "unknown option %d", option);
-    }
+    const OptDef* d = find_option(option);
+    if (!d) return UAM_E_INVALID;
+    *value = d->get(ctx);
+    return UAM_OK;
 }
 
 int uam_kernel_time(uam_ctx* ctx, double* ms_total, int64_t* launches) {
@@ -8400,92 +8358,105 @@ static void magic_div(uint32_t D, uint64_t* m, int32_t* sh) {
     *m = (uint64_t)(((one << *sh) + D - 1) / D);
 }
 
-// One K2g / K2h launch sequence (segment-grouped raster evaluation): what grouped_plan decides
-// for a batch, then its scratch carved by grouped_carve, then the launches (grouped_sort: the
-// counting sort's histogram, scan and scatter; grouped_eval; grouped_final: the output launch)
+// One K2g / K2h / K4h launch sequence (segment-grouped evaluation of the packed raster or the
+// packed volume): what grouped_plan / grouped_plan3d decide for a batch -- each its refusals,
+// tile rule, slot, seed, LDS need and kernel tables around the common grouped_sizes -- then the
+// scratch carved by grouped_carve, then the launches (grouped_sort: the counting sort's
+// histogram, scan and scatter; grouped_eval; grouped_final: the output launch)
 using GEvalFn = void (*)(KParams, KRaster, KGrp, const uint4*);
 using HEvalFn = void (*)(KParams, KRaster, KGrp);
 using GFinalFn = void (*)(KParams, KGrp, KOut, int32_t*, int32_t*);
 using HEvalXFn = void (*)(KParams, KRaster, KGrp, const int32_t*);
 using HFinalXFn = void (*)(KParams, KGrp, KOut, int32_t*, int32_t*, const int32_t*);
+using VEvalFn = void (*)(KParams, KVol4, KGrp);
 struct GPlan {
     KGrp kg;
-    bool sim;                 // K2h (the similarity form); K2g otherwise
-    bool exact;               // K2h's exact form (UAM_OPT_EXACT_SUM): hevx / finx, 40-B slots
+    bool vol;                 // K4h (the packed volume); the packed raster otherwise
+    bool sim;                 // K2h / K4h (the similarity form); K2g otherwise
+    bool exact;               // the exact form (UAM_OPT_EXACT_SUM: hevx / finx, 40-B slots;
+                              // UAM_OPT_EXACT_SUM_VOLUME: vev / finx, 48-B slots)
+    const char* needs;        // how the exact form's refusals begin
+    const int32_t* scale;     // the exact form's sum scale (null: none set)
+    bool seeds;               // the histogram launch forms each path's seed (kg.lbp / kg.ubp)
     HEvalXFn hevx;
     HFinalXFn finx;
     int64_t ncnt, nsb;        // counts ([bins][G_NBK]) and scan blocks
-    size_t lds, hist_dyn, ubytes, bytes;  // eval / histogram dynamic LDS, arc rows, scratch
-    size_t b_key, b_cnt, b_tot, b_ord, b_slot, b_ug, b_err, b_lbp;
+    size_t lds, hist_dyn, bytes;  // eval / histogram dynamic LDS, scratch
+    size_t b_key, b_cnt, b_tot, b_ord, b_slot, b_ug, b_err, b_seed;
     int bs;                   // evaluation workgroup
     GEvalFn ev;
     HEvalFn hev;
+    VEvalFn vev;
     GFinalFn fin;
 };
 
-// the sequence a batch takes: 1 (pl filled, scratch not yet carved), 0 when the batch is not
-// one K2g / K2h takes, < 0 on error
-static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, int64_t n_pairs,
-                        const double* utab, int32_t D, const KOut& ko, GPlan* pl) {
-    const int G = ctx->k2g_group;
-    // the exact form never stands aside for another sum order: a batch K2h does not take is an
-    // error with its reason (at every size: UAM_OPT_SORTED_MIN_PATHS does not apply)
-    const bool exact = ctx->exact_sum != 0;
-    auto no = [&](const char* why) {
-        return exact ? fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM needs K2h: %s", why) : 0;
-    };
-    if (G < 1 || G > G_MAXLEN) return no("UAM_OPT_GROUP is 0");
-    if (!kr.pmap) return no("no packed_dev");
-    if (ko.g_rows) return no("g_rows requested");
-    if (D > 16) return no("D > 16");
-    const int64_t W = ctx->kp.N + 2, P = n_pairs * D;
-    if (!exact && P < ctx->k2s_min) return 0;
-    if (n_pairs > INT32_MAX / D) return no("more than 2^31 paths");
-    if (exact) {
-        if (!ctx->k2g_sim) return no("UAM_OPT_K2G_SIM is 0");
-        if (ctx->kp.maxratio_smooth) return no("maxratio_smooth is set");
-        if (!kr.pk) return no("the packed copy is 4 GiB or larger");
-        if (ctx->kp.N > 4096) return no("N > 4096");
-    }
-    const size_t ubytes = (size_t)D * ctx->kp.N * 16;  // the unit-arc rows, staged in LDS
-    if (ubytes > (size_t)G_UTAB_LDS) return no("the unit-arc table exceeds its LDS share");
-    const int nseg = (int)((W + G - 1) / G);
-    const int64_t n_items = P * nseg;
-    if (n_items >= INT32_MAX) return no("more than 2^31 (path, group) items");
-    int tbits = ctx->k2g_tbits;
-    if (tbits == 0) {  // tiles of ~256 x 256 cells ...
-        tbits = 3;
-        while (tbits < G_TBITS_MAX && (std::max(kr.nx, kr.ny) >> tbits) > 256) ++tbits;
+// the exact forms never stand aside for another sum order: a batch they do not take is an
+// error with its reason (at every size: UAM_OPT_SORTED_MIN_PATHS does not apply)
+static int grouped_no(const GPlan& pl, const char* why) {
+    return pl.exact ? fail(UAM_E_INVALID, "%s: %s", pl.needs, why) : 0;
+}
+
+// A family's tile bits for a batch of n_items over nx x ny cells in nbands bands: returns the
+// key's bins per group length (tiles, or tiles x bands), 0 when the sort cannot hold them
+using GTilesFn = int (*)(const uam_ctx*, int32_t nx, int32_t ny, int32_t nbands, int64_t n_items,
+                         int* tbits);
+
+static int raster_tiles(const uam_ctx* ctx, int32_t nx, int32_t ny, int32_t, int64_t n_items,
+                        int* tbits) {
+    int tb = ctx->k2g_tbits;
+    if (tb == 0) {  // tiles of ~256 x 256 cells ...
+        tb = 3;
+        while (tb < G_TBITS_MAX && (std::max(nx, ny) >> tb) > 256) ++tb;
         // ... but coarser for a small batch, so the sort's counts (bins x partitions) stay
         // within half its items (cfg4's rank share of 8, 500k items at 8192^2: tiles of 512^2
         // 0.175 ms against 0.178-0.181 at 256^2; the whole 1M-path job keeps 256^2: 0.900
         // against 0.958 ms; profiles/r06/c10)
-        while (tbits > 3 && ((int64_t)(2 << (2 * tbits)) + 1) * G_NBK > n_items / 2) --tbits;
+        while (tb > 3 && ((int64_t)(2 << (2 * tb)) + 1) * G_NBK > n_items / 2) --tb;
     }
-    const int tiles = 1 << (2 * tbits);
+    *tbits = tb;
+    return 1 << (2 * tb);
+}
+
+// tiles: 8 x 8 by default (128^2 columns at 1024^2: cfg5 0.461 vs 0.491 ms at 16 x 16,
+// profiles/r04/vol2), UAM_OPT_K2G_TILE_BITS otherwise
+// (a tile-bits setting made for 2-D rasters may give more (tile, band) bins than the sort
+// holds: the key then takes the finest tiles that fit, which moves no bit of the outputs)
+static int volume_tiles(const uam_ctx* ctx, int32_t, int32_t, int32_t nbands, int64_t,
+                        int* tbits) {
+    int tb = ctx->k2g_tbits ? ctx->k2g_tbits : 3;
+    while (tb > 1 && (2 << (2 * tb)) * nbands + 1 > G_BINS_MAX) --tb;
+    *tbits = tb;
+    const int tiles = 1 << (2 * tb);
+    return tiles * nbands * 2 + 1 > G_BINS_MAX ? 0 : tiles * nbands;  // (more bands than bins: K4)
+}
+
+// What every sorted form shares: the item and bin counts, the scan blocks, the 256-B aligned
+// scratch sizes (slot / seed: the family's bytes per item / per path) and KGrp's common fields.
+// Returns as grouped_plan does.
+static int grouped_sizes(uam_ctx* ctx, GPlan* pl, const double* pairs, int64_t n_pairs,
+                         const double* utab, int32_t D, int32_t nx, int32_t ny, int32_t nbands,
+                         GTilesFn tiles_of, size_t slot, size_t seed) {
+    const int G = ctx->k2g_group;
+    const int64_t W = ctx->kp.N + 2, P = n_pairs * D;
+    const int nseg = (int)((W + G - 1) / G);
+    const int64_t n_items = P * nseg;
+    if (n_items >= INT32_MAX) return grouped_no(*pl, "more than 2^31 (path, group) items");
+    int tbits = 0;
+    const int tiles = tiles_of(ctx, nx, ny, nbands, n_items, &tbits);
+    if (!tiles) return grouped_no(*pl, "more (tile, band) bins than the sort holds");
     const int last_bin = (W % G) ? tiles : 0;  // a ragged last group gets its own bins
     const int bins = tiles + last_bin + 1;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     pl->ncnt = (int64_t)bins * G_NBK;
     pl->nsb = (pl->ncnt + 256 * SCAN_ITEMS - 1) / (256 * SCAN_ITEMS);
-    if (pl->nsb > 4096) return no("the sort's counts exceed 4096 scan blocks");
-    // K2h (the similarity form) unless disabled or maxratio_smooth (its turn rows are not
-    // scale-free): 24-B slots, the geometry in the output launch
-    // and its 32-bit offsets reach the whole packed copy; N <= 4096 (Phi / N by the reciprocal)
-    const bool sim = ctx->k2g_sim && !ctx->kp.maxratio_smooth && kr.pk && ctx->kp.N <= 4096;
-    pl->sim = sim;
-    pl->exact = exact;  // (sim holds: checked above)
-    pl->hevx = nullptr;
-    pl->finx = nullptr;
-    pl->ubytes = ubytes;
+    if (pl->nsb > 4096) return grouped_no(*pl, "the sort's counts exceed 4096 scan blocks");
     pl->b_key = al((size_t)n_items * 2), pl->b_cnt = al((size_t)pl->ncnt * 4);
     pl->b_tot = al(4096 * 4), pl->b_ord = al((size_t)n_items * 4);
-    pl->b_slot = al((size_t)n_items *
-                    (exact ? sizeof(HSlotX) : sim ? sizeof(HSlot) : sizeof(GSlot)));
+    pl->b_slot = al((size_t)n_items * slot);
     pl->b_ug = al((size_t)D * sizeof(UGeo)), pl->b_err = 256;
-    pl->b_lbp = sim ? al((size_t)P * 4) : 0;
+    pl->b_seed = al((size_t)P * seed);
     pl->bytes = pl->b_key + pl->b_cnt + pl->b_tot + pl->b_ord + pl->b_slot + pl->b_ug +
-                pl->b_err + pl->b_lbp;
+                pl->b_err + pl->b_seed;
     KGrp& kg = pl->kg;
     kg = KGrp{};
     kg.pairs = pairs;
@@ -8497,7 +8468,7 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
     kg.G = G;
     kg.nseg = nseg;
     int tshift = 0;
-    while (((std::max(kr.nx, kr.ny) - 1) >> tshift) >= (1 << tbits)) ++tshift;
+    while (((std::max(nx, ny) - 1) >> tshift) >= (1 << tbits)) ++tshift;
     kg.tshift = tshift;
     kg.tbits = tbits;
     kg.bins = bins;
@@ -8509,6 +8480,44 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
     kg.lb_stride = ctx->k2h_lbs;
     kg.nsb_raw = pl->nsb <= 1024 ? (int32_t)pl->nsb : 0;  // up to 1024 totals: scanned by the
                                                           // scatter
+    return 1;
+}
+
+// the sequence a raster batch takes: 1 (pl filled, scratch not yet carved), 0 when the batch is
+// not one K2g / K2h takes, < 0 on error
+static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, int64_t n_pairs,
+                        const double* utab, int32_t D, const KOut& ko, GPlan* pl) {
+    const int G = ctx->k2g_group;
+    const bool exact = ctx->exact_sum != 0;
+    *pl = GPlan{};
+    pl->exact = exact;
+    pl->needs = "UAM_OPT_EXACT_SUM needs K2h";
+    pl->scale = exact ? ctx->sum_scale : nullptr;
+    auto no = [&](const char* why) { return grouped_no(*pl, why); };
+    if (G < 1 || G > G_MAXLEN) return no("UAM_OPT_GROUP is 0");
+    if (!kr.pmap) return no("no packed_dev");
+    if (ko.g_rows) return no("g_rows requested");
+    if (D > 16) return no("D > 16");
+    if (!exact && n_pairs * D < ctx->k2s_min) return 0;
+    if (n_pairs > INT32_MAX / D) return no("more than 2^31 paths");
+    if (exact) {
+        if (!ctx->k2g_sim) return no("UAM_OPT_K2G_SIM is 0");
+        if (ctx->kp.maxratio_smooth) return no("maxratio_smooth is set");
+        if (!kr.pk) return no("the packed copy is 4 GiB or larger");
+        if (ctx->kp.N > 4096) return no("N > 4096");
+    }
+    const size_t ubytes = (size_t)D * ctx->kp.N * 16;  // the unit-arc rows, staged in LDS
+    if (ubytes > (size_t)G_UTAB_LDS) return no("the unit-arc table exceeds its LDS share");
+    // K2h (the similarity form) unless disabled or maxratio_smooth (its turn rows are not
+    // scale-free): 24-B slots, the geometry in the output launch
+    // and its 32-bit offsets reach the whole packed copy; N <= 4096 (Phi / N by the reciprocal)
+    const bool sim = ctx->k2g_sim && !ctx->kp.maxratio_smooth && kr.pk && ctx->kp.N <= 4096;
+    pl->sim = sim;  // (holds in the exact form: checked above)
+    int st = grouped_sizes(ctx, pl, pairs, n_pairs, utab, D, kr.nx, kr.ny, 1, raster_tiles,
+                           exact ? sizeof(HSlotX) : sim ? sizeof(HSlot) : sizeof(GSlot),
+                           sim ? 4 : 0);
+    if (st <= 0) return st;
+    const int nseg = pl->kg.nseg;
     // gathers in flight per lane (K2g, profiles/r03/k2g9, cfg3: 8 at G = 21 0.337 ms, 11 0.350,
     // 10 0.369, 6 0.351; K2h: 7, groups of 21 = three full chunks).  A raster far beyond the
     // L2s (over 2^25 cells: cfg4's 8192^2) misses more: fewer items resident per XCD (3
@@ -8516,11 +8525,9 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
     // 0.886 against 0.936 ms, profiles/r04/sweep7)
     const bool big = sim && (int64_t)kr.nx * kr.ny > ((int64_t)1 << 25);
     const int chl = ctx->k2g_chunk ? ctx->k2g_chunk : big ? 11 : sim ? 7 : 8;
-    pl->ev = nullptr;
-    pl->hev = nullptr;
-    const bool lbp = sim && !ctx->k2h_te && ctx->k2h_lbs > 0;
+    pl->seeds = sim && !ctx->k2h_te && ctx->k2h_lbs > 0;
     // the seeds' header and unit-arc reads from LDS when both fit beside the histogram's own
-    pl->hist_dyn = lbp ? (size_t)kr.hwords * 4 + ubytes : 0;
+    pl->hist_dyn = pl->seeds ? (size_t)kr.hwords * 4 + ubytes : 0;
     if (sim) {  // K2h: H_BS-item workgroups, the packed header in LDS
         static const HEvalFn hevals[8] = {k_h_eval<6, false>, k_h_eval<7, false>,
                                           k_h_eval<8, false>, k_h_eval<11, false>,
@@ -8539,17 +8546,10 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
         const int floor_lds = ctx->k2g_lds ? ctx->k2g_lds : big ? 54000 : 0;
         pl->lds = std::max(need, (size_t)std::min(floor_lds, 160 * 1024));
         if (pl->lds > 160 * 1024) return no("the packed header and arc rows exceed the LDS");
-        if (!ctx->k2h_attrs) {  // per context = per device (DeviceGuard active)
-            for (HEvalFn f : hevals)
-                HIP_TRY(hipFuncSetAttribute((const void*)f,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            for (HEvalXFn f : hevalsx)
-                HIP_TRY(hipFuncSetAttribute((const void*)f,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIP_TRY(hipFuncSetAttribute((const void*)k_g_hist,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, G_HIST_DYN_MAX));
-            ctx->k2h_attrs = true;
-        }
+        static const HEvalFn hist[1] = {k_g_hist};
+        st = raise_lds(&ctx->k2h_attrs, 160 * 1024, hevals, hevalsx);
+        if (!st) st = raise_lds(&ctx->k2h_hist_attr, G_HIST_DYN_MAX, hist);
+        if (st) return st;
     } else {  // K2g: 256-item workgroups, the code map in LDS
 #define UAM_G_EVALS(CH) k_g_eval<CH, false, false>, k_g_eval<CH, false, true>, \
                         k_g_eval<CH, true, false>, k_g_eval<CH, true, true>
@@ -8562,11 +8562,9 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
         pl->bs = 256;
         const size_t need = (size_t)((kr.pwords + 3) & ~3) * 4 + ubytes + 16;
         pl->lds = std::max(need, (size_t)std::min(ctx->k2g_lds, 160 * 1024));
-        if (pl->lds > 64 * 1024 && !ctx->k2g_attrs) {
-            for (GEvalFn f : evals)
-                HIP_TRY(hipFuncSetAttribute((const void*)f,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            ctx->k2g_attrs = true;
+        if (pl->lds > 64 * 1024) {
+            st = raise_lds(&ctx->k2g_attrs, 160 * 1024, evals);
+            if (st) return st;
         }
     }
     // the output launch holds a path's slots in registers up to 8 groups
@@ -8574,30 +8572,47 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
                   : nseg <= 4 ? k_g_final<4> : nseg <= 8 ? k_g_final<8> : k_g_final<0>;
     if (exact)
         pl->finx = nseg <= 4 ? k_h_final_x<4> : nseg <= 8 ? k_h_final_x<8> : k_h_final_x<0>;
-    const int st = err_word(ctx, &kg);  // (kg.tkey: the launchers, after tile_keys)
+    st = err_word(ctx, &pl->kg);  // (kg.tkey: the launchers, after tile_keys)
     return st ? st : 1;
 }
 
 // the plan's scratch at w (pl->bytes, 256-B aligned)
-static void grouped_carve(uam_ctx* ctx, GPlan* pl, char* w) {
+static void grouped_carve(GPlan* pl, char* w) {
     KGrp& kg = pl->kg;
     size_t o = 0;
-    kg.slot = (GSlot*)(w + o), o += pl->b_slot;  // 256-B aligned slots first (HSlot for K2h)
+    kg.slot = (GSlot*)(w + o), o += pl->b_slot;  // 256-B aligned slots first (HSlot for K2h,
+                                                 // VSlot / VSlotX for K4h)
     kg.ugeo = pl->sim ? (UGeo*)(w + o) : nullptr, o += pl->b_ug;
     kg.order = (int32_t*)(w + o), o += pl->b_ord;
     kg.cnt = (int32_t*)(w + o), o += pl->b_cnt;
     kg.tot = (int32_t*)(w + o), o += pl->b_tot;
     kg.err = (int32_t*)(w + o), o += pl->b_err;
-    kg.lbp = pl->sim && !ctx->k2h_te && ctx->k2h_lbs > 0 ? (float*)(w + o) : nullptr;
-    o += pl->b_lbp;
-    kg.seed_lds = kg.lbp && pl->hist_dyn <= (size_t)G_HIST_DYN_MAX;
+    char* seed = pl->seeds ? w + o : nullptr;
+    if (pl->vol) kg.ubp = (double*)seed;
+    else kg.lbp = (float*)seed;
+    o += pl->b_seed;
+    kg.seed_lds = seed && pl->hist_dyn <= (size_t)G_HIST_DYN_MAX;
     kg.key = (uint16_t*)(w + o);
 }
 
-static void grouped_sort(uam_ctx* ctx, const GPlan& pl, const KRaster& kr, hipStream_t s) {
+// A family's histogram launch (G_NBK workgroups of 1024, lds bytes of dynamic LDS) over its
+// grid: the raster's KRaster (k_g_hist) or the volume's KVol4 (k_v_hist)
+using GHistFn = void (*)(uam_ctx*, const KGrp&, const void* grid, size_t lds, hipStream_t);
+
+static void raster_hist(uam_ctx* ctx, const KGrp& kg, const void* kr, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(k_g_hist, dim3(G_NBK), dim3(1024), lds, s, ctx->kp, *(const KRaster*)kr,
+                       kg);
+}
+
+static void volume_hist(uam_ctx* ctx, const KGrp& kg, const void* kv, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(k_v_hist, dim3(G_NBK), dim3(1024), lds, s, ctx->kp, *(const KVol4*)kv, kg);
+}
+
+// the counting sort; the histogram launch is the only part that differs
+static void grouped_sort(uam_ctx* ctx, const GPlan& pl, GHistFn hist, const void* grid,
+                         hipStream_t s) {
     const KGrp& kg = pl.kg;
-    hipLaunchKernelGGL(k_g_hist, dim3(G_NBK), dim3(1024), kg.seed_lds ? pl.hist_dyn : 0, s,
-                       ctx->kp, kr, kg);
+    hist(ctx, kg, grid, kg.seed_lds ? pl.hist_dyn : 0, s);
     hipLaunchKernelGGL(k_scan_local, dim3((unsigned)pl.nsb), dim3(256), 0, s, kg.cnt, pl.ncnt,
                        kg.cnt, kg.tot);
     if (!kg.nsb_raw)
@@ -8610,13 +8625,19 @@ static void grouped_eval(uam_ctx* ctx, const GPlan& pl, const KRaster& kr, const
                          hipStream_t s) {
     const dim3 grid((unsigned)((pl.kg.n_items + pl.bs - 1) / pl.bs));
     if (pl.hevx)
-        hipLaunchKernelGGL(pl.hevx, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kr, pl.kg,
-                           ctx->sum_scale);
+        hipLaunchKernelGGL(pl.hevx, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kr, pl.kg, pl.scale);
     else if (pl.hev)
         hipLaunchKernelGGL(pl.hev, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kr, pl.kg);
     else
         hipLaunchKernelGGL(pl.ev, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kr, pl.kg,
                            (const uint4*)rec);
+}
+
+// K4h's: the exact form reads its scale through the volume's view
+static void grouped_eval(uam_ctx* ctx, const GPlan& pl, KVol4 kv, hipStream_t s) {
+    const dim3 grid((unsigned)((pl.kg.n_items + pl.bs - 1) / pl.bs));
+    if (pl.exact) kv.xscale = pl.scale;
+    hipLaunchKernelGGL(pl.vev, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kv, pl.kg);
 }
 
 static void grouped_final(uam_ctx* ctx, const GPlan& pl, const KOut& ko, int32_t* best_f,
@@ -8626,7 +8647,7 @@ static void grouped_final(uam_ctx* ctx, const GPlan& pl, const KOut& ko, int32_t
     const size_t lds = (size_t)2 * 64 * D * sizeof(double);
     if (pl.finx)
         hipLaunchKernelGGL(pl.finx, grid, dim3(64 * D), lds, s, ctx->kp, pl.kg, ko, best_f, best_l,
-                           ctx->sum_scale);
+                           pl.scale);
     else
         hipLaunchKernelGGL(pl.fin, grid, dim3(64 * D), lds, s, ctx->kp, pl.kg, ko, best_f, best_l);
 }
@@ -8640,7 +8661,7 @@ static int launch_grouped(uam_ctx* ctx, const KRaster& kr, const void* rec, cons
     GPlan pl;
     int st = grouped_plan(ctx, kr, pairs, n_pairs, utab, D, ko, &pl);
     if (st <= 0) return st;
-    if (pl.exact && !ctx->sum_scale)
+    if (pl.exact && !pl.scale)
         return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM is on and no sum scale is set "
                                  "(uam_raster_sum_scale, uam_set_sum_scale)");
     char* w = nullptr;
@@ -8649,7 +8670,7 @@ static int launch_grouped(uam_ctx* ctx, const KRaster& kr, const void* rec, cons
     st = tile_keys(ctx, pl.kg.tbits, ctx->k2g_curve, s);  // (enqueued only when they change)
     if (st) return st;
     pl.kg.tkey = ctx->d_tkey;
-    grouped_carve(ctx, &pl, w);
+    grouped_carve(&pl, w);
     KGrp& kg = pl.kg;
     kg.cells = ko.cells;
     // the waypoint cells depend on the pairs and arc rows only: k_cells (VALU and store bound)
@@ -8693,7 +8714,7 @@ static int launch_grouped(uam_ctx* ctx, const KRaster& kr, const void* rec, cons
         HIP_TRY(hipEventRecord(ctx->ev_join, ctx->s_lo));
         forked = true;
     }
-    grouped_sort(ctx, pl, kr, s);
+    grouped_sort(ctx, pl, raster_hist, &kr, s);
     grouped_eval(ctx, pl, kr, rec, s);
     grouped_final(ctx, pl, ko, best_f, best_l, s);
     if (hipGetLastError() != hipSuccess) return join(fail(UAM_E_HIP, "grouped evaluation launch"));
@@ -8707,19 +8728,17 @@ static int launch_grouped(uam_ctx* ctx, const KRaster& kr, const void* rec, cons
     return st ? st : 1;
 }
 
-// K4h launch (the packed volume in K2h's form); returns 1 if launched, 0 if the batch is not
-// one it takes (the caller runs K4).  Scratch: the pair-order scratch (order_scratch).
-// UAM_OPT_EXACT_SUM_VOLUME: the exact form (k_v_eval_x / k_v_final_x, 48-B slots) at every batch
-// size; it never stands aside for another sum order, so a batch K4h does not take is an error
-// with its reason, raised before any launch.
-static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
-                            const double* utab, int32_t D, const KOut& ko, int32_t* best_f,
-                            int32_t* best_l, hipStream_t s) {
+// the sequence a volume batch takes (K4h): as grouped_plan
+static int grouped_plan3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
+                          const double* utab, int32_t D, const KOut& ko, GPlan* pl) {
     const int G = ctx->k2g_group;
     const bool exact = ctx->exact_sum_vol != 0;
-    auto no = [&](const char* why) {
-        return exact ? fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME needs K4h: %s", why) : 0;
-    };
+    *pl = GPlan{};
+    pl->vol = pl->sim = true;
+    pl->exact = exact;
+    pl->needs = "UAM_OPT_EXACT_SUM_VOLUME needs K4h";
+    pl->scale = exact ? ctx->vol_sum_scale : nullptr;
+    auto no = [&](const char* why) { return grouped_no(*pl, why); };
     if (G < 1 || G > G_MAXLEN) return no("UAM_OPT_GROUP is 0");
     if (ko.cells || ko.g_rows) return no("cells or g_rows requested");
     if (D > 16) return no("D > 16");
@@ -8728,105 +8747,26 @@ static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6,
     if (!kv.pk)
         return no("the packed copy is 4 GiB or larger, or a layer or side holds 2^24 entries");
     if (ctx->kp.N > 4096) return no("N > 4096");
-    const int64_t W = ctx->kp.N + 2, P = n_pairs * D;
-    if (!exact && P < ctx->k2s_min) return 0;
+    if (!exact && n_pairs * D < ctx->k2s_min) return 0;
     if (n_pairs > INT32_MAX / D) return no("more than 2^31 paths");
-    if ((size_t)D * ctx->kp.N * 16 > (size_t)G_UTAB_LDS)
-        return no("the unit-arc table exceeds its LDS share");
+    const size_t ubytes = (size_t)D * ctx->kp.N * 16;
+    if (ubytes > (size_t)G_UTAB_LDS) return no("the unit-arc table exceeds its LDS share");
     if ((size_t)kv.hwords * 4 > (size_t)VPK_HDR_LDS)
         return no("the packed header exceeds its LDS share");
+    int st = grouped_sizes(ctx, pl, pairs6, n_pairs, utab, D, kv.nx, kv.ny, kv.nbands,
+                           volume_tiles, exact ? sizeof(VSlotX) : sizeof(VSlot), 8);
+    if (st <= 0) return st;
     // workgroups per CU: 3 by default through an LDS floor of 40 000 B (UAM_OPT_K2G_LDS_FLOOR
     // sets another): fewer items resident per XCD, so fewer of their lines miss L2 -- round 5's
     // bound form, cfg5: 0.394 ms at 3 with 7 in flight, 0.397 at 5 (28 000 B), 0.428 at 2
     // (60 000 B), 0.448 at 2 with 11 (profiles/r05/k4h2, cc)
-    const int64_t npad = G + 16;  // k_v_eval's padding slots
-    const size_t lds = std::max((size_t)(D * ctx->kp.N + npad) * 16 +
-                                    (size_t)((W + npad + 1) & ~1) * 8 +
-                                    (size_t)(ctx->k4h_te ? kv.bnd_off : kv.hwords) * 4,
-                                (size_t)std::min(ctx->k2g_lds ? ctx->k2g_lds : 40000, 160 * 1024));
-    const int nseg = (int)((W + G - 1) / G);
-    const int64_t n_items = P * nseg;
-    if (n_items >= INT32_MAX) return no("more than 2^31 (path, group) items");
-    // tiles: 8 x 8 by default (128^2 columns at 1024^2: cfg5 0.461 vs 0.491 ms at 16 x 16,
-    // profiles/r04/vol2), UAM_OPT_K2G_TILE_BITS otherwise
-    // (a tile-bits setting made for 2-D rasters may give more (tile, band) bins than the sort
-    // holds: the key then takes the finest tiles that fit, which moves no bit of the outputs)
-    int tbits = ctx->k2g_tbits ? ctx->k2g_tbits : 3;
-    while (tbits > 1 && (2 << (2 * tbits)) * kv.nbands + 1 > G_BINS_MAX) --tbits;
-    const int tiles = 1 << (2 * tbits);
-    if (tiles * kv.nbands * 2 + 1 > G_BINS_MAX)  // (more bands than bins: K4)
-        return no("more (tile, band) bins than the sort holds");
-    const int last_bin = (W % G) ? tiles * kv.nbands : 0;
-    const int bins = tiles * kv.nbands + last_bin + 1;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const int64_t ncnt = (int64_t)bins * G_NBK;
-    const int64_t nsb = (ncnt + 256 * SCAN_ITEMS - 1) / (256 * SCAN_ITEMS);
-    if (nsb > 4096) return no("the sort's counts exceed 4096 scan blocks");
-    if (exact && !ctx->vol_sum_scale)
-        return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM_VOLUME is on and no volume sum scale is set "
-                                 "(uam_volume_sum_scale, uam_set_volume_sum_scale)");
-    const size_t b_key = al((size_t)n_items * 2), b_cnt = al((size_t)ncnt * 4),
-                 b_ord = al((size_t)n_items * 4),
-                 b_slot = al((size_t)n_items * (exact ? sizeof(VSlotX) : sizeof(VSlot))),
-                 b_ug = al((size_t)D * sizeof(UGeo)), b_tot = al(4096 * 4), b_err = 256,
-                 b_ubp = al((size_t)P * 8);
-    char* w = nullptr;
-    int st = order_scratch(ctx, b_key + b_cnt + b_ord + b_slot + b_ug + b_tot + b_err + b_ubp, s,
-                           &w);
-    if (st) return st;
-    KGrp kg{};
-    kg.pairs = pairs6;
-    kg.utab = utab;
-    kg.n_pairs = n_pairs;
-    kg.P = (int32_t)P;
-    kg.D = D;
-    kg.W = (int32_t)W;
-    kg.G = G;
-    kg.nseg = nseg;
-    int tshift = 0;
-    while (((std::max(kv.nx, kv.ny) - 1) >> tshift) >= (1 << tbits)) ++tshift;
-    kg.tshift = tshift;
-    kg.tbits = tbits;
-    kg.bins = bins;
-    kg.last_bin = last_bin;
-    st = tile_keys(ctx, tbits, ctx->k2g_curve, s);
-    if (st) return st;
-    kg.tkey = ctx->d_tkey;
-    magic_div((uint32_t)nseg, &kg.m_nseg, &kg.sh_nseg);
-    magic_div((uint32_t)D, &kg.m_d, &kg.sh_d);
-    kg.inv_n = ctx->kp.N <= 4096 ? 1.0 / (double)ctx->kp.N : 0.0;
-    kg.lb_stride = ctx->k2h_lbs;
-    kg.n_items = n_items;
-    size_t o = 0;
-    kg.slot = (GSlot*)(w + o), o += b_slot;  // VSlot / VSlotX
-    kg.ugeo = (UGeo*)(w + o), o += b_ug;
-    kg.order = (int32_t*)(w + o), o += b_ord;
-    kg.cnt = (int32_t*)(w + o), o += b_cnt;
-    kg.tot = (int32_t*)(w + o), o += b_tot;
-    kg.err = (int32_t*)(w + o), o += b_err;
-    st = err_word(ctx, &kg);
-    if (st) return st;
-    kg.ubp = ctx->k2h_lbs > 0 && !ctx->k4h_te ? (double*)(w + o) : nullptr, o += b_ubp;
-    const size_t hist_dyn = (size_t)kv.hwords * 4 + (size_t)D * ctx->kp.N * 16;
-    kg.seed_lds = kg.ubp && hist_dyn <= (size_t)G_HIST_DYN_MAX;
-    kg.key = (uint16_t*)(w + o);
-    st = ktime_begin(ctx, s);
-    if (st) return st;
-    if (kg.seed_lds && !ctx->k4h_hist_attr) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_v_hist,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, G_HIST_DYN_MAX));
-        ctx->k4h_hist_attr = true;
-    }
-    hipLaunchKernelGGL(k_v_hist, dim3(G_NBK), dim3(1024), kg.seed_lds ? hist_dyn : 0, s,
-                       ctx->kp, kv, kg);
-    hipLaunchKernelGGL(k_scan_local, dim3((unsigned)nsb), dim3(256), 0, s, kg.cnt, ncnt, kg.cnt,
-                       kg.tot);
-    kg.nsb_raw = nsb <= 1024 ? (int32_t)nsb : 0;  // up to 1024 totals: scanned by the scatter
-    if (!kg.nsb_raw)
-        hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, s, kg.tot, (int)nsb);
-    hipLaunchKernelGGL(k_g_scatter, dim3(G_NBK + (kg.ugeo ? 1 : 0)), dim3(1024), 0, s, ctx->kp, kg);
-    const dim3 ge((unsigned)((n_items + 255) / 256));
-    using VEvalFn = void (*)(KParams, KVol4, KGrp);
+    const int64_t W = pl->kg.W, npad = G + 16;  // k_v_eval's padding slots
+    pl->lds = std::max((size_t)(D * ctx->kp.N + npad) * 16 + (size_t)((W + npad + 1) & ~1) * 8 +
+                           (size_t)(ctx->k4h_te ? kv.bnd_off : kv.hwords) * 4,
+                       (size_t)std::min(ctx->k2g_lds ? ctx->k2g_lds : 40000, 160 * 1024));
+    pl->bs = 256;
+    pl->seeds = ctx->k2h_lbs > 0 && !ctx->k4h_te;
+    pl->hist_dyn = (size_t)kv.hwords * 4 + ubytes;
     // gathers in flight per lane: 7 by default (the bound form at 3 workgroups per CU; 8 and 11
     // are built for 3 / 2 waves per SIMD)
     const int chl = ctx->k2g_chunk ? ctx->k2g_chunk : 7;
@@ -8843,33 +8783,54 @@ static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6,
                                          k_v_eval_x<11, true>,  k_v_eval_x<16, true>};
     const int vi = (chl <= 6 ? 0 : chl == 7 ? 1 : chl <= 8 ? 2 : chl == 11 ? 3 : 4) +
                    (ctx->k4h_te ? 5 : 0);
-    const VEvalFn ev = vevals[vi];
-    if (lds > 64 * 1024 && !ctx->k4h_attrs) {
-        for (VEvalFn f : vevals)
-            HIP_TRY(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-        for (VEvalFn f : vevalsx)
-            HIP_TRY(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-        ctx->k4h_attrs = true;
+    pl->vev = exact ? vevalsx[vi] : vevals[vi];
+    if (pl->lds > 64 * 1024) {
+        st = raise_lds(&ctx->k4h_attrs, 160 * 1024, vevals, vevalsx);
+        if (st) return st;
     }
-    const dim3 gf((unsigned)((n_pairs + 63) / 64));
-    const size_t lds_f = (size_t)2 * 64 * D * sizeof(double);
-    if (exact) {
-        KVol4 kvx = kv;
-        kvx.xscale = ctx->vol_sum_scale;
-        hipLaunchKernelGGL(vevalsx[vi], ge, dim3(256), lds, s, ctx->kp, kvx, kg);
-        hipLaunchKernelGGL(k_v_final_x, gf, dim3(64 * D), lds_f, s, ctx->kp, kg, ko, best_f,
-                           best_l, ctx->vol_sum_scale);
-    } else {
-        hipLaunchKernelGGL(ev, ge, dim3(256), lds, s, ctx->kp, kv, kg);
-        hipLaunchKernelGGL(k_v_final, gf, dim3(64 * D), lds_f, s, ctx->kp, kg, ko, best_f, best_l);
+    pl->fin = k_v_final;
+    if (exact) pl->finx = k_v_final_x;
+    return 1;  // (the error word: launch_grouped3d, after the carve as before)
+}
+
+// K4h launch (the packed volume in K2h's form); returns 1 if launched, 0 if the batch is not
+// one it takes (the caller runs K4).  Scratch: the pair-order scratch (order_scratch).
+// UAM_OPT_EXACT_SUM_VOLUME: the exact form (k_v_eval_x / k_v_final_x, 48-B slots) at every batch
+// size; it never stands aside for another sum order, so a batch K4h does not take is an error
+// with its reason, raised before any launch.
+static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
+                            const double* utab, int32_t D, const KOut& ko, int32_t* best_f,
+                            int32_t* best_l, hipStream_t s) {
+    GPlan pl;
+    int st = grouped_plan3d(ctx, kv, pairs6, n_pairs, utab, D, ko, &pl);
+    if (st <= 0) return st;
+    if (pl.exact && !pl.scale)
+        return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM_VOLUME is on and no volume sum scale is set "
+                                 "(uam_volume_sum_scale, uam_set_volume_sum_scale)");
+    char* w = nullptr;
+    st = order_scratch(ctx, pl.bytes, s, &w);
+    if (st) return st;
+    st = tile_keys(ctx, pl.kg.tbits, ctx->k2g_curve, s);
+    if (st) return st;
+    pl.kg.tkey = ctx->d_tkey;
+    grouped_carve(&pl, w);
+    st = err_word(ctx, &pl.kg);
+    if (st) return st;
+    st = ktime_begin(ctx, s);
+    if (st) return st;
+    if (pl.kg.seed_lds) {
+        static const VEvalFn hist[1] = {k_v_hist};
+        st = raise_lds(&ctx->k4h_hist_attr, G_HIST_DYN_MAX, hist);
+        if (st) return st;
     }
+    grouped_sort(ctx, pl, volume_hist, &kv, s);
+    grouped_eval(ctx, pl, kv, s);
+    grouped_final(ctx, pl, ko, best_f, best_l, s);
     if (hipGetLastError() != hipSuccess) return fail(UAM_E_HIP, "grouped volume evaluation launch");
     st = ktime_end(ctx, s);
     if (st) return st;
-    ctx->last_group = G;
-    ctx->last_kernel = exact ? "K4hx+pack" : "K4h+pack";
+    ctx->last_group = pl.kg.G;
+    ctx->last_kernel = pl.exact ? "K4hx+pack" : "K4h+pack";
     st = order_done(ctx, s);
     return st ? st : 1;
 }
@@ -9105,7 +9066,7 @@ static int eval_generated(uam_ctx* ctx, int32_t mode, const uam_raster_desc* des
         while (S > 2 && k3b_lds_bytes(D, S) > 160 * 1024) S = S == 6 ? 4 : S / 2;
         const int CPL = ctx->k3b_cpl >= 2 ? 2 : 1;
         const size_t l3 = k3b_lds_bytes(D, S);
-        if (!ctx->k3b_attrs) {  // per context = per device (DeviceGuard active)
+        {
             const void* fns[] = {(const void*)k_eval_pairs_k3b<2, 1>,
                                  (const void*)k_eval_pairs_k3b<4, 1>,
                                  (const void*)k_eval_pairs_k3b<8, 1>,
@@ -9116,10 +9077,8 @@ static int eval_generated(uam_ctx* ctx, int32_t mode, const uam_raster_desc* des
                                  (const void*)k_eval_pairs_k3b<4, 2>,
                                  (const void*)k_eval_pairs_k3b<8, 2>,
                                  (const void*)k_eval_pairs_k3b<16, 2>};
-            for (const void* f : fns)
-                HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            160 * 1024));
-            ctx->k3b_attrs = true;
+            st = raise_lds(&ctx->k3b_attrs, 160 * 1024, fns);
+            if (st) return st;
         }
 #define UAM_LAUNCH_K3B(S_, C_)                                                                 \
     hipLaunchKernelGGL((k_eval_pairs_k3b<S_, C_>), grid, block, l3, s, ctx->kg, ctx->kp, pairs,   \
@@ -9259,6 +9218,26 @@ int uam_raster_summary(uam_ctx* ctx, const uam_raster_desc* desc, const void* re
     return UAM_OK;
 }
 
+// The exact sums' scale of n cells: a raster's 16-B records (8 a lane at least) or, vox, a
+// volume's 8-B voxels (16 a lane at least); 2048 workgroups at most (the atomics: one per wave
+// and word)
+static int sum_scale(uam_ctx* ctx, const void* cells, int64_t n, bool vox, int32_t* scale,
+                     uam_stream stream) {
+    DeviceGuard dg(ctx->device);
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_sum_scale_init, dim3(1), dim3(64), 0, s, scale);
+    const int64_t per_wg = vox ? 4096 : 2048;
+    const dim3 grid((unsigned)std::min<int64_t>((n + per_wg - 1) / per_wg, 2048));
+    if (!vox)
+        hipLaunchKernelGGL(k_sum_scale<uint4>, grid, dim3(256), 0, s, (const uint4*)cells, n,
+                           scale);
+    else
+        hipLaunchKernelGGL(k_sum_scale<uint2>, grid, dim3(256), 0, s, (const uint2*)cells, n,
+                           scale);
+    HIP_TRY(hipGetLastError());
+    return UAM_OK;
+}
+
 int uam_raster_sum_scale(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
                          int32_t* scale, uam_stream stream) {
     if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
@@ -9266,27 +9245,22 @@ int uam_raster_sum_scale(uam_ctx* ctx, const uam_raster_desc* desc, const void* 
     const int st = make_kraster(desc, &kr);
     if (st) return st;
     if (!rec || !scale) return fail(UAM_E_INVALID, "rec/scale is NULL");
-    DeviceGuard dg(ctx->device);
-    const int64_t cells = (int64_t)kr.nx * kr.ny;
-    hipLaunchKernelGGL(k_sum_scale_init, dim3(1), dim3(64), 0, (hipStream_t)stream, scale);
-    // 8 cells a lane at least, 2048 workgroups at most (the atomics: one per wave and word)
-    const unsigned grid = (unsigned)std::min<int64_t>((cells + 2047) / 2048, 2048);
-    hipLaunchKernelGGL(k_sum_scale<uint4>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4*)rec, cells, scale);
-    HIP_TRY(hipGetLastError());
+    return sum_scale(ctx, rec, (int64_t)kr.nx * kr.ny, false, scale, stream);
+}
+
+// the caller's device words of a scale (uam_set_sum_scale, uam_set_volume_sum_scale)
+static int set_scale(uam_ctx* ctx, const int32_t* uam_ctx::*words, const int32_t* scale) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    ctx->*words = scale;
     return UAM_OK;
 }
 
 int uam_set_sum_scale(uam_ctx* ctx, const int32_t* scale) {
-    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
-    ctx->sum_scale = scale;
-    return UAM_OK;
+    return set_scale(ctx, &uam_ctx::sum_scale, scale);
 }
 
 int uam_set_volume_sum_scale(uam_ctx* ctx, const int32_t* scale) {
-    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
-    ctx->vol_sum_scale = scale;
-    return UAM_OK;
+    return set_scale(ctx, &uam_ctx::vol_sum_scale, scale);
 }
 
 int uam_exact_sum_host(const float* values, int64_t n, int32_t e, double* sum_out,
@@ -9398,15 +9372,7 @@ int uam_volume_sum_scale(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
     const int st = make_kvolume(vd, &kv);
     if (st) return st;
     if (!vol || !scale) return fail(UAM_E_INVALID, "vol/scale is NULL");
-    DeviceGuard dg(ctx->device);
-    const int64_t voxels = (int64_t)vd->nx * vd->ny * vd->nz;
-    hipLaunchKernelGGL(k_sum_scale_init, dim3(1), dim3(64), 0, (hipStream_t)stream, scale);
-    // 16 voxels a lane at least, 2048 workgroups at most (the atomics: one per wave and word)
-    const unsigned grid = (unsigned)std::min<int64_t>((voxels + 4095) / 4096, 2048);
-    hipLaunchKernelGGL(k_sum_scale<uint2>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       (const uint2*)vol, voxels, scale);
-    HIP_TRY(hipGetLastError());
-    return UAM_OK;
+    return sum_scale(ctx, vol, (int64_t)vd->nx * vd->ny * vd->nz, true, scale, stream);
 }
 
 namespace {
@@ -9540,10 +9506,11 @@ int uam_volume_pack(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol, vo
     return UAM_OK;
 }
 
-static int eval_generated3d_vol(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
-                                const double* pairs6, int64_t n_pairs, const double* utab,
-                                int32_t D, const uam_path_outputs* out, uam_stream stream);
-
+// The failures, in the order a caller sees them: an earlier call's device check; the context
+// (NULL, no geometry, no params); the exact form without packed_dev; n_pairs / D (n_pairs == 0
+// then returns UAM_OK); the volume descriptor; pairs6 / utab NULL; with packed_dev its
+// alignment, then K4h's own refusals (launch_grouped3d: errors in the exact form, otherwise the
+// batch goes on to K4w / K4); vol NULL, then its alignment (a batch K4h took never reads vol).
 int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
                          const void* packed, const double* pairs6, int64_t n_pairs,
                          const double* utab, int32_t D, const uam_path_outputs* out,
@@ -9552,72 +9519,52 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
         const int st = device_status(ctx);
         if (st) return st;
     }
-    // UAM_OPT_EXACT_SUM_VOLUME: K4h's exact form at every batch size or an error (no K4 / K4w,
-    // whose ordered sums would make the bits depend on the batch size)
-    const bool exact = ctx && ctx->exact_sum_vol;
-    if (exact && !packed) {
-        const int st = check_ctx(ctx, true);
-        if (st) return st;
-        return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME needs K4h: no packed_dev");
-    }
-    if (packed) {
-        int st = check_ctx(ctx, true);
-        if (st) return st;
-        if (n_pairs < 0 || D < 1 || D > 16)
-            return fail(UAM_E_INVALID, "n_pairs < 0 or D outside [1, 16]");
-        if (n_pairs == 0) return UAM_OK;
-        KVolume kv0;
-        st = make_kvolume(vd, &kv0);
-        if (st) return st;
-        if (!pairs6 || !utab) return fail(UAM_E_INVALID, "pointer is NULL");
-        if ((uintptr_t)packed & 255) return fail(UAM_E_INVALID, "packed volume not 256-B aligned");
-        KVol4 kv{};
-        VpkDims v;
-        vpk_dims(vd, &v);
-        vpk_kvol(vd, v, packed, &kv);
-        int zs = 0;  // altitude bands: at most 16, or UAM_OPT_K4H_BAND layers each
-        if (ctx->k4h_band > 0) {
-            while ((1 << zs) < ctx->k4h_band) ++zs;
-        }
-        while ((vd->nz - 1) >> zs >= 16) ++zs;
-        kv.zshift = zs;
-        kv.nbands = ((vd->nz - 1) >> zs) + 1;
-        const KOut ko = make_kout(out);
-        DeviceGuard dg(ctx->device);
-        if (exact || !want_wave(ctx, n_pairs * D)) {
-            st = launch_grouped3d(ctx, kv, pairs6, n_pairs, utab, D, ko,
-                                  out ? out->best_fval_idx : nullptr,
-                                  out ? out->best_length_idx : nullptr, (hipStream_t)stream);
-            if (st < 0) return st;
-            if (st == 1) return UAM_OK;  // last_kernel: "K4h+pack" / "K4hx+pack"
-            if (exact)
-                return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME: the batch did not run K4h");
-        }
-    }
-    return eval_generated3d_vol(ctx, vd, vol, pairs6, n_pairs, utab, D, out, stream);
-}
-
-static int eval_generated3d_vol(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
-                                const double* pairs6, int64_t n_pairs, const double* utab,
-                                int32_t D, const uam_path_outputs* out, uam_stream stream) {
     int st = check_ctx(ctx, true);
     if (st) return st;
+    // UAM_OPT_EXACT_SUM_VOLUME: K4h's exact form at every batch size or an error (no K4 / K4w,
+    // whose ordered sums would make the bits depend on the batch size)
+    const bool exact = ctx->exact_sum_vol != 0;
+    if (exact && !packed)
+        return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME needs K4h: no packed_dev");
     if (n_pairs < 0 || D < 1 || D > 16)
         return fail(UAM_E_INVALID, "n_pairs < 0 or D outside [1, 16]");
     if (n_pairs == 0) return UAM_OK;
     KVolume kv;
     st = make_kvolume(vd, &kv);
     if (st) return st;
-    if (!vol || !pairs6 || !utab) return fail(UAM_E_INVALID, "pointer is NULL");
+    if (!pairs6 || !utab) return fail(UAM_E_INVALID, "pointer is NULL");
+    const KOut ko = make_kout(out);
+    int32_t* best_f = out ? out->best_fval_idx : nullptr;
+    int32_t* best_l = out ? out->best_length_idx : nullptr;
+    DeviceGuard dg(ctx->device);
+    if (packed) {
+        if ((uintptr_t)packed & 255) return fail(UAM_E_INVALID, "packed volume not 256-B aligned");
+        KVol4 k4{};
+        VpkDims v;
+        vpk_dims(vd, &v);
+        vpk_kvol(vd, v, packed, &k4);
+        int zs = 0;  // altitude bands: at most 16, or UAM_OPT_K4H_BAND layers each
+        if (ctx->k4h_band > 0) {
+            while ((1 << zs) < ctx->k4h_band) ++zs;
+        }
+        while ((vd->nz - 1) >> zs >= 16) ++zs;
+        k4.zshift = zs;
+        k4.nbands = ((vd->nz - 1) >> zs) + 1;
+        if (exact || !want_wave(ctx, n_pairs * D)) {
+            st = launch_grouped3d(ctx, k4, pairs6, n_pairs, utab, D, ko, best_f, best_l,
+                                  (hipStream_t)stream);
+            if (st < 0) return st;
+            if (st == 1) return UAM_OK;  // last_kernel: "K4h+pack" / "K4hx+pack"
+            if (exact)
+                return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME: the batch did not run K4h");
+        }
+    }
+    if (!vol) return fail(UAM_E_INVALID, "pointer is NULL");
     if ((uintptr_t)vol & 255) return fail(UAM_E_INVALID, "volume buffer not 256-B aligned");
     kv.vox = (const uint2*)vol;
     kv.col = (const uint2*)((const char*)vol + vol_col_offset(vd));
     kv.cbits = (const uint32_t*)((const char*)vol + vol_bits_offset(vd));
     vol_bits_dims(vd, &kv);
-    const KOut ko = make_kout(out);
-    int32_t* best_f = out ? out->best_fval_idx : nullptr;
-    int32_t* best_l = out ? out->best_length_idx : nullptr;
-    DeviceGuard dg(ctx->device);
     const KRaster kr{};
     ctx->last_kernel = "K4";
     ctx->last_group = 0;

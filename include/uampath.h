@@ -325,6 +325,59 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* desc, const void* 
                          const void* packed_dev, const double* pairs6_dev, int64_t n_pairs,
                          const double* utab_dev, int32_t D, const uam_path_outputs* out,
                          uam_stream stream);
+
+/* ---- The volume over explicit 3-D waypoints and altitude-profile candidates -----------------
+ * uam_eval_generated3d flies every candidate of a pair along the straight climb between the
+ * pair's end altitudes.  The three calls below let the caller choose the altitudes: any 3-D
+ * polyline (uam_eval_waypoints3d), or per lateral candidate a family of A altitude profiles
+ * (uam_gen_paths3d writes their waypoints, uam_eval_generated3d_profiles evaluates them fused,
+ * without the 24 W bytes per path the waypoints would take).  All three read vol_dev only (no
+ * packed copy, no sum scale).
+ *
+ * The altitude-profile table ztab_dev [A][W][3] float64, W = N + 2, is caller-built data like
+ * the unit-arc table.  Waypoint j of the pair (x0, y0, z0, xf, yf, zf) under profile a has
+ *   z_j = (z0 * ztab[a][j][0] + zf * ztab[a][j][1]) + ztab[a][j][2]
+ * -- two products, their sum, then the sum with the third coefficient, each rounded to float64
+ * (no fused multiply-add).  Affine in the end altitudes: (1 - t, t, 0) with t = j / (N+1) is the
+ * straight climb, (0, 0, h) an absolute altitude h, (1 - t, t, h) a lift of h above the chord.
+ * ztab_dev == NULL is allowed only with A = 1 and means uam_eval_generated3d's own expression
+ * z0 + (zf - z0) * ((double)j / (double)(N+1)), with its bits.  x/y are exactly uam_gen_paths'
+ * points (the pair's end points at j = 0 and j = N+1).  Path index p = (q*D + d)*A + a;
+ * candidate index within a pair c = d*A + a.  1 <= A <= 8, 1 <= D <= 16, fewer than 2^31 paths
+ * (UAM_E_INVALID otherwise, and for ztab_dev == NULL with A != 1). */
+int uam_gen_paths3d(uam_ctx* ctx, const double* pairs6_dev, int64_t n_pairs,
+                    const double* utab_dev, int32_t D, const double* ztab_dev, int32_t A,
+                    double* wp3_dev /* [Q*D*A][W][3] */, uam_stream stream);
+/* The volume evaluation of explicit waypoints wp3_dev [P][W][3] = (x km, y km, z m): the oracle's
+ * orc_eval_paths3d bit for bit.  cost = (N+1) L + sum_j risk(voxel_j) / N and nfz_sum, added
+ * sequentially in waypoint order over the waypoints inside the volume (x, y and z); nfz_hits;
+ * offmap counts the waypoints outside it; below_terrain as uam_eval_generated3d; min_clearance =
+ * min over the waypoints inside the volume of z_j - terrain of the column, +inf when there is
+ * none; cells [P][W] = the voxel index (iy nx + ix) nz + iz, -1 outside the volume (a volume of
+ * 2^31 voxels or more is refused by the descriptor check, so every index fits).  The length term
+ * L, length and the kinematic rows (length_q, length, kin_sum) are formed from x/y alone and
+ * ignore altitude, exactly as in uam_eval_generated3d.  g_rows, best_fval_idx and
+ * best_length_idx are not written.  Batches of up to UAM_OPT_WAVE_MAX_PATHS paths run wave per
+ * path (uam_last_kernel "K4ew"), larger ones lane per path ("K4e"); same bits.
+ * Failures, in order: an earlier call's device check; the context; UAM_OPT_EXACT_SUM_VOLUME on
+ * (below); n_paths < 0 (0 returns UAM_OK); the descriptor; wp3_dev / vol_dev NULL; vol_dev not
+ * 256-B aligned. */
+int uam_eval_waypoints3d(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol_dev,
+                         const double* wp3_dev /* [P][W][3] (x km, y km, z m) */,
+                         int64_t n_paths, const uam_path_outputs* out, uam_stream stream);
+/* uam_eval_waypoints3d applied to uam_gen_paths3d's waypoints, bit for bit, in one kernel
+ * (uam_last_kernel "K4p"): the A profiles of a lateral candidate share its x/y points, the
+ * geometry terms and each waypoint's column.  best_fval_idx [Q] and best_length_idx [Q] are
+ * uam_argmin's rule over the pair's D*A candidates in index order c (take_sqrt set for the cost,
+ * unset for the length); they need the cost / length output respectively (UAM_E_INVALID
+ * otherwise).  A length does not depend on the profile, so among the profiles of one
+ * displacement the rule's first index wins: best_length_idx is a multiple of A unless the rule's
+ * zero quirk applies (a length of exactly 0 is replaced by whatever follows it). */
+int uam_eval_generated3d_profiles(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol_dev,
+                                  const double* pairs6_dev, int64_t n_pairs,
+                                  const double* utab_dev, int32_t D, const double* ztab_dev,
+                                  int32_t A, const uam_path_outputs* out, uam_stream stream);
+
 /* The packed volume (K4h), 256-B aligned sections:
  *   header  a 2-bit code per 8 x 8 columns (0: risk, psi_nfz +-0 in every layer and no no-fly
  *           flag; 1: psi_nfz +-0 and no flag; 2: no psi_nfz below zero; 3: otherwise), then the
@@ -445,14 +498,15 @@ int uam_dem_polygons(uam_ctx* ctx, const float* dem_dev, const uam_raster_desc* 
  * of them once), so any number of calls may pass between queries. */
 int uam_kernel_timing(uam_ctx* ctx, int32_t enable);
 int uam_kernel_time(uam_ctx* ctx, double* ms_total, int64_t* launches);
-/* The path evaluation the last uam_eval_generated* call on ctx ran: "K2h+pack" (segment-grouped
+/* The path evaluation the last uam_eval_generated* / uam_eval_waypoints3d call on ctx ran: "K2h+pack" (segment-grouped
  * raster with the similarity-form geometry, the default for packed rasters and batches >=
  * UAM_OPT_SORTED_MIN_PATHS paths), "K2g+pack" (the same with per-segment geometry:
  * UAM_OPT_K2G_SIM = 0 or maxratio_smooth), "K4h+pack" (the packed volume, K2h's form),
  * "K2hx+pack" / "K4hx+pack" (their exact-sum forms, UAM_OPT_EXACT_SUM / _VOLUME),
  * "K2s+pack" / "K2s+skip" / "K2s" (segment-sorted raster, sequential sums), "K2+skip" / "K2"
  * (lane per path), "K2w" (wave per path), "K2d" (D > 16), "K3b", "K3", "K3d", "K4", "K4w";
- * "" before the first call.  The string is static (never freed).  For benchmarks and tests:
+ * "K4e" / "K4ew" (uam_eval_waypoints3d lane / wave per path), "K4p"
+ * (uam_eval_generated3d_profiles); "" before the first call.  The string is static (never freed).  For benchmarks and tests:
  * which kernel a number belongs to. */
 const char* uam_last_kernel(const uam_ctx* ctx);
 
@@ -468,7 +522,8 @@ const char* uam_last_kernel(const uam_ctx* ctx);
  * map, against the north_star's 1e-5; the selections (best_fval_idx, best_length_idx) agreed
  * on all 100k cfg3 pairs (bench.py parity.vs_sequential_order) -- they can differ only where
  * two candidates of a pair are within that rounding of each other.  A caller that needs the
- * sequential bits sets UAM_OPT_GROUP = 0 (K2s / K4). */
+ * sequential bits sets UAM_OPT_GROUP = 0 (K2s / K4).  uam_eval_waypoints3d and
+ * uam_eval_generated3d_profiles (K4e / K4ew / K4p) always add sequentially: they report 0. */
 int32_t uam_last_group(const uam_ctx* ctx);
 
 /* Context options: which kernel form runs (results never depend on them, except for the sum
@@ -645,6 +700,9 @@ int uam_exact_sum_host(const float* values, int64_t n, int32_t e, double* sum_ou
  * the sort holds, 2^31 or more paths or (path, group) items, a packed copy K4h stands aside for
  * (4 GiB or more, 2^24 entries a layer or columns a side).  The errors are raised on the host
  * before any launch; the context stays usable.
+ * uam_eval_waypoints3d and uam_eval_generated3d_profiles form ordered sums and have no exact
+ * form yet (a follow-up): with the option on both fail on the host with UAM_E_INVALID, naming the
+ * option -- exact or an error, never ordered.  uam_gen_paths3d sums nothing and ignores it.
  *
  * uam_volume_sum_scale writes the volume's 16-byte scale {e_risk, e_psi, flags, 0} to the
  * caller's device buffer scale_dev (flags: bits 0-2 = a risk word holds NaN / +inf / -inf, bits

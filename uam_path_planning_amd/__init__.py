@@ -10,6 +10,7 @@ Modules:
                displacements -> costs + selection, raster / analytic / volume), refine, ...
   _lib         ctypes binding of the C ABI (include/uampath.h)
   arcs         unit-arc table of the candidate generator (solver.py:103-136)
+  profiles     altitude-profile tables for the volume (eval_generated3d_profiles, gen_paths3d)
   geometry     shape compiler (polygon / ball / square -> device tables)
   distributed  pair sharding and the RCCL raster broadcast (one process per GPU)
   scenario     canonical Nagasaki scenario and BASELINE configs

@@ -155,6 +155,14 @@ SIGNATURES = {
     "uam_eval_generated3d": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp, _vp,
                                             ctypes.c_int64, _vp, ctypes.c_int32,
                                             ctypes.POINTER(PathOutputs), _vp]),
+    "uam_gen_paths3d": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int32, _vp,
+                                       ctypes.c_int32, _vp, _vp]),
+    "uam_eval_waypoints3d": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp,
+                                            ctypes.c_int64, ctypes.POINTER(PathOutputs), _vp]),
+    "uam_eval_generated3d_profiles": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp,
+                                                     ctypes.c_int64, _vp, ctypes.c_int32, _vp,
+                                                     ctypes.c_int32,
+                                                     ctypes.POINTER(PathOutputs), _vp]),
     "uam_volume_packed_bytes": (ctypes.c_int, [ctypes.POINTER(VolumeDesc),
                                                ctypes.POINTER(ctypes.c_int64)]),
     "uam_volume_pack": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp, _vp]),

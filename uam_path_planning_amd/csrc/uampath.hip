@@ -602,9 +602,9 @@ struct Chunk {
     bool in[C];
 };
 
-template <bool GEN, int C>
+template <bool GEN, int C, class Src = PathSrc<GEN>>
 __device__ __forceinline__ void issue_chunk(const KRaster& rs, const uint4* __restrict__ rec,
-                                            const PathSrc<GEN>& src, int j0, int W,
+                                            const Src& src, int j0, int W,
                                             int32_t* cells, Chunk<C>& ch) {
 #pragma unroll
     for (int t = 0; t < C; ++t) {
@@ -681,9 +681,9 @@ __device__ __forceinline__ int32_t raster_cell_skip(const KRaster& rs, const uin
 // (chunks of 4-16 at 4-8 waves per SIMD measured 4-36% slower on cfg3, r02)
 constexpr int SKIP_CHUNK = 8;  // gathers per chunk
 constexpr int SKIP_MINW = 5;   // waves per SIMD the skip kernel is compiled for (6 spills)
-template <bool GEN>
+template <bool GEN, class Src = PathSrc<GEN>>
 __device__ __forceinline__ void raster_pass2_skip(const KRaster& rs, const uint4* __restrict__ rec,
-                                                  const uint32_t* bits, const PathSrc<GEN>& src,
+                                                  const uint32_t* bits, const Src& src,
                                                   int W, int32_t* cells, double dN, PathAcc& a) {
     constexpr int CH = SKIP_CHUNK;
     for (int j0 = 0; j0 < W; j0 += CH) {
@@ -1115,9 +1115,9 @@ constexpr int MODE_RASTER_SKIP = 4;
 // Volume mode (BASELINE config 5, no reference counterpart): the waypoint's voxel
 // (ix, iy as in raster mode, iz = floor((z - z0) / dz)) holds {risk f32, psi_nfz f32} (risk
 // already carries the altitude-layer weight) and its column {terrain f32, flags}.
-template <bool GEN, int C>
+template <bool GEN, int C, class Src = PathSrc<GEN>>
 __device__ __forceinline__ void issue_chunk_vol(const KVolume& vs, const uint32_t* sbits,
-                                                const PathSrc<GEN>& src, int j0, int W,
+                                                const Src& src, int j0, int W,
                                                 int32_t* cells, Chunk<C>& ch) {
 #pragma unroll
     for (int t = 0; t < C; ++t) {
@@ -1136,9 +1136,9 @@ __device__ __forceinline__ void issue_chunk_vol(const KVolume& vs, const uint32_
     }
 }
 
-template <bool GEN, int C>
+template <bool GEN, int C, class Src = PathSrc<GEN>>
 __device__ __forceinline__ void consume_chunk_vol(const KVolume& vs, const Chunk<C>& ch,
-                                                  const PathSrc<GEN>& src, int j0, int W,
+                                                  const Src& src, int j0, int W,
                                                   double dN, PathAcc& a) {
 #pragma unroll
     for (int t = 0; t < C; ++t) {
@@ -1186,8 +1186,8 @@ __device__ __forceinline__ void kin_row(const KParams& p, double pn, double nk, 
 // Pass 1 of a path: get_cost's length term L (problem.py:130-146 with the quirk), the true
 // length (length_of, solver.py:49) and the sum of the 3N kinematic rows (problem.py:100-107),
 // optionally storing the rows.  Shared by every path kernel, so their bits agree.
-template <bool GEN>
-__device__ __forceinline__ void path_pass1(const KParams& p, const PathSrc<GEN>& src,
+template <bool GEN, class Src = PathSrc<GEN>>
+__device__ __forceinline__ void path_pass1(const KParams& p, const Src& src,
                                            double* grow, PathAcc& a) {
     const int N = p.N, W = N + 2;
     const bool ls = p.length_smooth != 0, ms = p.maxratio_smooth != 0;
@@ -1245,10 +1245,10 @@ __device__ __forceinline__ void path_pass1(const KParams& p, const PathSrc<GEN>&
 
 // One path: pass 1 = geometry-only terms (length_of, true length, kinematic rows), pass 2 =
 // per-waypoint penalty (analytic formulas or the record gather).  C = gathers per chunk.
-template <int MODE, bool GEN, int C>
+template <int MODE, bool GEN, int C, class Src = PathSrc<GEN>>
 __device__ __forceinline__ PathAcc eval_path(const KGeom& g, const KParams& p, const KRaster& rs,
                                              const KVolume& vs, const uint4* __restrict__ rec,
-                                             const PathSrc<GEN>& src, int64_t path,
+                                             const Src& src, int64_t path,
                                              const KOut& out, const uint32_t* sbits = nullptr) {
     const int N = p.N, W = N + 2;
     const int n_rows = 3 * N + g.n_obstacles * W;
@@ -3532,7 +3532,20 @@ __device__ __forceinline__ int wave_compact_nonzero(double* a, int n, int lane) 
 }
 
 
-template <int MODE, bool GEN>
+// Explicit 3-D waypoint source [W][3] = (x km, y km, z m) of uam_eval_waypoints3d: a type of its
+// own, so PathSrc<GEN> and every kernel instantiating it stay as they are.
+struct PathSrc3 {
+    const double* __restrict__ wp;
+    __device__ __forceinline__ double alt(int j) const { return wp[3 * j + 2]; }
+    __device__ __forceinline__ void at(int j, double& px, double& py) const {
+        px = wp[3 * j];
+        py = wp[3 * j + 1];
+    }
+};
+
+// XYZ (volume mode, GEN = false): wp is [P][W][3] and the altitude the stored z (K4ew); the
+// instances without it are unchanged.
+template <int MODE, bool GEN, bool XYZ = false>
 __global__ __launch_bounds__(256) void k_eval_wave(KGeom g, KParams p, KRaster rs, KVolume vs,
                                                    const uint4* __restrict__ rec,
                                                    const double* __restrict__ wp,
@@ -3552,26 +3565,30 @@ __global__ __launch_bounds__(256) void k_eval_wave(KGeom g, KParams p, KRaster r
     double* ph = sg + W;  // Phi_j / N
     double* ps = ph + W;  // no-fly psi_j
     double* kn = ps + W;  // kinematic rows [N][3]
-    PathSrc<GEN> src;
-    src.W = W;
-    src.wp = nullptr;
-    src.u = nullptr;
-    src.x0 = src.y0 = src.xf = src.yf = 0.0;
-    src.za = src.zb = 0.0;
-    if (GEN) {
-        const int64_t q = path / D;
-        const int d = (int)(path - q * D);
-        if (MODE == UAM_MODE_VOLUME) {
-            const double* pr = pairs + 6 * q;
-            src.x0 = pr[0], src.y0 = pr[1], src.za = pr[2];
-            src.xf = pr[3], src.yf = pr[4], src.zb = pr[5];
-        } else {
-            const double4 pr = reinterpret_cast<const double4*>(pairs)[q];
-            src.x0 = pr.x, src.y0 = pr.y, src.xf = pr.z, src.yf = pr.w;
-        }
-        src.u = utab + (int64_t)d * N * 2;
+    std::conditional_t<XYZ, PathSrc3, PathSrc<GEN>> src;
+    if constexpr (XYZ) {
+        src.wp = wp + path * (int64_t)W * 3;
     } else {
-        src.wp = wp + path * (int64_t)W * 2;
+        src.W = W;
+        src.wp = nullptr;
+        src.u = nullptr;
+        src.x0 = src.y0 = src.xf = src.yf = 0.0;
+        src.za = src.zb = 0.0;
+        if (GEN) {
+            const int64_t q = path / D;
+            const int d = (int)(path - q * D);
+            if (MODE == UAM_MODE_VOLUME) {
+                const double* pr = pairs + 6 * q;
+                src.x0 = pr[0], src.y0 = pr[1], src.za = pr[2];
+                src.xf = pr[3], src.yf = pr[4], src.zb = pr[5];
+            } else {
+                const double4 pr = reinterpret_cast<const double4*>(pairs)[q];
+                src.x0 = pr.x, src.y0 = pr.y, src.xf = pr.z, src.yf = pr.w;
+            }
+            src.u = utab + (int64_t)d * N * 2;
+        } else {
+            src.wp = wp + path * (int64_t)W * 2;
+        }
     }
     for (int j = lane; j < W; j += 64) {
         double x, y;
@@ -3736,6 +3753,207 @@ __global__ __launch_bounds__(256) void k_eval_wave(KGeom g, KParams p, KRaster r
         if (out.min_clearance)
             out.min_clearance[path] = MODE == UAM_MODE_RASTER ? p.altitude - hmax : cmin;
         if (out.below_terrain) out.below_terrain[path] = below;
+    }
+}
+
+// ----------------------------------------------------------------------------------------
+// K4e / K4ew / K4p: the volume over explicit 3-D waypoints and over altitude-profile candidates
+// (uam_eval_waypoints3d, uam_gen_paths3d, uam_eval_generated3d_profiles).  Definition: the
+// oracle's orc_eval_paths3d, sequential sums in waypoint order.  K4ew is k_eval_wave's XYZ
+// instance.
+
+// K4e: lane per path through eval_path's volume mode (8 gathers in flight per lane)
+__global__ __launch_bounds__(256) void k_eval_waypoints3d(KGeom g, KParams p, KVolume vs,
+                                                          const double* __restrict__ wp3,
+                                                          int64_t n_paths, KOut out) {
+    const int64_t path = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (path >= n_paths) return;
+    PathSrc3 src;
+    src.wp = wp3 + path * (int64_t)(p.N + 2) * 3;
+    const KRaster rs{};
+    const PathAcc a =
+        eval_path<UAM_MODE_VOLUME, false, 8>(g, p, rs, vs, nullptr, src, path, out);
+    write_path(out, p, UAM_MODE_VOLUME, path, a);
+}
+
+// Altitude of waypoint j under a profile row c = ztab[a][j] (include/uampath.h): two products,
+// their sum, then the third coefficient, each rounded (-ffp-contract=off).
+__device__ __forceinline__ double profile_alt(double za, double zb, const double* c) {
+    return (za * c[0] + zb * c[1]) + c[2];
+}
+
+// wp3 [Q*D*A][W][3]: x/y exactly k_gen_paths' points, z by the profile table (ztab == nullptr,
+// A = 1: the straight climb of uam_eval_generated3d, PathSrc::alt's expression)
+__global__ __launch_bounds__(256) void k_gen_paths3d(const double* __restrict__ pairs6,
+                                                     int64_t n_pairs,
+                                                     const double* __restrict__ utab, int D,
+                                                     const double* __restrict__ ztab, int A,
+                                                     int N, double* __restrict__ wp3) {
+    const int W = N + 2;
+    const int64_t total = n_pairs * D * A * W;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t path = i / W;
+        const int j = (int)(i - path * W);
+        const int64_t qd = path / A;
+        const int a = (int)(path - qd * A);
+        const int64_t q = qd / D;
+        const int d = (int)(qd - q * D);
+        const double* pr = pairs6 + 6 * q;
+        double px, py;
+        if (j == 0) {
+            px = pr[0];
+            py = pr[1];
+        } else if (j == W - 1) {
+            px = pr[3];
+            py = pr[4];
+        } else {
+            const double* u = utab + ((int64_t)d * N + (j - 1)) * 2;
+            arc_point(pr[0], pr[1], pr[3], pr[4], u[0], u[1], px, py);
+        }
+        wp3[3 * i] = px;
+        wp3[3 * i + 1] = py;
+        wp3[3 * i + 2] = ztab ? profile_alt(pr[2], pr[5], ztab + ((int64_t)a * W + j) * 3)
+                              : pr[2] + (pr[5] - pr[2]) * ((double)j / (double)(W - 1));
+    }
+}
+
+// K4p: the A altitude profiles of one lateral candidate (pair q, displacement d) on one lane.
+// Global wave w -> displacement d = w % D (wave-uniform: the unit-arc row and the profile rows
+// are read through scalar loads), pairs [(w / D) * 64, +64), as k_eval_generated maps them; the
+// waves of a workgroup are consecutive displacements of the same 64 pairs.  (k_eval_pairs'
+// workgroup of all D waves would cap the kernel at 128 registers, which 8 sets of accumulators
+// do not fit.)  The A paths share their x/y points, so pass 1 (L, length, kinematic sum) runs
+// once, and they share each waypoint's column, so its entry {terrain, flags} is loaded once;
+// the A voxels of a waypoint lie in that column's run of nz layers (8 B each: 16 layers a 128-B
+// line).  Per chunk of PC waypoints the column loads and the A x PC voxel loads are issued
+// together and consumed in waypoint order, each profile into its own accumulators, so every
+// profile keeps the sequential bits of eval_path.  AB: the compile-time bound of A
+// (accumulators and chunk in registers).  The in-volume test depends on the waypoint's own z,
+// so off / hits / below / clearance are per profile.  Outputs are stored from registers (A
+// consecutive paths per lane); the selection runs afterwards (k_argmin over D * A).
+struct ProfAcc {
+    double cost, nsum, cmin;
+    int32_t nh, off, below;
+};
+
+template <int AB>
+constexpr int prof_chunk() {
+    return AB <= 2 ? 8 : 4;
+}
+
+template <int AB>
+__global__ __launch_bounds__(256) void k_eval_profiles(KParams p, KVolume vs,
+                                                       const double* __restrict__ pairs6,
+                                                       int64_t n_pairs,
+                                                       const double* __restrict__ utab, int D,
+                                                       const double* __restrict__ ztab, int A,
+                                                       int64_t n_waves, KOut out,
+                                                       const int32_t* __restrict__ order) {
+    constexpr int PC = prof_chunk<AB>();
+    // order (optional): slot -> pair, K4's spatial order of the pairs; workgroup b then takes
+    // the waves of xcd_chunk(b), so the pairs sharing an XCD's L2 are spatial neighbours.
+    // Every pair is read and written at its own index: results do not depend on the order.
+    const int64_t blk = order ? xcd_chunk(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+    const int64_t wave = blk * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (wave >= n_waves) return;  // whole wave
+    const int lane = threadIdx.x & 63;
+    const int d = __builtin_amdgcn_readfirstlane((int)(wave % D));
+    const int64_t slot = (wave / D) * 64 + lane;
+    const bool in = slot < n_pairs;
+    const int64_t q = (order && in) ? (int64_t)order[slot] : slot;
+    const int N = p.N, W = N + 2;
+    if (in) {
+        PathSrc<true> src;
+        src.W = W;
+        src.wp = nullptr;
+        const double* pr = pairs6 + 6 * q;
+        src.x0 = pr[0], src.y0 = pr[1], src.za = pr[2];
+        src.xf = pr[3], src.yf = pr[4], src.zb = pr[5];
+        src.u = utab + (int64_t)d * N * 2;
+        PathAcc g1;
+        path_pass1<true>(p, src, nullptr, g1);
+        ProfAcc acc[AB];
+#pragma unroll
+        for (int a = 0; a < AB; ++a) {
+            acc[a].cost = (double)(N + 1) * g1.L;
+            acc[a].nsum = 0.0;
+            acc[a].cmin = INFINITY;
+            acc[a].nh = 0, acc[a].off = 0, acc[a].below = 0;
+        }
+        const double dN = (double)N;
+        const int64_t path0 = (q * D + d) * A;
+        // the altitude of waypoint j under profile a (recomputed when consumed: its operands
+        // come from scalar loads, and holding PC x A of them would cost as many registers as
+        // the voxels)
+        auto alt = [&](int a, int j) {
+            return ztab ? profile_alt(src.za, src.zb, ztab + ((int64_t)a * W + j) * 3)
+                        : src.alt(j);
+        };
+        for (int j0 = 0; j0 < W; j0 += PC) {
+            uint2 col[PC], vox[PC][AB];
+            uint32_t inb[PC];
+#pragma unroll
+            for (int t = 0; t < PC; ++t) {
+                const int j = j0 + t;
+                inb[t] = 0;
+                if (j >= W) continue;
+                double x0, x1;
+                src.at(j, x0, x1);
+                // vol_fetch's column arithmetic, once for the A profiles
+                const double fx = floor((x0 - vs.x0) * vs.inv_dx);
+                const double fy = floor((vs.y_top - x1) * vs.inv_dy);
+                const bool inxy = (fx >= 0.0) && (fx < (double)vs.nx) && (fy >= 0.0) &&
+                                  (fy < (double)vs.ny);
+                const int32_t ix = inxy ? (int32_t)fx : 0, iy = inxy ? (int32_t)fy : 0;
+                const int64_t c = (int64_t)iy * vs.nx + ix;
+                col[t] = vs.col[c];  // unconditional: off-volume lanes read column 0 (cached)
+#pragma unroll
+                for (int a = 0; a < AB; ++a) {
+                    if (a >= A) continue;
+                    const double fz = floor((alt(a, j) - vs.z0) * vs.inv_dz);
+                    const bool inz = inxy && (fz >= 0.0) && (fz < (double)vs.nz);
+                    const int64_t v = c * vs.nz + (inz ? (int64_t)fz : (int64_t)0);
+                    vox[t][a] = vs.vox[v];
+                    inb[t] |= inz ? 1u << a : 0u;
+                    if (out.cells) out.cells[(path0 + a) * W + j] = inz ? (int32_t)v : -1;
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < PC; ++t) {
+                if (j0 + t >= W) break;
+                const double terrain = (double)__uint_as_float(col[t].x);
+                const int nfz = (col[t].y & UAM_FLAG_NFZ) ? 1 : 0;
+#pragma unroll
+                for (int a = 0; a < AB; ++a) {
+                    if (a >= A) continue;
+                    if (!((inb[t] >> a) & 1u)) {
+                        ++acc[a].off;
+                        continue;
+                    }
+                    const double z = alt(a, j0 + t);
+                    acc[a].cost = acc[a].cost + (double)__uint_as_float(vox[t][a].x) / dN;
+                    acc[a].nsum = acc[a].nsum + (double)__uint_as_float(vox[t][a].y);
+                    acc[a].nh += nfz;
+                    acc[a].below += vol_below(vs, z, col[t].x) ? 1 : 0;
+                    acc[a].cmin = fmin(acc[a].cmin, z - terrain);
+                }
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < AB; ++a) {
+            if (a >= A) continue;
+            const int64_t gp = path0 + a;
+            if (out.cost) out.cost[gp] = acc[a].cost;
+            if (out.length_q) out.length_q[gp] = g1.L;
+            if (out.length) out.length[gp] = g1.len;
+            if (out.kin_sum) out.kin_sum[gp] = g1.ksum;
+            if (out.nfz_sum) out.nfz_sum[gp] = acc[a].nsum;
+            if (out.min_clearance) out.min_clearance[gp] = acc[a].cmin;
+            if (out.nfz_hits) out.nfz_hits[gp] = acc[a].nh;
+            if (out.offmap) out.offmap[gp] = acc[a].off;
+            if (out.below_terrain) out.below_terrain[gp] = acc[a].below;
+        }
     }
 }
 
@@ -9597,6 +9815,179 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
     st = ktime_end(ctx, (hipStream_t)stream);
     if (st) return st;
     if (order) return order_done(ctx, (hipStream_t)stream);
+    return UAM_OK;
+}
+
+// ---- the volume over explicit 3-D waypoints and altitude-profile candidates (K4e / K4ew / K4p)
+
+// UAM_OPT_EXACT_SUM_VOLUME's contract is "exact or an error, never ordered": these forms add in
+// waypoint order, so with the option on they refuse on the host
+static int no_exact_volume(const uam_ctx* ctx, const char* call) {
+    if (!ctx->exact_sum_vol) return UAM_OK;
+    return fail(UAM_E_INVALID,
+                "UAM_OPT_EXACT_SUM_VOLUME: %s forms ordered sums and has no exact form", call);
+}
+
+// vol_dev's sections as the kernels read them (uam_eval_generated3d's checks, in its order)
+static int volume_view(const uam_volume_desc* vd, const void* vol, KVolume* kv) {
+    if (!vol) return fail(UAM_E_INVALID, "pointer is NULL");
+    if ((uintptr_t)vol & 255) return fail(UAM_E_INVALID, "volume buffer not 256-B aligned");
+    kv->vox = (const uint2*)vol;
+    kv->col = (const uint2*)((const char*)vol + vol_col_offset(vd));
+    kv->cbits = (const uint32_t*)((const char*)vol + vol_bits_offset(vd));
+    vol_bits_dims(vd, kv);
+    return UAM_OK;
+}
+
+static int profile_dims(int64_t n_pairs, int32_t D, const double* ztab, int32_t A) {
+    if (n_pairs < 0 || D < 1 || D > 16)
+        return fail(UAM_E_INVALID, "n_pairs < 0 or D outside [1, 16]");
+    if (A < 1 || A > 8) return fail(UAM_E_INVALID, "A = %d outside [1, 8]", A);
+    if (!ztab && A != 1)
+        return fail(UAM_E_INVALID, "ztab is NULL (the straight climb) with A = %d: A must be 1", A);
+    if (n_pairs > (((int64_t)1 << 31) - 1) / ((int64_t)D * A))
+        return fail(UAM_E_INVALID, "2^31 or more paths");
+    return UAM_OK;
+}
+
+int uam_gen_paths3d(uam_ctx* ctx, const double* pairs6, int64_t n_pairs, const double* utab,
+                    int32_t D, const double* ztab, int32_t A, double* wp3, uam_stream stream) {
+    int st = check_ctx(ctx, true);
+    if (st) return st;
+    st = profile_dims(n_pairs, D, ztab, A);
+    if (st) return st;
+    if (n_pairs == 0) return UAM_OK;
+    if (!pairs6 || !utab || !wp3) return fail(UAM_E_INVALID, "pointer is NULL");
+    DeviceGuard dg(ctx->device);
+    const int64_t total = n_pairs * D * A * (ctx->kp.N + 2);
+    hipLaunchKernelGGL(k_gen_paths3d, dim3(grid_for(total, 256)), dim3(256), 0,
+                       (hipStream_t)stream, pairs6, n_pairs, utab, D, ztab, A, ctx->kp.N, wp3);
+    HIP_TRY(hipGetLastError());
+    return UAM_OK;
+}
+
+int uam_eval_waypoints3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                         const double* wp3, int64_t n_paths, const uam_path_outputs* out,
+                         uam_stream stream) {
+    if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
+        const int st = device_status(ctx);
+        if (st) return st;
+    }
+    int st = check_ctx(ctx, true);
+    if (st) return st;
+    st = no_exact_volume(ctx, "uam_eval_waypoints3d");
+    if (st) return st;
+    if (n_paths < 0) return fail(UAM_E_INVALID, "n_paths < 0");
+    if (n_paths == 0) return UAM_OK;
+    KVolume kv;
+    st = make_kvolume(vd, &kv);  // under 2^31 voxels: every voxel index fits out->cells
+    if (st) return st;
+    if (!wp3) return fail(UAM_E_INVALID, "pointer is NULL");
+    st = volume_view(vd, vol, &kv);
+    if (st) return st;
+    const KOut ko = make_kout(out);
+    DeviceGuard dg(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_group = 0;
+    const int64_t per_wave = ewave_doubles(ctx->kp.N) * (int64_t)sizeof(double);
+    if (want_wave(ctx, n_paths) && per_wave <= 65536) {  // launch_wave's shape
+        const int wpb = (int)std::min<int64_t>(4, 65536 / per_wave);
+        const int64_t blocks = (n_paths + wpb - 1) / wpb;
+        if (blocks <= INT32_MAX) {
+            ctx->last_kernel = "K4ew";
+            st = ktime_begin(ctx, s);
+            if (st) return st;
+            const KRaster kr{};
+            hipLaunchKernelGGL((k_eval_wave<UAM_MODE_VOLUME, false, true>), dim3((unsigned)blocks),
+                               dim3(64 * wpb), (size_t)(wpb * per_wave), s, ctx->kg, ctx->kp, kr,
+                               kv, nullptr, wp3, nullptr, nullptr, 1, n_paths, ko);
+            HIP_TRY(hipGetLastError());
+            return ktime_end(ctx, s);
+        }
+    }
+    const int64_t blocks = (n_paths + 255) / 256;
+    if (blocks > INT32_MAX) return fail(UAM_E_INVALID, "batch too large");
+    ctx->last_kernel = "K4e";
+    st = ktime_begin(ctx, s);
+    if (st) return st;
+    hipLaunchKernelGGL(k_eval_waypoints3d, dim3((unsigned)blocks), dim3(256), 0, s, ctx->kg,
+                       ctx->kp, kv, wp3, n_paths, ko);
+    HIP_TRY(hipGetLastError());
+    return ktime_end(ctx, s);
+}
+
+int uam_eval_generated3d_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                                  const double* pairs6, int64_t n_pairs, const double* utab,
+                                  int32_t D, const double* ztab, int32_t A,
+                                  const uam_path_outputs* out, uam_stream stream) {
+    if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
+        const int st = device_status(ctx);
+        if (st) return st;
+    }
+    int st = check_ctx(ctx, true);
+    if (st) return st;
+    st = no_exact_volume(ctx, "uam_eval_generated3d_profiles");
+    if (st) return st;
+    st = profile_dims(n_pairs, D, ztab, A);
+    if (st) return st;
+    if (n_pairs == 0) return UAM_OK;
+    KVolume kv;
+    st = make_kvolume(vd, &kv);
+    if (st) return st;
+    if (!pairs6 || !utab) return fail(UAM_E_INVALID, "pointer is NULL");
+    const KOut ko = make_kout(out);
+    int32_t* best_f = out ? out->best_fval_idx : nullptr;
+    int32_t* best_l = out ? out->best_length_idx : nullptr;
+    if ((best_f && !ko.cost) || (best_l && !ko.length))
+        return fail(UAM_E_INVALID,
+                    "best_fval_idx needs the cost output, best_length_idx the length output");
+    st = volume_view(vd, vol, &kv);
+    if (st) return st;
+    DeviceGuard dg(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_waves = (n_pairs + 63) / 64 * D;
+    const int64_t blocks = (n_waves + 3) / 4;
+    if (blocks > INT32_MAX) return fail(UAM_E_INVALID, "batch too large");
+    ctx->last_kernel = "K4p";
+    ctx->last_group = 0;
+    // K4's pair order over the volume's x/y extent (results do not depend on it)
+    const int32_t* order = nullptr;
+    if (ctx->pair_order && n_pairs >= 4096 && n_pairs < INT32_MAX) {
+        KRaster kxy{};
+        kxy.nx = kv.nx, kxy.ny = kv.ny, kxy.x0 = kv.x0, kxy.y_top = kv.y_top;
+        kxy.dx = vd->dx, kxy.dy = vd->dy;
+        st = raster_pair_order(ctx, kxy, pairs6, n_pairs, s, &order, 1);
+        if (st) return st;
+    }
+    st = ktime_begin(ctx, s);
+    if (st) return st;
+#define UAM_PROFILES(AB_)                                                                      \
+    hipLaunchKernelGGL((k_eval_profiles<AB_>), dim3((unsigned)blocks), dim3(256), 0, s,       \
+                       ctx->kp, kv, pairs6, n_pairs, utab, D, ztab, A, n_waves, ko, order)
+    if (A == 1)
+        UAM_PROFILES(1);
+    else if (A == 2)
+        UAM_PROFILES(2);
+    else if (A <= 4)
+        UAM_PROFILES(4);
+    else
+        UAM_PROFILES(8);
+#undef UAM_PROFILES
+    HIP_TRY(hipGetLastError());
+    st = ktime_end(ctx, s);
+    if (st) return st;
+    if (order) {
+        st = order_done(ctx, s);
+        if (st) return st;
+    }
+    // main.py:175-180 over the pair's D * A candidates in index order c = d * A + a (every
+    // profile of a displacement stores the same length)
+    const dim3 g2(grid_for(n_pairs, 256, INT32_MAX));
+    if (best_f)
+        hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.cost, n_pairs, D * A, 1, best_f);
+    if (best_l)
+        hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.length, n_pairs, D * A, 0, best_l);
+    HIP_TRY(hipGetLastError());
     return UAM_OK;
 }
 

@@ -367,7 +367,8 @@ class Engine:
     def last_kernel(self):
         """Which path evaluation the last eval_generated / eval_generated3d ran (uam_last_kernel:
         "K2h+pack", "K2hx+pack" (the exact sums), "K2g+pack", "K4h+pack", "K4hx+pack" (the
-        volume's exact sums), "K2s+pack", "K2+skip", "K2w", "K3b", ...)."""
+        volume's exact sums), "K2s+pack", "K2+skip", "K2w", "K3b", ...), or the last
+        eval_waypoints3d ("K4e" / "K4ew") / eval_generated3d_profiles ("K4p")."""
         return self.lib.uam_last_kernel(self._ctx).decode()
 
     def last_group(self):
@@ -558,6 +559,73 @@ class Engine:
             self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf),
             _ptr(volume.packed), _ptr(pr), Q, _ptr(ut), D, ctypes.byref(s), self.stream),
             "uam_eval_generated3d")
+        return o
+
+    # -- volume: explicit 3-D waypoints and altitude-profile candidates -------------------
+    def _profile_inputs(self, pairs6, utab, ztab):
+        """(pairs6 [Q, 6], utab [D, N, 2], ztab [A, N+2, 3] or None, Q, D, A) on the device,
+        shapes checked against params.N (profiles.py builds the tables)."""
+        torch = _torch()
+        N = self.params.N
+        pr = self.tensor(pairs6, torch.float64).reshape(-1, 6)
+        ut = self.tensor(utab, torch.float64)
+        if ut.dim() != 3 or ut.shape[1] != N or ut.shape[2] != 2:
+            raise ValueError(f"arc table has shape {tuple(ut.shape)}, params N={N} needs "
+                             f"[D, {N}, 2]")
+        zt, A = None, 1
+        if ztab is not None:
+            zt = self.tensor(ztab, torch.float64)
+            if zt.dim() != 3 or zt.shape[1] != N + 2 or zt.shape[2] != 3:
+                raise ValueError(f"profile table has shape {tuple(zt.shape)}, params N={N} "
+                                 f"needs [A, {N + 2}, 3]")
+            A = zt.shape[0]
+        return pr, ut, zt, pr.shape[0], ut.shape[0], A
+
+    def gen_paths3d(self, pairs6, utab, ztab=None):
+        """The waypoints [Q*D*A, N+2, 3] (x km, y km, z m) of pairs6 [Q, 6] x utab [D, N, 2] x
+        the altitude-profile table ztab [A, N+2, 3] (uam_gen_paths3d; None: A = 1, the straight
+        climb of eval_generated3d); path p = (q*D + d)*A + a."""
+        torch = _torch()
+        pr, ut, zt, Q, D, A = self._profile_inputs(pairs6, utab, ztab)
+        wp3 = self.empty((Q * D * A, self.params.N + 2, 3), torch.float64)
+        _lib.check(self.lib.uam_gen_paths3d(self._ctx, _ptr(pr), Q, _ptr(ut), D, _ptr(zt), A,
+                                            _ptr(wp3), self.stream), "uam_gen_paths3d")
+        return wp3
+
+    def eval_waypoints3d(self, wp3, volume, want_cells=False):
+        """wp3 [P, N+2, 3] float64 (x km, y km, z m) against the volume's voxels
+        (uam_eval_waypoints3d: the oracle's eval_paths3d bit for bit).  Reads volume.buf only."""
+        torch = _torch()
+        W = self.params.N + 2
+        w = self.tensor(wp3, torch.float64)
+        if w.dim() < 2 or w.shape[-1] != 3 or w.shape[-2] != W:
+            raise ValueError(f"waypoints have shape {tuple(w.shape)}, params N={W - 2} needs "
+                             f"[P, {W}, 3]")
+        w = w.reshape(-1, W, 3)
+        P = w.shape[0]
+        o, s = self._outputs(P, W, _lib.MODE_VOLUME, want_cells, False)
+        _lib.check(self.lib.uam_eval_waypoints3d(
+            self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf), _ptr(w), P,
+            ctypes.byref(s), self.stream), "uam_eval_waypoints3d")
+        return o
+
+    def eval_generated3d_profiles(self, pairs6, utab, ztab, volume, want_cells=False,
+                                  outputs=None):
+        """eval_waypoints3d of gen_paths3d's waypoints in one kernel, with the selection over
+        each pair's D*A candidates (uam_eval_generated3d_profiles): path p = (q*D + d)*A + a,
+        best_fval_idx / best_length_idx [Q] hold the candidate c = d*A + a.  Reads volume.buf
+        only."""
+        pr, ut, zt, Q, D, A = self._profile_inputs(pairs6, utab, ztab)
+        W = self.params.N + 2
+        if outputs is not None:
+            o, s = outputs
+            _check_outputs(o, Q * D * A, Q, W)
+        else:
+            o, s = self._outputs(Q * D * A, W, _lib.MODE_VOLUME, want_cells, False, n_pairs=Q)
+        _lib.check(self.lib.uam_eval_generated3d_profiles(
+            self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf), _ptr(pr), Q,
+            _ptr(ut), D, _ptr(zt), A, ctypes.byref(s), self.stream),
+            "uam_eval_generated3d_profiles")
         return o
 
     def gen_paths(self, pairs, utab):

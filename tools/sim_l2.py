@@ -7,7 +7,11 @@ then t + 1, ...), and every gather's 128-B line through a 4 MiB 16-way LRU per X
 16-B records (code-3 blocks, 8 cells per line); code-0 waypoints issue no request.  Prints the
 modelled misses per step for each ordering, to be compared with the PMC's TCC_MISS.
 
+--no-ragged-bins: one bin per tile (K2h / K4h's key) instead of the ragged last group's items in
+bins of their own (K2g's key); --per-xcd: the misses of each XCD's range beside the total.
+
 usage: python tools/sim_l2.py [--R 4096] [--pairs 100000] [--groups 21,24] [--orders morton4,hilbert4]
+                              [--no-ragged-bins] [--per-xcd]
 """
 import argparse
 import ctypes
@@ -58,6 +62,9 @@ def main():
     ap.add_argument("--window", type=int, default=32768)
     ap.add_argument("--rec-layouts", default="1x8",
                     help="16-B record lines: HxW cells per 128-B line (1x8 = row-major)")
+    ap.add_argument("--no-ragged-bins", action="store_true",
+                    help="one bin per tile: the ragged last group's items keep their tile's key")
+    ap.add_argument("--per-xcd", action="store_true", help="also print each XCD's misses")
     a = ap.parse_args()
     so = "/tmp/libsiml2.so"
     subprocess.run(["gcc", "-O2", "-shared", "-fPIC", "-o", so,
@@ -125,7 +132,7 @@ def main():
           j1 = np.minimum(j0 + G, W)
           mid = (j0 + j1 - 1) // 2
           mx, my, mi = ix[items_p, mid], iy[items_p, mid], inr[items_p, mid]
-          last = (items_s == nseg - 1) & (W % G != 0)
+          last = (items_s == nseg - 1) & (W % G != 0) & (not a.no_ragged_bins)
           # the item's direction (its first to last waypoint) in 2^db bins, a minor key
           ex, ey = ix[items_p, j1 - 1] - ix[items_p, j0], iy[items_p, j1 - 1] - iy[items_p, j0]
           ang = (np.arctan2(ey, ex) + np.pi) / (2 * np.pi)
@@ -147,7 +154,7 @@ def main():
               perm = np.argsort(k, kind="stable")
               n = perm.size
               nb = (n + 255) // 256
-              total = 0
+              total, per = 0, []
               for x in range(8):
                   c0 = x * (nb >> 3) + min(x, nb & 7)
                   c1 = c0 + (nb >> 3) + (1 if x < (nb & 7) else 0)
@@ -161,9 +168,12 @@ def main():
                           ok = t < L
                           stream.append(line[p[ok], s0[ok] + t])
                   st = np.ascontiguousarray(np.concatenate(stream))
-                  total += lib.sim_lru(st.ctypes.data, st.size, 2048, 16)
+                  per.append(lib.sim_lru(st.ctypes.data, st.size, 2048, 16))
+                  total += per[-1]
               print(f"G={G:2d} {order:9s}: modelled L2 misses {total / 1e6:6.2f}M per step "
                     f"({total / max(1, (line != 0xFFFFFFFF).sum()):.3f} per gather)", flush=True)
+              if a.per_xcd:
+                  print("      per XCD (M): " + " ".join(f"{v / 1e6:.2f}" for v in per), flush=True)
 
 
 if __name__ == "__main__":

@@ -80,6 +80,14 @@
 #ifndef UAM_K2H_BS  // K2h evaluation: items per workgroup
 #define UAM_K2H_BS 256
 #endif
+#ifndef UAM_K2H_RAGGED_BINS
+// K2h / K4h sort key: 1 gives a ragged last group's items bins of their own, as K2g's key does
+// (there the straight-line chunks need them); 0 sorts on one bin per tile (per tile and band),
+// so the last groups' items sit among their tile's other items instead of forming a second,
+// sparser pass over all tiles at the end of the order (tools/sim_l2.py --no-ragged-bins; the
+// measured A/B is in DESIGN.md §5)
+#define UAM_K2H_RAGGED_BINS 0
+#endif
 #ifndef UAM_SHAPE_GRID_N  // shape-grid index: cells per side
 #define UAM_SHAPE_GRID_N 64
 #endif
@@ -5251,7 +5259,8 @@ __global__ __launch_bounds__(1024) void k_seg_final(KParams p, KSeg ks, KOut out
 // sums differ by rounding only (<= 1e-12 relative, tests/test_oracle_golden.py); against the
 // grouped oracle they are bit-exact.
 constexpr int G_TBITS_MAX = 6;                          // up to 64 x 64 tiles over the raster
-// tile bins twice over (a ragged last group's items have their own) + one for off-raster / NaN
+// tile bins twice over (K2g: a ragged last group's items have their own; K2h / K4h sort on one
+// bin per tile and use half of them) + one for off-raster / NaN
 constexpr int G_BINS_MAX = (2 << (2 * G_TBITS_MAX)) + 1;
 constexpr int G_NBK = UAM_G_NBK;                        // partitions of the counting sort
 constexpr int G_HIST_DYN_MAX = 119 * 1024;  // k_g_hist's dynamic LDS (K2h seeds) beside its 40 KiB
@@ -5603,8 +5612,14 @@ __global__ __launch_bounds__(1024) void k_g_hist(KParams p, KRaster rs, KGrp kg)
             if ((fx >= 0.0) && (fx < (double)rs.nx) && (fy >= 0.0) && (fy < (double)rs.ny)) {
                 const uint32_t tx = (uint32_t)fx >> kg.tshift, ty = (uint32_t)fy >> kg.tshift;
                 key = tk[(ty << kg.tbits) | tx];
-                // a ragged last group's items in their own bins: the waves then rarely mix
-                // group lengths, so k_g_eval's straight-line chunks stay wave-uniform
+                // K2g (kg.last_bin > 0): a ragged last group's items in their own bins; the
+                // waves then rarely mix group lengths, so k_g_eval's straight-line chunks stay
+                // wave-uniform.  K2h adds nothing (kg.last_bin == 0, one bin per tile): h_item's
+                // chunk loop runs the wave's most chunks and masks every slot past a lane's own
+                // group (vjb, vinB, nvB), and its LDS rows are padded by G + CH slots, which
+                // covers a last group of one waypoint in a wave of full ones -- so a wave may
+                // mix group lengths freely, and the last groups' items stay among their tile's
+                // other items instead of forming a sparse second pass over all the tiles
                 if (sg[k] == kg.nseg - 1) key += kg.last_bin;
             }
             kg.key[i] = (uint16_t)key;
@@ -6981,6 +6996,8 @@ __global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
                 (tz >= 0.0) && (tz < (double)vs.nz)) {
                 const uint32_t cx = (uint32_t)tx >> kg.tshift, cy = (uint32_t)ty >> kg.tshift;
                 key = ((uint32_t)tz >> vs.zshift) * tiles + tk[(cy << kg.tbits) | cx];
+                // (kg.last_bin is 0, one bin per tile and band, as K2h's: k_v_eval masks the
+                // slots past a lane's group and pads s_u / s_jw by G + 16 slots)
                 if (sg[k] == kg.nseg - 1) key += kg.last_bin;
             }
             kg.key[i] = (uint16_t)key;
@@ -8650,7 +8667,7 @@ static int volume_tiles(const uam_ctx* ctx, int32_t, int32_t, int32_t nbands, in
 
 // What every sorted form shares: the item and bin counts, the scan blocks, the 256-B aligned
 // scratch sizes (slot / seed: the family's bytes per item / per path) and KGrp's common fields.
-// Returns as grouped_plan does.
+// Reads pl->sim (set by the caller: it decides the bins).  Returns as grouped_plan does.
 static int grouped_sizes(uam_ctx* ctx, GPlan* pl, const double* pairs, int64_t n_pairs,
                          const double* utab, int32_t D, int32_t nx, int32_t ny, int32_t nbands,
                          GTilesFn tiles_of, size_t slot, size_t seed) {
@@ -8662,7 +8679,10 @@ static int grouped_sizes(uam_ctx* ctx, GPlan* pl, const double* pairs, int64_t n
     int tbits = 0;
     const int tiles = tiles_of(ctx, nx, ny, nbands, n_items, &tbits);
     if (!tiles) return grouped_no(*pl, "more (tile, band) bins than the sort holds");
-    const int last_bin = (W % G) ? tiles : 0;  // a ragged last group gets its own bins
+    // a ragged last group gets its own bins in K2g alone (k_g_eval's straight-line chunks);
+    // K2h / K4h mask every slot, so they sort on one bin per tile (UAM_K2H_RAGGED_BINS)
+    const bool ragged_bins = (W % G) && (!pl->sim || UAM_K2H_RAGGED_BINS);
+    const int last_bin = ragged_bins ? tiles : 0;
     const int bins = tiles + last_bin + 1;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     pl->ncnt = (int64_t)bins * G_NBK;

@@ -157,8 +157,8 @@ def _vary_psi(e, vol):
 
 
 def test_k4h_pack_layout(oracle_mod):
-    """uam_volume_pack against its definition (uampath.hip VpkDims / KVol4): the 4-B risk and
-    8-B {risk, |psi| | nfz << 31} planes per layer (4 x 8-column blocks, one index), the 16-B
+    """uam_volume_pack against its definition (uampath.hip VpkDims; KVol4: k4h.inc): the 4-B risk
+    and 8-B {risk, |psi| | nfz << 31} planes per layer (4 x 8-column blocks, one index), the 16-B
     voxels ({risk, psi} of the voxel, {terrain, flags} of the column; 4 x 2-column blocks), the
     8-B {risk, terrain} plane (4 x 4-column blocks), the column terrain (4 x 8), zero
     padding, the 2-bit code per 8 x 8 columns (3: a psi below zero in any

@@ -36,9 +36,14 @@ LDS = 65536
 def _source():
     import uam_path_planning_amd
 
-    path = os.path.join(os.path.dirname(uam_path_planning_amd.__file__), "csrc", "uampath.hip")
-    with open(path) as f:
-        return f.read()
+    # the one translation unit: the root and every piece it includes
+    csrc = os.path.join(os.path.dirname(uam_path_planning_amd.__file__), "csrc")
+    names = ["uampath.hip"] + sorted(f for f in os.listdir(csrc) if f.endswith(".inc"))
+    text = []
+    for name in names:
+        with open(os.path.join(csrc, name)) as f:
+            text.append(f.read())
+    return "".join(text)
 
 
 def _constants():

@@ -36,6 +36,29 @@ def test_header_symbols_exported(lib):
     assert lib.uam_abi_version() == _lib.ABI_VERSION == 2
 
 
+def test_csrc_includes_are_build_deps():
+    """Every file of csrc/ that uampath.hip or a .inc piece includes is in build.DEPS (a touched
+    one rebuilds the library), and no .inc piece of csrc/ is left un-included."""
+    from uam_path_planning_amd import build
+
+    csrc = os.path.dirname(os.path.abspath(build.SRC))
+    deps = {os.path.abspath(p) for p in build.DEPS}
+    pieces = {os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".inc")}
+    assert pieces
+    included = set()
+    for path in sorted(pieces | {os.path.abspath(build.SRC)}):
+        with open(path) as f:
+            names = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', f.read(), re.M)
+        for name in names:
+            target = os.path.normpath(os.path.join(csrc, name))
+            if os.path.dirname(target) != csrc:
+                continue  # (include/uampath.h: build.HEADER)
+            assert os.path.isfile(target), (path, name)
+            assert target in deps, (path, name)
+            included.add(target)
+    assert pieces <= included, sorted(os.path.basename(p) for p in pieces - included)
+
+
 def _vpk_sections(nx, ny, nz):
     """The packed volume's sections (uampath.hip VpkDims): header (codes, bounds, superblocks),
     bound scratch, then in 4 x 8-column blocks the 4-B risk layers, the 4-B column terrain and

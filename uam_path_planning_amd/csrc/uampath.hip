@@ -1,13 +1,43 @@
 // uampath.hip -- MI355X (gfx950) kernels + C ABI for batched candidate-path cost evaluation.
 //
-// Kernels (SURVEY.md §2 native inventory):
-//   k_prepare        per-shape normaliser psi(centre) (problem.py:79 recomputes it per call)
-//   k_eval_points    Φ / per-region / obstacle penalties + collides at arbitrary points
-//   k_raster_build   K1: one 16-B record per DEM cell {Φ, Σψ_nfz, dem, flags}
-//   k_dem_mosaic     VRT tile mosaic into the DEM plane
-//   k_eval_paths     K2 (raster gather) / K3 (analytic) with K4 (arc generator) fused
-//   k_argmin         K5: reference selection rule per candidate group
-//   k_gen_paths, k_path_length  batched create_x_init / length_of
+// One translation unit.  Contents, in order; the K2h, sum-scale and K4h text is in .inc pieces
+// included where it stood (a touched piece rebuilds the library: build.py DEPS), the rest is in
+// this file under the banner or lead comment named.  DESIGN.md section 4 lists for every kernel
+// the path that selects it.
+//   device-side tables; reference formulas (device)   no kernels
+//   kernels            k_prepare k_eval_points k_dem_mosaic k_volume_build k_volume_colbits
+//   K2 gather skip     k_raster_summary k_raster_summary_w
+//   Packed raster      k_raster_pack k_raster_pack_map k_raster_pack_map_w k_t4_bminmax
+//                      k_raster_bounds
+//   (K2 / K3 / volume, K4's arc generator fused)  k_eval_waypoints k_eval_generated k_eval_pairs
+//   K6, geometry       no kernels; then the wave-uniform shape walk K1, K3b and K6 share
+//   (K1)               k_raster_build k_raster_build_cells
+//   K3b                k_eval_pairs_k3b
+//   (K6, L-BFGS)       k_rf_push k_refine
+//   K2w                k_eval_wave
+//   K4e / K4ew / K4p   k_eval_waypoints3d k_gen_paths3d k_eval_profiles
+//   K7                 k_tm_points k_tm_sep k_reproject
+//   K8                 k_ccl_init_dem k_ccl_init_sub k_ccl_merge k_ccl_flatten k_ccl_count_roots
+//                      k_ccl_assign k_ccl_stats k_ccl_extents; ccl_tile.inc: k_ccl_tile
+//                      k_ccl_flatten_roots k_ccl_count_rootbits k_ccl_assign_rootbits
+//                      k_ccl_flatten_cells k_ccl_bmerge k_ccl_stats_rows k_ccl_extents_rows
+//   (utilities)        k_fill_segs_i32 k_scan_local k_scan_totals k_gen_paths k_argmin (K5)
+//                      k_path_length
+//   host side          last error, HIP_TRY, DeviceGuard, grid_for, shape_box
+//   Pair order         k_pair_bounds k_pair_keys k_pair_scan k_pair_scatter (K3)
+//                      k_rorder_hist k_rorder_scatter (K2)
+//   (K2s)              k_seg_hist k_seg_scatter k_seg_eval k_seg_final
+//   (K2g)              k_g_hist k_g_scatter k_g_eval k_g_final
+//   k2h.inc            K2h: k_h_eval k_h_eval_x k_cells k_h_final k_h_final_x; the exact-sum
+//                      arithmetic (X128) host and device share
+//   sum_scale.inc      k_sum_scale_init k_sum_scale
+//   k4h.inc            K4h: k_volume_pack_planes k_volume_pack_t4 k_volume_codes k_v_hist
+//                      k_v_eval (k_v_eval_x) k_v_final k_v_final_x
+//   struct uam_ctx and its helpers; then the C ABI (include/uampath.h) with the launches'
+//   static helpers between its entry points: context, geometry, params, K1; K2w launch; the
+//   option table; pair-order scratch and K2s launch; the grouped plan (K2g / K2h / K4h);
+//   PackDims and eval_generated's dispatch; raster, volume, 3-D profile, refinement, CRS,
+//   polygon and RCCL entry points.
 //
 // Numerics: float64 throughout, compiled with -ffp-contract=off so every product and sum is a
 // separately rounded IEEE operation in the reference's order (problem.py, quadratic_obstacle.py,
@@ -6029,1361 +6059,16 @@ __global__ __launch_bounds__(1024) void k_g_final(KParams p, KGrp kg, KOut out,
     put_selection(kg, bad, q0, t, s_cost, s_len, best_f, best_l);
 }
 
-// ---- K2h: generated candidates in the similarity form (oracle orc_eval_generated_h) --------
-// The candidate arcs are p_k = C + (1/2) R(v) u_k (u_0 = (1, 0), u_{N+1} = (-1, 0)): the unit
-// polyline of the displacement's table row under a similarity of scale h = |v| / 2.  Every
-// term that depends on the geometry only -- get_cost's L (problem.py:130-146, with the quirk's
-// anchor term), the true length (solver.py:49), the kinematic rows (problem.py:100-107, their
-// ratio rows scale with h, their turn rows are the unit polyline's) -- is a per-displacement
-// sum of the unit polyline times h (maxratio_smooth = 0), formed once per launch (UGeo) and
-// scaled per path in the output launch.  What stays per waypoint is what the raster decides:
-// the point, its cell and its record (Phi / N, psi, terrain, no-fly hit), with K2g's sort,
-// staging and grouped partial sums; so an item carries no f64 geometry (no segment norms, no
-// square roots, no kinematic rows) and its slot is 24 B.  Exact in real arithmetic; in float64
-// the geometry terms differ from per-segment sums by rounding only (bench.py
-// parity.vs_sequential_order on the whole cfg3 batch).
+// K2h: similarity form; exact-sum arithmetic (X128); k_h_eval*, k_cells, k_h_final*
+#include "k2h.inc"
 
-struct alignas(8) HSlot {  // 24 B per (path, group), written by one lane
-    double cost;   // Phi / N of the group's waypoints, from +0.0 in waypoint order
-    double psi;    // the no-fly psi, likewise
-    float hmax;    // max terrain of the group's waypoints as consume reads it
-    uint32_t cnt;  // nfz hits | off-raster << 8
-};
+// sum scales of the exact forms: k_sum_scale_init, k_sum_scale
+#include "sum_scale.inc"
 
-// ---- exact raster sums (UAM_OPT_EXACT_SUM; the definition: include/uampath.h) ---------------
-// A field's float32 words are added as integers in units of the raster's quantum
-// q = 2^(e - 96), e = max(1, largest biased exponent field among the finite cells) - 126: a
-// word is a signed 24-bit significand shifted by sh = max(b, 1) - 54 - e <= 72 (a right shift
-// truncates the magnitude), so |term| < 2^96 and a 128-bit two's-complement sum holds 2^31 of
-// them.  Integer addition is associative: the sum does not depend on the group length, on the
-// order of the groups or on which lane adds what.  One rounding, to float64, at the end.
-// The same functions run on the host (uam_exact_sum_host) and in the kernels.
-struct X128 {  // two's complement, two 64-bit limbs
-    uint64_t lo, hi;
-};
-enum : uint32_t { XF_NAN = 1u, XF_PINF = 2u, XF_NINF = 4u };  // a field's side flags
-constexpr int X_E_MIN = -125, X_E_MAX = 128;                  // the exponents a raster can give
+// K4h: packed volume, k_volume_pack_planes / _t4, k_volume_codes, k_v_hist, k_v_eval, k_v_final*
+#include "k4h.inc"
 
-__host__ __device__ __forceinline__ X128 x_add(X128 a, X128 b) {
-    X128 r;
-    r.lo = a.lo + b.lo;
-    r.hi = a.hi + b.hi + (r.lo < a.lo ? 1u : 0u);  // the low limb's carry
-    return r;
-}
-__host__ __device__ __forceinline__ X128 x_neg(X128 a) {
-    X128 r;
-    r.lo = ~a.lo + 1u;
-    r.hi = ~a.hi + (r.lo == 0 ? 1u : 0u);
-    return r;
-}
-// the exponent a word asks of its raster: max(b, 1) - 126 for a finite word, X_E_MIN otherwise
-__host__ __device__ __forceinline__ int32_t x_word_exp(uint32_t w) {
-    const int32_t b = (int32_t)((w >> 23) & 255u);
-    return b == 255 ? X_E_MIN : (b > 1 ? b : 1) - 126;
-}
-// a word's side flags (0 for a finite word)
-__host__ __device__ __forceinline__ uint32_t x_word_flags(uint32_t w) {
-    const uint32_t f = (w & 0x7fffffu) ? XF_NAN : (w >> 31) ? XF_NINF : XF_PINF;
-    return ((w >> 23) & 255u) == 255u ? f : 0u;
-}
-// a word's term at the exponent e >= x_word_exp(w) (0 for a non-finite word): selects and masks
-// only, so the kernels' consume loops stay straight-line code
-__host__ __device__ __forceinline__ X128 x_term(uint32_t w, int32_t e) {
-    const uint32_t b = (w >> 23) & 255u;
-    // the 24-bit significand: no hidden bit in a denormal, nothing from a non-finite word
-    const uint32_t m = b == 255u ? 0u : (w & 0x7fffffu) | (b ? 0x800000u : 0u);
-    const int sh = (int)(b ? b : 1u) - 54 - e;  // <= 72
-    const int rs = sh < 0 ? (-sh < 24 ? -sh : 24) : 0;  // a right shift of >= 24 leaves nothing
-    const int ls = sh > 0 ? sh : 0;
-    const int s = ls & 63;
-    const uint64_t a = (uint64_t)(m >> rs) << s;
-    const uint64_t c = ((uint64_t)m >> 1) >> (63 - s);  // the bits shifted past the low limb
-    const uint64_t lo = ls < 64 ? a : 0u;
-    const uint64_t hi = ls < 64 ? c : a;  // (ls >= 64: s <= 8, so a holds every bit)
-    // the sign: -t = ~t + 1 through a mask (the low limb carries only when it is 0)
-    const uint64_t sg = w >> 31, mk = 0u - sg;
-    X128 t;
-    t.lo = (lo ^ mk) + sg;
-    t.hi = (hi ^ mk) + (sg & (lo == 0 ? 1u : 0u));
-    return t;
-}
-// S 2^(e - 96) rounded once to float64, to nearest even: the magnitude normalised by its
-// leading zeros, its top 53 bits, a guard bit and the sticky rest (no int128 -> double
-// conversion: the device has none).  e in [X_E_MIN, X_E_MAX] keeps the result a normal double.
-__host__ __device__ __forceinline__ double x_to_double(X128 s, int32_t e) {
-    const bool neg = (s.hi >> 63) != 0;
-    if (neg) s = x_neg(s);
-    if ((s.lo | s.hi) == 0) return 0.0;
-    const int lz = s.hi ? __builtin_clzll(s.hi) : 64 + __builtin_clzll(s.lo);
-    X128 n;  // s << lz: bit 127 set
-    if (lz >= 64) {
-        n.hi = s.lo << (lz - 64);
-        n.lo = 0;
-    } else if (lz) {
-        n.hi = (s.hi << lz) | (s.lo >> (64 - lz));
-        n.lo = s.lo << lz;
-    } else {
-        n = s;
-    }
-    const uint64_t mant = n.hi >> 11;  // in [2^52, 2^53)
-    const bool guard = (n.hi >> 10) & 1u, sticky = ((n.hi & 0x3ffu) | n.lo) != 0;
-    const uint64_t inc = (guard && (sticky || (mant & 1u))) ? 1u : 0u;
-    const int ex = 127 - lz + e - 96;  // the leading bit's binade
-    // (a carry out of the fraction steps the exponent field: the next power of two)
-    uint64_t bits = ((uint64_t)(ex + 1023) << 52) + (mant - ((uint64_t)1 << 52)) + inc;
-    bits |= neg ? (uint64_t)1 << 63 : 0u;
-    double r;
-    __builtin_memcpy(&r, &bits, 8);
-    return r;
-}
-// a field's result: IEEE's for the non-finite words that were left out of S
-__host__ __device__ __forceinline__ double x_result(X128 s, uint32_t flags, int32_t e) {
-    if ((flags & XF_NAN) || ((flags & XF_PINF) && (flags & XF_NINF))) return __builtin_nan("");
-    if (flags & XF_PINF) return __builtin_inf();
-    if (flags & XF_NINF) return -__builtin_inf();
-    return x_to_double(s, e);
-}
-
-struct alignas(8) HSlotX {  // the exact form's slot: 40 B per (path, group)
-    uint64_t c_lo, c_hi;  // the sum of the group's phi terms
-    uint64_t n_lo, n_hi;  // the sum of its psi terms
-    float hmax;           // as HSlot's
-    uint32_t cnt;         // as HSlot's | phi flags << 16 | psi flags << 19
-};
-
-// every (path, group) item in K2g's sorted order: the group's points, cells and packed entries
-// only.  Every chunk is straight-line, in three phases so the LDS and memory round trips of its
-// CH slots overlap: the CH cells (the arc formula; p_0 / p_{W-1} from the pair's cells), the CH
-// header reads (code word, bound entry, superblock), then per slot the decisions and two
-// unconditional loads -- the code's entry (a slot with nothing to read takes the first p4 line)
-// and the terrain (the first t4 word unless fetched) -- by 32-bit offsets from the packed
-// copy's base; then the branch-free consume.
-//
-// The terrain maximum by bounds (build-defined; the outputs are exactly the per-waypoint
-// maximum's): min_clearance needs only the path's maximum terrain M, an order-free maximum, so
-// a waypoint's exact terrain is fetched (t4) only when it could still be M.  Every in-raster
-// waypoint w has decoded bounds lb_w <= terrain_w <= ub_w (pk_bound_raw + pk_bound_decode).  The item keeps
-//   Lb: a lower bound of M: the path's seed (below), raised by its own waypoints' lb as it
-//       goes; off-raster waypoints count +0.0, their exact value;
-//   E:  the maximum of exact terrain values of the path: the seed E0 (h_path_seed, formed once
-//       per path by the histogram launch: the exact terrain of the sampled waypoint with the
-//       largest lb) and those the item takes (fetched, code-3 records, off-raster +0.0, blocks
-//       whose bounds coincide).
-// It fetches w iff !(ub_w <= E) && !(ub_w < Lb) (NaN bounds: "no bound", always fetched).
-// Exactness: let w* hold M, in this item's group.  If w* was not taken exactly, then either
-// ub_w* <= E, so M <= E and E -- an exact terrain value of the path -- is M; or ub_w* < Lb <= M,
-// impossible since M <= ub_w*.  So the group holding M reports M, every group reports at most
-// its own maximum (E holds exact values), and the output launch's maximum over the groups is M.
-// (A group without M may report less than its own maximum: only the path's is an output.)
-// The slot's hmax is that E.  (Measured, cfg3: 0.19 fetches per waypoint with the sampled lb
-// alone and chunks issued one ahead, tools/k2h_counts.py.)
-// K2h workgroup: 256 items (cfg3 0.297 ms against 0.306 at 512, profiles/r05/k2h12)
-constexpr int H_BS = UAM_K2H_BS;
-// EX (UAM_OPT_EXACT_SUM): the phi and psi words added as 128-bit integer terms at the raster's
-// exponents e_phi / e_psi (x_term) into an HSlotX, the non-finite ones as side flags
-template <int CH, bool TE, bool EX = false>  // TE: the terrain in the entry (UAM_OPT_K2H_TERRAIN 1)
-__device__ __forceinline__ void h_item(const KParams& p, const KRaster& rs, const KGrp& kg,
-                                       const uint32_t* __restrict__ s_hdr,
-                                       const double2* __restrict__ s_u, bool live, int32_t item,
-                                       int32_t path, int32_t q, const double4& pr,
-                                       float seed, int32_t e_phi = 0, int32_t e_psi = 0) {
-    // a lane past the last item evaluates nothing and writes nothing
-    const int s = item - path * kg.nseg;
-    const int32_t d = path - q * kg.D;
-    const int N = p.N, W = kg.W;
-    // waypoint j's unit vector is urow[j] (j = 1..N); the slots past a row's ends read the
-    // neighbouring rows or the staged padding (LDS either way), and their cells are replaced
-    const double2* urow = s_u + d * N - 1;
-    const int j0 = s * kg.G, j1 = live ? min(j0 + kg.G, W) : j0;
-    // chunks: the wave's most, so the loop is wave-uniform
-    int nch = (j1 - j0 + CH - 1) / CH;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nch = max(nch, __shfl_xor(nch, o));
-    const double vx = pr.x - pr.z, vy = pr.y - pr.w;
-    const double cx = (pr.z + pr.x) * 0.5, cy = (pr.w + pr.y) * 0.5;
-    const double dN = (double)N, yN = kg.inv_n;
-    auto over_n = [&](double a) {  // Phi / N exactly as k_g_eval forms it (K2h: N <= 4096)
-        const double q0 = a * yN;
-        const double q1 = fma(fma(-q0, dN, a), yN, q0);
-        return __builtin_isinf(a) ? q0 : q1;
-    };
-    // the end points' cells, formed once
-    int32_t ixF, iyF, ixL, iyL;
-    const bool inF = gen_cell(rs, pr.x, pr.y, ixF, iyF);
-    const bool inL = gen_cell(rs, pr.z, pr.w, ixL, iyL);
-    const uint16_t* const bnd = reinterpret_cast<const uint16_t*>(s_hdr + rs.bnd_off);
-    const float2* const sbt = reinterpret_cast<const float2*>(s_hdr + rs.sbt_off);
-    const char* const pk = rs.pk;
-    // the plane offsets as values (a select between the struct's fields otherwise becomes a
-    // select of their addresses and a memory read per slot)
-    const uint32_t o4 = __builtin_amdgcn_readfirstlane(rs.o4);
-    const uint32_t o8 = __builtin_amdgcn_readfirstlane(rs.o8);
-    const uint32_t o16 = __builtin_amdgcn_readfirstlane(rs.o16);
-    const uint32_t ot4 = __builtin_amdgcn_readfirstlane(rs.ot4);
-    const uint32_t op8 = __builtin_amdgcn_readfirstlane(rs.op8);
-    double gc = 0.0, gn = 0.0;
-    X128 xc = {0, 0}, xn = {0, 0};  // EX: the group's phi and psi terms
-    uint32_t xf = 0;                // EX: their side flags (phi | psi << 3)
-    // EX: one word into its field's sum (straight-line: wave-uniform skips of all-zero slots
-    // and of the flags, and slots split into aligned planes, gained nothing at cfg3)
-    auto x_take = [&](X128& acc, uint32_t w, int32_t e, int fs) {
-        acc = x_add(acc, x_term(w, e));
-        xf |= x_word_flags(w) << fs;
-    };
-    float Lb = seed, E = seed;  // the path's seed: an exact terrain value of the path
-    uint32_t nh = 0, off = 0;
-    // one chunk ahead: chunk c + 1's loads are issued before chunk c is consumed (the fetch
-    // rule then sees E without chunk c's fetched values: valid, E only holds exact values).
-    // Iteration c issues chunk c + 1 into the B arrays and consumes chunk c from the A arrays.
-    uint4 rA[CH];
-    float tvA[CH];
-    uint32_t kcA[CH], vinA = 0, tkA = 0;
-    int nvA = 0;
-    // (ahead: chunk c + 1 issued before chunk c is consumed -- the same at cfg3 with 256-item
-    // workgroups, profiles/r05/k2h12)
-    constexpr bool ahead = false;
-    for (int c = ahead ? -1 : 0; c < nch; ++c) {  // (nch wave-uniform)
-        const int ci = ahead ? c + 1 : c;  // the chunk issued by this iteration
-        uint4 rB[CH];
-        float tvB[CH];
-        uint32_t kcB[CH], vinB = 0, tkB = 0;
-        int nvB = 0;
-        if (ci < nch) {
-            const int jc = j0 + ci * CH;
-            const double2* uc = urow + jc;
-            // phase 1: the cells (in-raster and in-group bits per slot)
-            int32_t ix[CH], iy[CH];
-            uint32_t vjb = 0;
-#pragma unroll
-            for (int t = 0; t < CH; ++t) {
-                const int j = jc + t;
-                const double2 u = uc[t];
-                int32_t x, y;
-                bool in = gen_cell(rs, cx + 0.5 * (vx * u.x - vy * u.y),
-                                   cy + 0.5 * (vy * u.x + vx * u.y), x, y);
-                if (t == 0) {  // (j == 0 only in a chunk's first slot)
-                    const bool f = jc == 0;
-                    x = f ? ixF : x;
-                    y = f ? iyF : y;
-                    in = f ? inF : in;
-                }
-                const bool l = j == W - 1;
-                ix[t] = l ? ixL : x;
-                iy[t] = l ? iyL : y;
-                in = l ? inL : in;
-                const bool vj = j < j1;
-                vjb |= (uint32_t)vj << t;
-                vinB |= (uint32_t)(in & vj) << t;
-            }
-            // phase 2: the header reads (cell (0, 0) for a slot off the raster: valid reads)
-            uint32_t cw[CH], be[CH];
-            float2 sb[CH];
-#pragma unroll
-            for (int t = 0; t < CH; ++t) {
-                const int32_t b = pk_block(rs, ix[t], iy[t]);
-                cw[t] = s_hdr[b >> 4] >> ((b & 15) * 2);
-                if constexpr (!TE) {
-                    const uint32_t bx = (uint32_t)(ix[t] >> rs.bshift);
-                    const uint32_t by = (uint32_t)(iy[t] >> rs.bshift);
-                    be[t] = bnd[__umul24(by, (uint32_t)rs.bnbx) + bx];
-                    sb[t] = sbt[__umul24(by >> 2, (uint32_t)rs.sbnbx) + (bx >> 2)];
-                }
-            }
-            // phase 3: the decisions and the loads
-#pragma unroll
-            for (int t = 0; t < CH; ++t) {
-                const bool vin = (vinB >> t) & 1u, vj = (vjb >> t) & 1u;
-                const uint32_t code = cw[t] & (vin ? 3u : 0u);
-                if constexpr (TE) {
-                    // code 1: the 8-B {phi, terrain} entry; 2 / 3: the 16-B record (both carry
-                    // the exact terrain); code 0: nothing to read (phi, psi +-0, terrain +0.0)
-                    const bool rec = code & 2u;
-                    const uint32_t a4 = (uint32_t)p4_addr(rs, ix[t], iy[t]);
-                    const uint32_t ab = (uint32_t)p44_addr(rs, ix[t], iy[t]) << 3;
-                    const uint32_t voff = rec ? o16 + (a4 << 4) : code ? op8 + (ab & ~15u) : o4;
-                    kcB[t] = code | (rec ? 0u : (ab & 8u));
-                    rB[t] = *reinterpret_cast<const uint4*>(pk + voff);
-                    (void)vj;
-                    continue;
-                }
-                float ub, lb;
-                pk_bound_decode(be[t], sb[t], ub, lb);
-                // off the raster or code 0: +0.0, an exact value and a lower bound; a block
-                // of one value: ub
-                const bool zero = !vin | (code == 0u);
-                Lb = fmaxf(Lb, vj ? (zero ? 0.0f : lb) : -INFINITY);
-                E = fmaxf(E, vj ? (zero ? 0.0f : lb == ub ? ub : -INFINITY) : -INFINITY);
-                const bool fetch = !zero & (code != 3u) & !(ub <= E) & !(ub < Lb);
-                const uint32_t a4 = (uint32_t)p4_addr(rs, ix[t], iy[t]);
-                // the entry's byte offset in its plane: a4 * 4 / 8 / 16 for codes 1 / 2 / 3;
-                // its aligned 16 B and the cell's word in them
-                const uint32_t ab = a4 << (code + 1u);
-                const uint32_t base = (code & 2u) ? ((code & 1u) ? o16 : o8) : o4;
-                const uint32_t voff = base + (code ? (ab & ~15u) : 0u);
-                kcB[t] = code | (ab & 12u);
-                rB[t] = *reinterpret_cast<const uint4*>(pk + voff);
-                tvB[t] = *reinterpret_cast<const float*>(pk + (ot4 + (fetch ? a4 * 4u : 0u)));
-                tkB |= (uint32_t)fetch << t;
-            }
-            nvB = max(0, min(CH, j1 - jc));  // slots past the group's end: no waypoint
-        }
-        if (!ahead) {
-#pragma unroll
-            for (int t = 0; t < CH; ++t) rA[t] = rB[t], tvA[t] = tvB[t], kcA[t] = kcB[t];
-            vinA = vinB, tkA = tkB, nvA = nvB;
-        }
-        if (c >= 0) {
-#pragma unroll
-            for (int t = 0; t < CH; ++t) {
-                const bool vl = t < nvA;
-                const bool in = (vinA >> t) & 1u;
-                if constexpr (TE) {
-                    const uint4 r = rA[t];
-                    const uint32_t code = kcA[t] & 3u;  // (0 off the raster)
-                    const bool rec = code & 2u, s1 = kcA[t] & 8u;
-                    const uint32_t lo = s1 ? r.z : r.x, hi = s1 ? r.w : r.y;
-                    const uint32_t phi = code ? (rec ? r.x : lo) : 0u;
-                    const uint32_t tb = rec ? ((r.w & UAM_FLAG_NODATA) ? 0u : r.z) : hi;
-                    nh += (rec && (r.w & UAM_FLAG_NFZ)) ? 1u : 0u;
-                    off += (vl && !in) ? 1u : 0u;
-                    if constexpr (EX) {
-                        x_take(xc, phi, e_phi, 0);
-                        x_take(xn, rec ? r.y : 0u, e_psi, 3);
-                    } else {
-                        gc = gc + over_n((double)__uint_as_float(phi));
-                        gn = gn + (rec ? (double)__uint_as_float(r.y) : 0.0);
-                    }
-                    // (off the raster, or code 0: +0.0 exactly)
-                    E = fmaxf(E, code ? __uint_as_float(tb) : vl ? 0.0f : -INFINITY);
-                    continue;
-                }
-                uint32_t phi, psi, hit;
-                float rter;
-                pk_terms_k(rA[t], kcA[t], phi, psi, hit, rter);
-                nh += hit;
-                off += (vl && !in) ? 1u : 0u;
-                if constexpr (EX) {
-                    x_take(xc, phi, e_phi, 0);
-                    x_take(xn, psi, e_psi, 3);
-                } else {
-                    gc = gc + over_n((double)__uint_as_float(phi));
-                    gn = gn + (double)__uint_as_float(psi);
-                }
-                const float ter = (kcA[t] & 3u) == 3u ? rter : ((tkA >> t) & 1u) ? tvA[t] : -INFINITY;
-                E = fmaxf(E, ter);
-            }
-        }
-        if (ahead) {
-#pragma unroll
-            for (int t = 0; t < CH; ++t) rA[t] = rB[t], tvA[t] = tvB[t], kcA[t] = kcB[t];
-            vinA = vinB, tkA = tkB, nvA = nvB;
-        }
-    }
-    if constexpr (EX) {
-        HSlotX o;
-        o.c_lo = xc.lo, o.c_hi = xc.hi;
-        o.n_lo = xn.lo, o.n_hi = xn.hi;
-        o.hmax = E;
-        o.cnt = nh | (off << 8) | (xf << 16);
-        if (live) reinterpret_cast<HSlotX*>(kg.slot)[(int64_t)s * kg.P + path] = o;
-        return;
-    }
-    HSlot o;
-    o.cost = gc;
-    o.psi = gn;
-    o.hmax = E;
-    o.cnt = nh | (off << 8);
-    if (live) reinterpret_cast<HSlot*>(kg.slot)[(int64_t)s * kg.P + path] = o;
-}
-
-// K2h evaluation: workgroups of H_BS items (xcd_chunk), the packed raster's header (codes,
-// bounds, superblocks) and the unit-arc rows (+ G + CH padding slots) staged in LDS, then one item
-// per lane (h_item)
-template <int CH, bool TE, bool EX>
-__device__ __forceinline__ void h_eval_wg(KParams p, KRaster rs, KGrp kg, int32_t e_phi,
-                                          int32_t e_psi) {
-    PK_CODES_CHECK(CH);
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
-    uint32_t* s_hdr = s_dyn;
-    // the header in LDS: codes, bounds and superblocks; the code map alone with TE
-    const int hw = TE ? rs.bnd_off : rs.hwords;
-    double2* s_u = reinterpret_cast<double2*>(s_dyn + hw);
-    // the item's order entry, pair and path bound first: their dependent round trips overlap
-    // the staging below instead of following it
-    const int64_t pos = xcd_chunk(blockIdx.x, gridDim.x) * H_BS + threadIdx.x;
-    const bool live = pos < kg.n_items;
-    const int32_t item = live ? kg.order[pos] : 0;
-    const int32_t path = (int32_t)div_magic((uint32_t)item, kg.m_nseg, kg.sh_nseg);
-    const int32_t q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d);
-    const double4 pr = reinterpret_cast<const double4*>(kg.pairs)[q];
-    const float seed = kg.lbp ? kg.lbp[path] : -INFINITY;
-    const int nu = kg.D * p.N;
-    {  // staging: every load of a thread issued before its first LDS store (hw % 4 == 0)
-        constexpr int U = 4;
-        const int nv = hw >> 2;
-        const uint4* src = reinterpret_cast<const uint4*>(rs.pmap);
-        uint4* dst = reinterpret_cast<uint4*>(s_hdr);
-        const uint4* gu = reinterpret_cast<const uint4*>(kg.utab);
-        uint4* du = reinterpret_cast<uint4*>(s_u);
-        for (int i0 = threadIdx.x; i0 < nv + nu; i0 += H_BS * U) {
-            uint4 v[U];
-#pragma unroll
-            for (int k = 0; k < U; ++k) {  // unconditional loads (past the end: the first word)
-                const int i = i0 + k * H_BS;
-                v[k] = *(i < nv ? src + i : i < nv + nu ? gu + (i - nv) : src);
-            }
-#pragma unroll
-            for (int k = 0; k < U; ++k) {  // unconditional stores (past the end: a pad slot)
-                const int i = i0 + k * H_BS;
-                *(i < nv ? dst + i : du + min(i - nv, nu)) = v[k];
-            }
-        }
-    }
-    __syncthreads();
-    // the padding: a lane's slots reach index nu + G + CH - 2 at most (a last group of one
-    // waypoint in a wave of full ones)
-    if ((int)threadIdx.x < kg.G + CH) s_u[nu + threadIdx.x] = make_double2(0.0, 0.0);
-    __syncthreads();
-    h_item<CH, TE, EX>(p, rs, kg, s_hdr, s_u, live, item, path, q, pr, seed, e_phi, e_psi);
-}
-template <int CH, bool TE>
-__global__ __launch_bounds__(H_BS, UAM_K2H_MINW) void k_h_eval(KParams p, KRaster rs, KGrp kg) {
-    h_eval_wg<CH, TE, false>(p, rs, kg, 0, 0);
-}
-// the exact form (UAM_OPT_EXACT_SUM): the raster's exponents scale = {e_phi, e_psi, ...}
-// (uam_raster_sum_scale) read once per workgroup at a uniform address
-template <int CH, bool TE>
-__global__ __launch_bounds__(H_BS, UAM_K2H_MINW) void k_h_eval_x(
-    KParams p, KRaster rs, KGrp kg, const int32_t* __restrict__ scale) {
-    const int32_t e_phi = __builtin_amdgcn_readfirstlane(scale[0]);
-    const int32_t e_psi = __builtin_amdgcn_readfirstlane(scale[1]);
-    h_eval_wg<CH, TE, true>(p, rs, kg, e_phi, e_psi);
-}
-
-// The waypoint cells (the reference's returned waypoints as raster cells, solver.py:49,
-// main.py:186-190) of the sorted forms: cells[path][j] = iy nx + ix (-1 off the raster) by the
-// evaluations' own point and cell arithmetic (gen_cell), one thread per (path, j), so
-// consecutive threads write consecutive cells -- whole lines, no gathers.  (Written by the
-// evaluation's lanes through LDS instead, the 21-cell runs of scattered items cost K2h ~120 us
-// of partial-line writes per cfg3 step: 402 MB of WRITE_SIZE for 164 MB of cells,
-// profiles/r04/final2/cells.)
-// The waypoint cells of paths [path0, path0 + np) by one workgroup of nt threads (np <= 1024):
-// each path's chord terms (cx, cy, vx, vy: arc_point's) and end-point cells go to s_cv / s_e
-// once, then work item w = (path lp = w / R, run k = w % R) forms the run's 4 cells
-// j = 4k ... 4k + 3 of one path (R = ceil(W / 4) runs a path; cells past W are not stored),
-// so a lane reads its path's terms once and selects nothing per cell; items advance by nt a
-// step (nt = lstep R + kstep, one conditional subtraction).  Every thread of the workgroup
-// calls it (it synchronises).  u_rows: the unit-arc rows (LDS when staged).
-__device__ __forceinline__ void cells_rows(const KParams& p, const KGrp& kg, int64_t path0,
-                                           int np, double4* s_cv, int4* s_e,
-                                           const double2* __restrict__ u_rows, int t, int nt) {
-    const int W = kg.W, N = p.N;
-    __syncthreads();  // (a previous block's reads of s_cv / s_e are done)
-    for (int i = t; i < np; i += nt) {
-        const int32_t path = (int32_t)(path0 + i);
-        const int32_t q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d);
-        const double4 pr = reinterpret_cast<const double4*>(kg.pairs)[q];
-        s_cv[i] = make_double4((pr.z + pr.x) * 0.5, (pr.w + pr.y) * 0.5, pr.x - pr.z,
-                               pr.y - pr.w);
-        int32_t ix, iy;  // the end points: the pair's own coordinates
-        const int32_t c0 = gen_cell_g(kg.cx0, kg.cy_top, kg.cinv_dx, kg.cinv_dy, kg.cnx, kg.cny,
-                                      pr.x, pr.y, ix, iy) ? iy * kg.cnx + ix : -1;
-        const int32_t c1 = gen_cell_g(kg.cx0, kg.cy_top, kg.cinv_dx, kg.cinv_dy, kg.cnx, kg.cny,
-                                      pr.z, pr.w, ix, iy) ? iy * kg.cnx + ix : -1;
-        s_e[i] = make_int4((path - q * kg.D) * N, c0, c1, 0);
-    }
-    __syncthreads();
-    int32_t* out = kg.cells + path0 * W;
-    const int R = (W + 3) >> 2, items = np * R;
-    int lp = t / R, k = t - lp * R;
-    const int lstep = nt / R, kstep = nt - lstep * R;
-    for (int w = t; w < items; w += nt) {
-        const double4 cv = s_cv[lp];
-        const int4 e = s_e[lp];
-        const int j0 = 4 * k;
-        int32_t v[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int jj = j0 + c;
-            const double2 u = u_rows[e.x + min(max(jj - 1, 0), N - 1)];
-            const double x0 = cv.x + 0.5 * (cv.z * u.x - cv.w * u.y);  // arc_point's ops
-            const double x1 = cv.y + 0.5 * (cv.w * u.x + cv.z * u.y);
-            int32_t ix, iy;
-            const bool in = gen_cell_g(kg.cx0, kg.cy_top, kg.cinv_dx, kg.cinv_dy, kg.cnx, kg.cny,
-                                       x0, x1, ix, iy);
-            v[c] = jj == 0 ? e.y : jj == W - 1 ? e.z : in ? iy * kg.cnx + ix : -1;
-        }
-        // streaming stores: the 164 MB of cfg3's cells do not stay in L2 / the Infinity Cache
-        // as dirty lines whose write-back the next step's gathers would meet (plain stores:
-        // cfg3 with cells 0.399 against 0.374 ms, profiles/r05/cc6); a wave's runs cover ~3
-        // paths' contiguous rows
-        int32_t* o = out + (int64_t)lp * W + j0;
-        if (j0 + 3 < W && !(((uintptr_t)o) & 7)) {
-            typedef int32_t v2i __attribute__((ext_vector_type(2)));
-            const v2i w0 = {v[0], v[1]}, w1 = {v[2], v[3]};
-            __builtin_nontemporal_store(w0, reinterpret_cast<v2i*>(o));
-            __builtin_nontemporal_store(w1, reinterpret_cast<v2i*>(o) + 1);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (j0 + c < W) o[c] = v[c];
-        }
-        lp += lstep, k += kstep;
-        if (k >= R) k -= R, ++lp;
-    }
-}
-
-// The waypoint cells (the reference's returned waypoints as raster cells, solver.py:49,
-// main.py:186-190) of the sorted forms that do not write them in their output launch (K2g):
-// cells[path][j] = iy nx + ix (-1 off the raster) by the evaluations' own point and cell
-// arithmetic, workgroups of 64 consecutive paths (cells_rows) looping over the path blocks.
-// (Written by the evaluation's lanes through LDS instead, the 21-cell runs of scattered items
-// cost K2h ~120 us of partial-line writes per cfg3 step: 402 MB of WRITE_SIZE for 164 MB of
-// cells, profiles/r04/final2/cells.)
-template <bool ULDS>  // the unit-arc rows staged in LDS (D N <= 1024) or read from global
-__global__ __launch_bounds__(256) void k_cells(KParams p, KGrp kg) {
-    constexpr int kUtabLds = 1024;  // (16 KiB)
-    __shared__ double4 s_cv[64];
-    __shared__ int4 s_e[64];
-    __shared__ double2 s_u[ULDS ? kUtabLds : 1];
-    const int t = threadIdx.x;
-    const double2* __restrict__ gu = reinterpret_cast<const double2*>(kg.utab);
-    if (ULDS)
-        for (int k = t; k < kg.D * p.N; k += 256) s_u[k] = gu[k];
-    const int64_t nblk = ((int64_t)kg.P + 63) / 64;
-    // (a grid smaller than nblk loops over the blocks: the side-stream launch's share of CUs)
-    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-        const int64_t path0 = blk * 64;
-        const int np = (int)min((int64_t)64, (int64_t)kg.P - path0);
-        cells_rows(p, kg, path0, np, s_cv, s_e, ULDS ? s_u : gu, t, 256);
-    }
-}
-
-// outputs of every path (block = 64 pairs x D, k_g_final's layout): the geometry terms from
-// the pair's scale and the displacement's unit sums (oracle sim_geo), cost = (N+1) L + the
-// Phi / N partials in group order, and the main.py:175-180 selection
-// EX (UAM_OPT_EXACT_SUM): a path's HSlotX sums added as integers and their flags ORed, each
-// field rounded once (x_result), cost = (N+1) L + fl(S_phi) / N, nfz_sum = fl(S_psi)
-template <int NR, bool EX>  // slots per path held in registers (0: a loop for long paths)
-__device__ __forceinline__ void h_final_wg(KParams p, KGrp kg, KOut out,
-                                           int32_t* __restrict__ best_f,
-                                           int32_t* __restrict__ best_l, int32_t e_phi,
-                                           int32_t e_psi) {
-    using Slot = std::conditional_t<EX, HSlotX, HSlot>;
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int D = kg.D, t = threadIdx.x;
-    double* s_cost = smem;
-    double* s_len = smem + 64 * D;
-    const int64_t q0 = (int64_t)blockIdx.x * 64;
-    const int qi = t / D, di = t - qi * D;
-    const bool bad = *kg.err != 0;  // an inconsistent sort (k_g_scatter / k_v_hist)
-    const Slot* slot = reinterpret_cast<const Slot*>(kg.slot);
-    if (q0 + qi < kg.n_pairs) {
-        const int64_t gp = (q0 + qi) * D + di;
-        Slot g[NR > 0 ? NR : 1];
-        if (NR > 0) {
-#pragma unroll
-            for (int s = 0; s < NR; ++s) g[s] = slot[(int64_t)min(s, kg.nseg - 1) * kg.P + gp];
-        }
-        const double4 pr = reinterpret_cast<const double4*>(kg.pairs)[q0 + qi];
-        const UGeo u = kg.ugeo[di];
-        // sim_geo (oracle): h = |v| / 2, h^2 = |v|^2 / 4
-        const double vx = pr.x - pr.z, vy = pr.y - pr.w;
-        const double sv = vx * vx + vy * vy;
-        const double h = sqrt(sv) * 0.5, h2 = sv * 0.25;
-        const bool ls = p.length_smooth != 0;
-        double L;
-        if (p.quirk_length) {
-            const double ax = p.anchor_mode ? p.anchor_x : pr.x;
-            const double ay = p.anchor_mode ? p.anchor_y : pr.y;
-            const double dx = pr.x - ax, dy = pr.y - ay;
-            const double n = sqrt(dx * dx + dy * dy);
-            L = (ls ? n * n : n) + (ls ? h2 * u.s2n : h * u.s1n);
-        } else {
-            L = ls ? h2 * u.s2a : h * u.s1a;
-        }
-        const double len = h * u.s1a;
-        const double ksum = (h > 0.0 && h < INFINITY) ? h * u.e12 + u.e3 : 0.0;
-        double nsum = 0.0, hmax = -INFINITY;
-        int32_t nh = 0, off = 0;
-        double cost = (double)(p.N + 1) * L;
-        X128 xc = {0, 0}, xn = {0, 0};
-        uint32_t xf = 0;
-        auto take = [&](const Slot& gs) {
-            if constexpr (EX) {
-                xc = x_add(xc, X128{gs.c_lo, gs.c_hi});
-                xn = x_add(xn, X128{gs.n_lo, gs.n_hi});
-                xf |= gs.cnt >> 16;
-            } else {
-                cost = cost + gs.cost;
-                nsum = nsum + gs.psi;
-            }
-            hmax = fmax(hmax, (double)gs.hmax);
-            nh += (int32_t)(gs.cnt & 255u);
-            off += (int32_t)((gs.cnt >> 8) & 255u);
-        };
-        if (NR > 0) {
-#pragma unroll
-            for (int s = 0; s < NR; ++s) {
-                if (s >= kg.nseg) break;
-                take(g[s]);
-            }
-        } else {
-            for (int s = 0; s < kg.nseg; ++s) {
-                const Slot gs = slot[(int64_t)s * kg.P + gp];
-                take(gs);
-            }
-        }
-        if constexpr (EX) {  // one rounding per field, a true division
-            cost = cost + x_result(xc, xf & 7u, e_phi) / (double)p.N;
-            nsum = x_result(xn, (xf >> 3) & 7u, e_psi);
-        }
-        put_outputs(out, gp, bad, cost, L, len, ksum, nsum, p.altitude - hmax, nh, off, 0);
-        s_cost[di * 64 + qi] = cost;
-        s_len[di * 64 + qi] = len;
-    }
-    __syncthreads();
-    put_selection(kg, bad, q0, t, s_cost, s_len, best_f, best_l);
-}
-template <int NR>
-__global__ __launch_bounds__(1024) void k_h_final(KParams p, KGrp kg, KOut out,
-                                                  int32_t* __restrict__ best_f,
-                                                  int32_t* __restrict__ best_l) {
-    h_final_wg<NR, false>(p, kg, out, best_f, best_l, 0, 0);
-}
-template <int NR>
-__global__ __launch_bounds__(1024) void k_h_final_x(KParams p, KGrp kg, KOut out,
-                                                    int32_t* __restrict__ best_f,
-                                                    int32_t* __restrict__ best_l,
-                                                    const int32_t* __restrict__ scale) {
-    const int32_t e_phi = __builtin_amdgcn_readfirstlane(scale[0]);
-    const int32_t e_psi = __builtin_amdgcn_readfirstlane(scale[1]);
-    h_final_wg<NR, true>(p, kg, out, best_f, best_l, e_phi, e_psi);
-}
-
-// uam_raster_sum_scale: scale = {e_phi, e_psi, flags, 0} of a record raster, flags = the phi
-// words' side flags | the psi words' << 3.  Integer maxima and ORs only, so the words do not
-// depend on the reduction's order: k_sum_scale_init writes the neutral words, then every wave
-// of k_sum_scale folds its cells (a grid-stride loop) and issues one atomic per word.
-// V: the cell -- a raster's 16-B record {phi, psi_nfz, ...} (uint4) or a volume's 8-B voxel
-// {risk, psi_nfz} (uint2, uam_volume_sum_scale); the two fields are its first two words.
-__global__ void k_sum_scale_init(int32_t* __restrict__ scale) {
-    if (threadIdx.x < 4) scale[threadIdx.x] = threadIdx.x < 2 ? X_E_MIN : 0;
-}
-template <typename V>
-__global__ __launch_bounds__(256) void k_sum_scale(const V* __restrict__ rec, int64_t cells,
-                                                   int32_t* __restrict__ scale) {
-    int32_t ec = X_E_MIN, en = X_E_MIN;
-    uint32_t fl = 0;
-    // 64 B of loads in flight per lane (past the end: the last cell again)
-    constexpr int U = 64 / (int)sizeof(V);
-    const int64_t step = (int64_t)gridDim.x * 256;
-    for (int64_t c0 = (int64_t)blockIdx.x * 256 + threadIdx.x; c0 < cells; c0 += step * U) {
-        V r[U];
-#pragma unroll
-        for (int k = 0; k < U; ++k) r[k] = rec[min(c0 + k * step, cells - 1)];
-#pragma unroll
-        for (int k = 0; k < U; ++k) {
-            ec = max(ec, x_word_exp(r[k].x));
-            en = max(en, x_word_exp(r[k].y));
-            fl |= x_word_flags(r[k].x) | (x_word_flags(r[k].y) << 3);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ec = max(ec, __shfl_xor(ec, o));
-        en = max(en, __shfl_xor(en, o));
-        fl |= (uint32_t)__shfl_xor((int32_t)fl, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (ec > X_E_MIN) atomicMax(scale + 0, ec);
-        if (en > X_E_MIN) atomicMax(scale + 1, en);
-        if (fl) atomicOr(scale + 2, (int32_t)fl);
-    }
-}
-
-// ---- K4h: the volume (config 5) in K2h's form -------------------------------------------------
-// The packed volume (uam_volume_pack; layout: VpkDims).  Planes in K2h's 4 x 8-column blocks,
-// one per layer (layer-major), all at one index i4: r4 {risk}, e8 {risk, |psi| | nfz << 31} and
-// v16, the whole voxel {risk, psi_nfz, terrain, flags} (the column's terrain and flags beside
-// the layer's pair); t4 the column terrain (one layer, the same column index).  A header
-// (staged in LDS) holds a 2-bit code per 8 x 8-column block -- 0: every voxel of its columns has
-// risk == +-0, psi == +-0 and no no-fly flag (nothing to read but the terrain); 1: psi == +-0 and
-// no flag (r4); 2: no psi below zero (e8); 3: v16 -- then the column terrain's bounds (the
-// raster's scheme: u16 codes per bound block of columns, float2 {base, step} per 4 x 4 bound
-// blocks).  The (path, group) items are sorted on the altitude band and the Hilbert tile of the
-// middle waypoint (band-major, so the items an XCD runs together share a band's lines),
-// evaluated with K2h's grouped partial sums, and the output launch adds the similarity-form
-// geometry.  Definition: oracle orc_eval_generated_h, mode 2.
-
-struct alignas(16) VSlot {  // 32 B per (path, group)
-    double cost;   // risk / N of the group's waypoints, from +0.0 in waypoint order
-    double psi;    // psi_nfz likewise
-    double cm;     // min over the group's waypoints of z_j - terrain (+inf: none)
-    uint32_t cnt;  // nfz hits | off-volume << 8 | below-terrain << 16
-    uint32_t pad;
-};
-
-struct alignas(16) VSlotX {  // the exact form's slot (UAM_OPT_EXACT_SUM_VOLUME): 48 B
-    uint64_t c_lo, c_hi;  // the sum of the group's risk terms
-    uint64_t n_lo, n_hi;  // the sum of its psi terms
-    double cm;            // as VSlot's
-    uint32_t cnt;         // as VSlot's | risk flags << 24 | psi flags << 27
-    uint32_t pad;
-};
-
-struct KVol4 {
-    int32_t nx, ny, nz;
-    double x0, y_top, z0, dz, inv_dx, inv_dy, inv_dz;
-    int32_t zshift, nbands;
-    const uint32_t* __restrict__ hdr;   // codes | bounds | superblocks
-    int32_t hwords, cnbx, bnd_off, sbt_off, bshift, bnbx, sbnbx;
-    int32_t nb8, lnby4;
-    uint32_t layer;                     // i4 entries per layer (lnby4 nb8 32)
-    // the planes from the packed base by 32-bit byte offsets (o4: r4, o8: e8, o16: v16, ot4:
-    // t4); null when the copy is 4 GiB or larger or a layer holds 2^24 entries (K4h stands aside)
-    const char* __restrict__ pk;
-    uint32_t o4, o8, o16, ot4;
-    // the terrain-in-entry form's plane q8 {risk, column terrain} in 4 x 4-column blocks per
-    // layer (nb4 blocks a row, layer44 entries a layer) at byte offset oq8
-    uint32_t oq8, layer44;
-    int32_t nb4;
-    // v16 in 4 x 2-column blocks per layer (8 entries, one 128-B line): nbx4 blocks a row,
-    // layer42 entries a layer
-    uint32_t layer42;
-    int32_t nbx4;
-    // the exact form's scale words {e_risk, e_psi, flags, 0} (uam_volume_sum_scale; read by the
-    // EX kernels only, null otherwise)
-    const int32_t* __restrict__ xscale;
-};
-
-constexpr int VPK_CSHIFT = 3;           // code blocks of 8 x 8 columns
-constexpr int VPK_HDR_LDS = 64 * 1024;  // the header in LDS up to this
-
-// the column (ix, iy)'s index in the 4 x 8-column blocks (t4; i4 = it + iz layer)
-__device__ __forceinline__ uint32_t vt4_index(const KVol4& v, int32_t ix, int32_t iy) {
-    return ((__umul24((uint32_t)(iy >> 2), (uint32_t)v.nb8) + (uint32_t)(ix >> 3)) << 5) |
-           (((uint32_t)iy & 3u) << 3) | ((uint32_t)ix & 7u);
-}
-
-// v16's in-layer index of column (ix, iy): 4 x 2-column blocks (8 entries of 16 B, one line)
-__device__ __forceinline__ uint32_t vv16_index(const KVol4& v, int32_t ix, int32_t iy) {
-    return ((__umul24((uint32_t)(iy >> 1), (uint32_t)v.nbx4) + (uint32_t)(ix >> 2)) << 3) |
-           (((uint32_t)iy & 1u) << 2) | ((uint32_t)ix & 3u);
-}
-
-// q8's in-layer index of column (ix, iy): 4 x 4-column blocks (16 entries of 8 B, one line)
-__device__ __forceinline__ uint32_t vq8_index(const KVol4& v, int32_t ix, int32_t iy) {
-    return ((__umul24((uint32_t)(iy >> 2), (uint32_t)v.nb4) + (uint32_t)(ix >> 2)) << 4) |
-           (((uint32_t)iy & 3u) << 2) | ((uint32_t)ix & 3u);
-}
-
-// the layer planes r4, e8, v16 and q8: one thread per i4 entry (r4 / e8 at i4, v16 and q8 at
-// their own block indices), which writes all four (padding: zero)
-__global__ __launch_bounds__(256) void k_volume_pack_planes(const uint2* __restrict__ vox,
-                                                            const uint2* __restrict__ col,
-                                                            KVol4 v, uint32_t* __restrict__ r4,
-                                                            uint2* __restrict__ e8,
-                                                            uint4* __restrict__ v16,
-                                                            uint2* __restrict__ q8) {
-    const int64_t total = (int64_t)v.nz * v.layer;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t w = (int32_t)(i & 31);
-        const int64_t blk = i >> 5;
-        const int32_t bx = (int32_t)(blk % v.nb8);
-        const int64_t r = blk / v.nb8;
-        const int32_t by = (int32_t)(r % v.lnby4), iz = (int32_t)(r / v.lnby4);
-        const int32_t ix = bx * 8 + (w & 7), iy = by * 4 + (w >> 3);
-        uint2 a = make_uint2(0u, 0u), cl = make_uint2(0u, 0u);
-        if (ix < v.nx && iy < v.ny) {
-            const int64_t c = (int64_t)iy * v.nx + ix;
-            a = vox[c * v.nz + iz];
-            cl = col[c];
-        }
-        r4[i] = a.x;
-        e8[i] = make_uint2(a.x, (a.y & 0x7fffffffu) | ((cl.y & UAM_FLAG_NFZ) ? 0x80000000u : 0u));
-        if (ix < v.nbx4 * 4 && iy < ((v.ny + 1) >> 1) * 2)  // (v16's padded extent)
-            v16[(int64_t)iz * v.layer42 + vv16_index(v, ix, iy)] = make_uint4(a.x, a.y, cl.x, cl.y);
-        if (ix < v.nb4 * 4 && iy < v.lnby4 * 4)  // (q8 is narrower: nb4 4-column blocks)
-            q8[(int64_t)iz * v.layer44 + vq8_index(v, ix, iy)] = make_uint2(a.x, cl.x);
-    }
-}
-
-// the column terrain plane (one thread per entry; padding: zero)
-__global__ __launch_bounds__(256) void k_volume_pack_t4(const uint2* __restrict__ col, KVol4 v,
-                                                        float* __restrict__ t4) {
-    const int64_t total = (int64_t)v.lnby4 * v.nb8 * 32;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int32_t w = (int32_t)(i & 31);
-    const int64_t blk = i >> 5;
-    const int32_t bx = (int32_t)(blk % v.nb8), by = (int32_t)(blk / v.nb8);
-    const int32_t ix = bx * 8 + (w & 7), iy = by * 4 + (w >> 3);
-    t4[i] = (ix < v.nx && iy < v.ny) ? __uint_as_float(col[(int64_t)iy * v.nx + ix].x) : 0.0f;
-}
-
-// the code map: one thread per 32-bit word (16 blocks of 8 x 8 columns)
-__global__ __launch_bounds__(256) void k_volume_codes(const uint2* __restrict__ vox,
-                                                      const uint2* __restrict__ col, int nx,
-                                                      int ny, int nz, int cnbx, int nblocks,
-                                                      int cwords, uint32_t* __restrict__ cmap) {
-    const int wd = blockIdx.x * blockDim.x + threadIdx.x;
-    if (wd >= cwords) return;
-    uint32_t word = 0;
-    for (int k = 0; k < 16; ++k) {
-        const int b = wd * 16 + k;
-        if (b >= nblocks) break;
-        const int by = b / cnbx, bx = b - by * cnbx;
-        bool need = false, neg = false, nz_r = false;
-        for (int y = by << VPK_CSHIFT; y < min(ny, (by + 1) << VPK_CSHIFT); ++y)
-            for (int x = bx << VPK_CSHIFT; x < min(nx, (bx + 1) << VPK_CSHIFT); ++x) {
-                const int64_t c = (int64_t)y * nx + x;
-                if (col[c].y & UAM_FLAG_NFZ) need = true;
-                for (int iz = 0; iz < nz; ++iz) {  // every layer's own psi and risk
-                    const uint2 a = vox[c * nz + iz];
-                    if (a.y & 0x7fffffffu) need = true;
-                    if ((a.y >> 31) && a.y != 0x80000000u) neg = true;
-                    if (a.x & 0x7fffffffu) nz_r = true;
-                }
-            }
-        const uint32_t code = need ? (neg ? 3u : 2u) : nz_r ? 1u : 0u;
-        word |= code << (2 * k);
-    }
-    cmap[wd] = word;
-}
-
-// the altitude of waypoint j (uam_eval_generated3d: z0 + (zf - z0) (j / (N+1)))
-__device__ __forceinline__ double vz_at(double za, double zb, double jw) {
-    return za + (zb - za) * jw;
-}
-
-// the voxel of a generated point (false outside the volume or NaN, with (0, 0, 0) then: valid
-// header and plane indices)
-__device__ __forceinline__ bool vol_voxel(const KVol4& vs, double x0, double x1, double z,
-                                          int32_t& ix, int32_t& iy, int32_t& iz) {
-    const double tx = (x0 - vs.x0) * vs.inv_dx, ty = (vs.y_top - x1) * vs.inv_dy;
-    const double tz = (z - vs.z0) * vs.inv_dz;
-    const bool in = (tx >= 0.0) & (tx < (double)vs.nx) & (ty >= 0.0) & (ty < (double)vs.ny) &
-                    (tz >= 0.0) & (tz < (double)vs.nz);
-    ix = in ? (int32_t)tx : 0;
-    iy = in ? (int32_t)ty : 0;
-    iz = in ? (int32_t)tz : 0;
-    return in;
-}
-
-// K4h: a path's clearance seed (k_v_eval's E and Ub): the exact clearance z - T (T the column's
-// terrain, t4) of the in-volume sampled waypoint with the smallest z - lb, over j = 0, s, 2s,
-// ... (s = kg.lb_stride) and j = W - 1, at their own voxels and altitudes by the evaluation's
-// operations (+inf: none).  It is an exact clearance of the path, so at least the path's
-// minimum M.  hdr / u: the packed header and the unit-arc table (LDS copies when staged).
-__device__ __forceinline__ double v_path_seed(const KParams& p, const KVol4& vs, const KGrp& kg,
-                                             int32_t path, const uint32_t* __restrict__ hdr,
-                                             const double2* __restrict__ utab) {
-    const int32_t q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d), d = path - q * kg.D;
-    const double* pr = kg.pairs + (int64_t)q * 6;
-    const double ax = pr[0], ay = pr[1], za = pr[2], bx = pr[3], by = pr[4], zb = pr[5];
-    const double2* u = utab + d * p.N - 1;
-    const int W = kg.W;
-    constexpr uint32_t NONE = 0xffffffffu;
-    double Ub = INFINITY, zbest = 0.0;
-    uint32_t best = NONE;  // the t4 index of the sample holding Ub
-    auto take = [&](double x0, double x1, double z) {
-        int32_t ix, iy, iz;
-        const bool in = vol_voxel(vs, x0, x1, z, ix, iy, iz);
-        const uint32_t bx2 = (uint32_t)(ix >> vs.bshift), by2 = (uint32_t)(iy >> vs.bshift);
-        const uint32_t e = reinterpret_cast<const uint16_t*>(hdr + vs.bnd_off)[by2 * vs.bnbx + bx2];
-        const float2 sb =
-            reinterpret_cast<const float2*>(hdr + vs.sbt_off)[(by2 >> 2) * vs.sbnbx + (bx2 >> 2)];
-        float ub, lb;
-        pk_bound_decode(e, sb, ub, lb);
-        const double v = z - (double)lb;
-        const bool dn = in && v < Ub;  // (a NaN bound: no)
-        Ub = dn ? v : Ub;
-        zbest = dn ? z : zbest;
-        best = dn ? vt4_index(vs, ix, iy) : best;
-    };
-    take(ax, ay, vz_at(za, zb, 0.0 / (double)(W - 1)));
-    take(bx, by, vz_at(za, zb, (double)(W - 1) / (double)(W - 1)));
-    // four samples at a time, every load of the four issued together (a sample past the last
-    // interior waypoint repeats it)
-    constexpr int K = 4;
-    for (int j0 = kg.lb_stride; j0 < W - 1; j0 += K * kg.lb_stride) {
-        double2 uu[K];
-        int jj[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            jj[k] = min(j0 + k * kg.lb_stride, W - 2);
-            uu[k] = u[jj[k]];
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double x0, x1;
-            arc_point(ax, ay, bx, by, uu[k].x, uu[k].y, x0, x1);
-            take(x0, x1, vz_at(za, zb, (double)jj[k] / (double)(W - 1)));
-        }
-    }
-    return best == NONE ? INFINITY
-                        : zbest - (double)reinterpret_cast<const float*>(vs.pk + vs.ot4)[best];
-}
-
-// sort, launch 1 (K4h): keys on (altitude band, tile) of each item's middle waypoint
-__global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
-    __shared__ __attribute__((aligned(16))) int32_t h[G_BINS_MAX];
-    __shared__ uint16_t tk[1 << (2 * G_TBITS_MAX)];
-    // with kg.seed_lds: the packed header and the unit-arc table staged for the seeds
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_vhist_dyn[];
-    const int t = threadIdx.x, b = blockIdx.x;
-    if (b == 0 && t == 0) *kg.err = 0;
-    for (int k = t; k < kg.bins; k += 1024) h[k] = 0;
-    for (int k = t; k < (1 << (2 * kg.tbits)); k += 1024) tk[k] = kg.tkey[k];
-    const uint32_t* s_hdr = vs.hdr;
-    const double2* s_ut = reinterpret_cast<const double2*>(kg.utab);
-    if (kg.ubp && kg.seed_lds) {
-        uint4* dh = reinterpret_cast<uint4*>(s_vhist_dyn);
-        const uint4* gh = reinterpret_cast<const uint4*>(vs.hdr);
-        for (int k = t; k < (vs.hwords >> 2); k += 1024) dh[k] = gh[k];
-        double2* du = reinterpret_cast<double2*>(s_vhist_dyn + vs.hwords);
-        for (int k = t; k < kg.D * p.N; k += 1024) du[k] = s_ut[k];
-        s_hdr = s_vhist_dyn;
-        s_ut = du;
-    }
-    __syncthreads();
-    const int64_t lo = ((int64_t)kg.P * b / G_NBK) * kg.nseg;
-    const int64_t hi = ((int64_t)kg.P * (b + 1) / G_NBK) * kg.nseg;
-    const int N = p.N, W = kg.W;
-    const int tiles = 1 << (2 * kg.tbits);
-    const double inv_w1 = 1.0 / (double)(W - 1);
-    // U items per thread with all their loads issued first (k_g_hist's batching)
-    constexpr int U = 4;
-    for (int64_t i0 = lo + t; i0 < hi; i0 += 1024 * U) {
-        double pr[U][6];
-        double2 u[U];
-        int jm[U], sg[U];
-#pragma unroll
-        for (int k = 0; k < U; ++k) {
-            const int32_t i = (int32_t)min(i0 + k * 1024, hi - 1);
-            const int32_t path = (int32_t)div_magic((uint32_t)i, kg.m_nseg, kg.sh_nseg);
-            sg[k] = (int)(i - (int64_t)path * kg.nseg);
-            const int32_t q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d);
-            const int32_t d = path - q * kg.D;
-            const int j0 = sg[k] * kg.G, j1 = min(j0 + kg.G, W);
-            jm[k] = (j0 + j1 - 1) >> 1;
-            const double2* pp = reinterpret_cast<const double2*>(kg.pairs + (int64_t)q * 6);
-            const double2 a = pp[0], b2 = pp[1], c = pp[2];
-            pr[k][0] = a.x, pr[k][1] = a.y, pr[k][2] = b2.x, pr[k][3] = b2.y, pr[k][4] = c.x,
-            pr[k][5] = c.y;
-            u[k] = reinterpret_cast<const double2*>(kg.utab)[d * N + min(max(jm[k] - 1, 0), N - 1)];
-        }
-#pragma unroll
-        for (int k = 0; k < U; ++k) {
-            const int64_t i = i0 + k * 1024;
-            if (i >= hi) break;
-            double x0, x1;
-            if (jm[k] == 0) {
-                x0 = pr[k][0], x1 = pr[k][1];
-            } else if (jm[k] == W - 1) {
-                x0 = pr[k][3], x1 = pr[k][4];
-            } else {
-                arc_point(pr[k][0], pr[k][1], pr[k][3], pr[k][4], u[k].x, u[k].y, x0, x1);
-            }
-            // (the key only orders the items: j / (W-1) by a reciprocal is exact enough)
-            const double z = vz_at(pr[k][2], pr[k][5], (double)jm[k] * inv_w1);
-            const double tx = (x0 - vs.x0) * vs.inv_dx, ty = (vs.y_top - x1) * vs.inv_dy;
-            const double tz = (z - vs.z0) * vs.inv_dz;
-            uint32_t key = kg.bins - 1;
-            if ((tx >= 0.0) && (tx < (double)vs.nx) && (ty >= 0.0) && (ty < (double)vs.ny) &&
-                (tz >= 0.0) && (tz < (double)vs.nz)) {
-                const uint32_t cx = (uint32_t)tx >> kg.tshift, cy = (uint32_t)ty >> kg.tshift;
-                key = ((uint32_t)tz >> vs.zshift) * tiles + tk[(cy << kg.tbits) | cx];
-                // (kg.last_bin is 0, one bin per tile and band, as K2h's: k_v_eval masks the
-                // slots past a lane's group and pads s_u / s_jw by G + 16 slots)
-                if (sg[k] == kg.nseg - 1) key += kg.last_bin;
-            }
-            kg.key[i] = (uint16_t)key;
-            atomicAdd(&h[key], 1);
-        }
-    }
-    if (kg.ubp) {  // the partition's paths' clearance seeds, one thread per path
-        const int64_t plo = (int64_t)kg.P * b / G_NBK, phi = (int64_t)kg.P * (b + 1) / G_NBK;
-        for (int64_t pth = plo + t; pth < phi; pth += 1024)
-            kg.ubp[pth] = v_path_seed(p, vs, kg, (int32_t)pth, s_hdr, s_ut);
-    }
-    __syncthreads();
-    for (int k = t; k < kg.bins; k += 1024) kg.cnt[(int64_t)k * G_NBK + b] = h[k];
-}
-
-// every (path, group) item in sorted order (h_item's phases): the CH waypoints' voxels (x, y by
-// the arc formula or the pair's end points, z on the linear climb), the header reads, then per
-// slot the decisions and two unconditional loads -- the code's entry (r4 / e8 / v16, the dummy
-// line in code 0 or outside the volume) and the terrain (the first t4 word unless fetched) -- by
-// 32-bit offsets from the packed base; then the branch-free consume.
-//
-// The terrain by bounds (as K2h's; the outputs are exactly the per-waypoint ones).  Waypoint j
-// in the volume has lb_j <= T_j <= ub_j (the column grid's bounds) and
-//   below_j = zc_j < T_j (zc_j its layer centre): decided when zc_j < lb_j (1) or zc_j >= ub_j
-//       (0), else its terrain is fetched;
-//   c_j = z_j - T_j, whose path minimum is min_clearance: z_j - ub_j <= c_j <= z_j - lb_j (the
-//       float64 subtraction is monotone).  The item keeps Ub, an upper bound of the path minimum
-//       M (the path's seed, then its own waypoints' z - lb), and E, the minimum of exact c_j of
-//       the path: the seed (v_path_seed: the exact clearance of the sampled waypoint with the
-//       smallest z - lb, formed once per path by the histogram launch) and those it takes
-//       (fetched, v16's, one-value blocks); it fetches w iff it is undecided or
-//       !(z_w - ub_w >= E) && !(z_w - ub_w > Ub).  If w* holds M and is not taken: z - ub >= E
-//       gives M >= E >= M, and z - ub > Ub >= M is impossible.  NaN bounds (no bound) always
-//       fetch.
-// EX (UAM_OPT_EXACT_SUM_VOLUME; k_v_eval_x below): the risk and psi words added as 128-bit
-// integer terms at the volume's exponents e_risk / e_psi (x_term) into a VSlotX, the non-finite
-// ones as side flags.  One body for both forms, in the kernel itself: moved into an inlined
-// function, the EX = false instantiations no longer allocated the registers they had (DESIGN
-// §10), so the exact form is this kernel's third template flag and vs.xscale its scale.
-template <int CH, bool TE, bool EX = false>  // TE: the terrain in the entry (UAM_OPT_K4H_TERRAIN 1)
-__global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(KParams p, KVol4 vs,
-                                                                              KGrp kg) {
-    PK_CODES_CHECK(CH);
-    // unit-arc rows + padding, then j / (W-1) (+ padding), then the header
-    extern __shared__ __attribute__((aligned(16))) double2 s_u[];
-    const int N = p.N, W = kg.W;
-    const int nu = kg.D * N, npad = kg.G + 16;  // a lane's slots reach j <= W + G + CH - 3
-    double* s_jw = reinterpret_cast<double*>(s_u + nu + npad);
-    const int njw = W + npad;
-    uint32_t* s_hdr = reinterpret_cast<uint32_t*>(s_jw + ((njw + 1) & ~1));
-    // the item's order entry, pair and path bound before the staging (their round trips
-    // overlap it)
-    const int64_t pos = xcd_chunk(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
-    const bool live = pos < kg.n_items;
-    const int32_t item = live ? kg.order[pos] : 0;
-    const int32_t path = (int32_t)div_magic((uint32_t)item, kg.m_nseg, kg.sh_nseg);
-    const int s = item - path * kg.nseg;
-    const int32_t q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d), d = path - q * kg.D;
-    const double* prp = kg.pairs + (int64_t)q * 6;
-    const double2 pa = *reinterpret_cast<const double2*>(prp);
-    const double2 pb = *reinterpret_cast<const double2*>(prp + 2);
-    const double2 pc = *reinterpret_cast<const double2*>(prp + 4);
-    const double seed = kg.ubp ? kg.ubp[path] : INFINITY;  // an exact clearance of the path
-    double Ub = seed;
-    for (int i = threadIdx.x; i < nu + npad; i += 256)
-        s_u[i] = i < nu ? reinterpret_cast<const double2*>(kg.utab)[i] : make_double2(0.0, 0.0);
-    for (int j = threadIdx.x; j < njw; j += 256)
-        s_jw[j] = j < W ? (double)j / (double)(W - 1) : 0.0;
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(vs.hdr);
-        uint4* dst = reinterpret_cast<uint4*>(s_hdr);
-        const int hw = TE ? vs.bnd_off : vs.hwords;  // (TE: the code map alone)
-        for (int i = threadIdx.x; i < (hw >> 2); i += 256) dst[i] = src[i];
-    }
-    __syncthreads();
-    const double ax = pa.x, ay = pa.y, za = pb.x, bx = pb.y, by = pc.x, zb = pc.y;
-    const double2* urow = s_u + d * N - 1;  // waypoint j's unit vector: urow[j]
-    const int j0 = s * kg.G, j1 = live ? min(j0 + kg.G, W) : j0;
-    int nch = (j1 - j0 + CH - 1) / CH;  // the wave's most: a wave-uniform loop
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nch = max(nch, __shfl_xor(nch, o));
-    const double vx = ax - bx, vy = ay - by;
-    const double cx = (bx + ax) * 0.5, cy = (by + ay) * 0.5;
-    const double dN = (double)N, yN = kg.inv_n;
-    auto over_n = [&](double a) {  // (K4h: N <= 4096)
-        const double q0 = a * yN;
-        const double q1 = fma(fma(-q0, dN, a), yN, q0);
-        return __builtin_isinf(a) ? q0 : q1;
-    };
-    // the layer centre of layer iz (the below-terrain test)
-    auto zc_of = [&](int32_t iz) { return vs.z0 + ((double)iz + 0.5) * vs.dz; };
-    // the end points' voxels, formed once
-    int32_t ixF, iyF, izF, ixL, iyL, izL;
-    const double zF = vz_at(za, zb, s_jw[0]), zL = vz_at(za, zb, s_jw[W - 1]);
-    const bool inF = vol_voxel(vs, ax, ay, zF, ixF, iyF, izF);
-    const bool inL = vol_voxel(vs, bx, by, zL, ixL, iyL, izL);
-    const uint16_t* const bnd = reinterpret_cast<const uint16_t*>(s_hdr + vs.bnd_off);
-    const float2* const sbt = reinterpret_cast<const float2*>(s_hdr + vs.sbt_off);
-    const char* const pk = vs.pk;
-    const uint32_t o4 = __builtin_amdgcn_readfirstlane(vs.o4);
-    const uint32_t o8 = __builtin_amdgcn_readfirstlane(vs.o8);
-    const uint32_t o16 = __builtin_amdgcn_readfirstlane(vs.o16);
-    const uint32_t ot4 = __builtin_amdgcn_readfirstlane(vs.ot4);
-    const uint32_t layer = __builtin_amdgcn_readfirstlane(vs.layer);
-    const uint32_t oq8 = __builtin_amdgcn_readfirstlane(vs.oq8);
-    const uint32_t layer44 = __builtin_amdgcn_readfirstlane(vs.layer44);
-    const uint32_t layer42 = __builtin_amdgcn_readfirstlane(vs.layer42);
-    double gc = 0.0, gn = 0.0, E = seed;
-    uint32_t nh = 0, off = 0, bel = 0;
-    X128 xc = {0, 0}, xn = {0, 0};  // EX: the group's risk and psi terms
-    uint32_t xf = 0;                // EX: their side flags (risk | psi << 3)
-    // EX: the volume's exponents, read once per workgroup at a uniform address
-    int32_t e_risk = 0, e_psi = 0;
-    if constexpr (EX) {
-        e_risk = __builtin_amdgcn_readfirstlane(vs.xscale[0]);
-        e_psi = __builtin_amdgcn_readfirstlane(vs.xscale[1]);
-    }
-    // EX: one word into its field's sum (straight-line, as h_item's)
-    auto x_take = [&](X128& acc, uint32_t w, int32_t e, int fs) {
-        acc = x_add(acc, x_term(w, e));
-        xf |= x_word_flags(w) << fs;
-    };
-    // one chunk ahead, as h_item: iteration c issues chunk c + 1 (B arrays) and consumes chunk
-    // c (A arrays)
-    // (the slot's layer rides in its kind word's high bits; consume recomputes its altitude)
-    uint4 rA[CH];
-    float tvA[CH];
-    uint32_t kcA[CH], vinA = 0, tkA = 0, bvA = 0;
-    int nvA = 0, jcA = 0;
-    constexpr bool ahead = false;  // (h_item's)
-    for (int c = ahead ? -1 : 0; c < nch; ++c) {  // (nch wave-uniform)
-        const int ci = ahead ? c + 1 : c;  // the chunk issued by this iteration
-        uint4 rB[CH];
-        float tvB[CH];
-        uint32_t kcB[CH], vinB = 0, tkB = 0, bvB = 0;
-        int nvB = 0;
-        const int jc = j0 + ci * CH;
-        if (ci < nch) {
-            double zB[CH];
-            int32_t izB[CH];
-            const double2* uc = urow + jc;
-            // phase 1: the voxels
-            int32_t ix[CH], iy[CH];
-#pragma unroll
-            for (int t = 0; t < CH; ++t) {
-                const int j = jc + t;
-                const double2 u = uc[t];
-                const double z = vz_at(za, zb, s_jw[j]);
-                int32_t x, y, zz;
-                bool in = vol_voxel(vs, cx + 0.5 * (vx * u.x - vy * u.y),
-                                    cy + 0.5 * (vy * u.x + vx * u.y), z, x, y, zz);
-                if (t == 0) {  // (j == 0 only in a chunk's first slot)
-                    const bool f = jc == 0;
-                    x = f ? ixF : x;
-                    y = f ? iyF : y;
-                    zz = f ? izF : zz;
-                    in = f ? inF : in;
-                }
-                const bool l = j == W - 1;
-                ix[t] = l ? ixL : x;
-                iy[t] = l ? iyL : y;
-                izB[t] = l ? izL : zz;
-                in = l ? inL : in;
-                zB[t] = z;  // (the end points' z by the same formula)
-                vinB |= (uint32_t)(in & (j < j1)) << t;
-            }
-            // phase 2: the header reads (column (0, 0) outside the volume: valid reads)
-            uint32_t cw[CH], be[CH];
-            float2 sb[CH];
-#pragma unroll
-            for (int t = 0; t < CH; ++t) {
-                const uint32_t b = __umul24((uint32_t)(iy[t] >> VPK_CSHIFT), (uint32_t)vs.cnbx) +
-                                   (uint32_t)(ix[t] >> VPK_CSHIFT);
-                cw[t] = s_hdr[b >> 4] >> ((b & 15u) * 2u);
-                if constexpr (!TE) {
-                    const uint32_t bx2 = (uint32_t)(ix[t] >> vs.bshift);
-                    const uint32_t by2 = (uint32_t)(iy[t] >> vs.bshift);
-                    be[t] = bnd[__umul24(by2, (uint32_t)vs.bnbx) + bx2];
-                    sb[t] = sbt[__umul24(by2 >> 2, (uint32_t)vs.sbnbx) + (bx2 >> 2)];
-                }
-            }
-            // phase 3: the decisions and the loads
-#pragma unroll
-            for (int t = 0; t < CH; ++t) {
-                const bool vin = (vinB >> t) & 1u;
-                const uint32_t code = cw[t] & (vin ? 3u : 0u);
-                if constexpr (TE) {
-                    // codes 0 / 1: the 8-B {risk, column terrain} entry (q8); 2 / 3: v16
-                    const bool rec = code & 2u;
-                    const uint32_t iz = (uint32_t)izB[t];
-                    const uint32_t a16 = vv16_index(vs, ix[t], iy[t]) + __umul24(iz, layer42);
-                    const uint32_t ab = (vq8_index(vs, ix[t], iy[t]) + __umul24(iz, layer44)) << 3;
-                    const uint32_t voff = rec ? o16 + (a16 << 4) : oq8 + (ab & ~15u);
-                    kcB[t] = code | (rec ? 0u : (ab & 8u)) | (iz << 8);
-                    rB[t] = *reinterpret_cast<const uint4*>(pk + voff);
-                    continue;
-                }
-                float ub, lb;
-                pk_bound_decode(be[t], sb[t], ub, lb);
-                const double z = zB[t], zc = zc_of(izB[t]);
-                const bool k1 = zc < (double)lb, k0 = zc >= (double)ub;
-                // a one-value block: the exact term; every in-volume waypoint's z - lb bounds M
-                E = (vin & (lb == ub)) ? fmin(E, z - (double)ub) : E;
-                Ub = vin ? fmin(Ub, z - (double)lb) : Ub;
-                const double clo = z - (double)ub;
-                const bool fetch =
-                    vin & (code != 3u) & (!(k1 | k0) | (!(clo >= E) & !(clo > Ub)));
-                const uint32_t it = vt4_index(vs, ix[t], iy[t]);
-                const uint32_t a4 = it + __umul24((uint32_t)izB[t], layer);
-                // codes 1 / 2: the r4 / e8 entry's aligned 16 B and word; 3: v16 (its own index)
-                const uint32_t ab = a4 << (code + 1u);
-                const uint32_t a16 = vv16_index(vs, ix[t], iy[t]) + __umul24((uint32_t)izB[t], layer42);
-                const uint32_t voff = code == 3u ? o16 + (a16 << 4)
-                                                 : (code == 2u ? o8 : o4) + (code ? (ab & ~15u) : 0u);
-                kcB[t] = code | (code == 3u ? 0u : (ab & 12u)) | ((uint32_t)izB[t] << 8);
-                rB[t] = *reinterpret_cast<const uint4*>(pk + voff);
-                tvB[t] = *reinterpret_cast<const float*>(pk + (ot4 + (fetch ? it * 4u : 0u)));
-                tkB |= (uint32_t)fetch << t;
-                bvB |= (uint32_t)k1 << t;
-            }
-            nvB = max(0, min(CH, j1 - jc));  // slots past the group's end: no waypoint
-        }
-        if (!ahead) {
-#pragma unroll
-            for (int t = 0; t < CH; ++t) rA[t] = rB[t], tvA[t] = tvB[t], kcA[t] = kcB[t];
-            vinA = vinB, tkA = tkB, bvA = bvB, nvA = nvB, jcA = jc;
-        }
-        if (c >= 0) {
-#pragma unroll
-            for (int t = 0; t < CH; ++t) {
-                const bool vl = t < nvA, in = (vinA >> t) & 1u;
-                if constexpr (TE) {
-                    const uint4 r = rA[t];
-                    const bool rec = kcA[t] & 2u, s1 = kcA[t] & 8u;
-                    const uint32_t lo = s1 ? r.z : r.x, hi = s1 ? r.w : r.y;
-                    const uint32_t risk = in ? (rec ? r.x : lo) : 0u;
-                    const float ter = __uint_as_float(rec ? r.z : hi);  // (+0 on nodata)
-                    nh += (rec && (r.w & UAM_FLAG_NFZ)) ? 1u : 0u;
-                    off += (vl && !in) ? 1u : 0u;
-                    if constexpr (EX) {
-                        x_take(xc, risk, e_risk, 0);
-                        x_take(xn, rec ? r.y : 0u, e_psi, 3);
-                    } else {
-                        gc = gc + over_n((double)__uint_as_float(risk));
-                        gn = gn + (rec ? (double)__uint_as_float(r.y) : 0.0);
-                    }
-                    const double z = vz_at(za, zb, s_jw[jcA + t]);
-                    bel += (in && zc_of((int32_t)(kcA[t] >> 8)) < (double)ter) ? 1u : 0u;
-                    E = in ? fmin(E, z - (double)ter) : E;
-                    continue;
-                }
-                uint32_t risk, psi, hit;
-                float rter;
-                pk_terms_k(rA[t], kcA[t], risk, psi, hit, rter);
-                const bool c3 = (kcA[t] & 3u) == 3u;
-                if constexpr (EX) {
-                    x_take(xc, risk, e_risk, 0);
-                    x_take(xn, psi, e_psi, 3);
-                } else {
-                    gc = gc + over_n((double)__uint_as_float(risk));
-                    gn = gn + (double)__uint_as_float(psi);
-                }
-                nh += hit;
-                off += (vl && !in) ? 1u : 0u;
-                // the exact terrain, where taken: v16's (code 3) or the fetched one
-                const bool ex = in & (c3 | ((tkA >> t) & 1u));
-                const float ter = c3 ? rter : tvA[t];
-                const double z = vz_at(za, zb, s_jw[jcA + t]);
-                const uint32_t below =
-                    ex ? (zc_of((int32_t)(kcA[t] >> 8)) < (double)ter ? 1u : 0u) : ((bvA >> t) & 1u);
-                bel += in ? below : 0u;
-                E = ex ? fmin(E, z - (double)ter) : E;
-            }
-        }
-        if (ahead) {
-#pragma unroll
-            for (int t = 0; t < CH; ++t) rA[t] = rB[t], tvA[t] = tvB[t], kcA[t] = kcB[t];
-            vinA = vinB, tkA = tkB, bvA = bvB, nvA = nvB, jcA = jc;
-        }
-    }
-    if constexpr (EX) {
-        VSlotX o;
-        o.c_lo = xc.lo, o.c_hi = xc.hi;
-        o.n_lo = xn.lo, o.n_hi = xn.hi;
-        o.cm = E;
-        o.cnt = nh | (off << 8) | (bel << 16) | (xf << 24);
-        o.pad = 0;
-        if (live) reinterpret_cast<VSlotX*>(kg.slot)[(int64_t)s * kg.P + path] = o;
-        return;
-    }
-    VSlot o;
-    o.cost = gc;
-    o.psi = gn;
-    o.cm = E;
-    o.cnt = nh | (off << 8) | (bel << 16);
-    o.pad = 0;
-    if (live) reinterpret_cast<VSlot*>(kg.slot)[(int64_t)s * kg.P + path] = o;
-}
-// the exact form (UAM_OPT_EXACT_SUM_VOLUME), k_v_eval's sibling: the same body with EX set
-template <int CH, bool TE>
-constexpr auto k_v_eval_x = k_v_eval<CH, TE, true>;
-
-// outputs of every path (block = 64 pairs x D): the similarity-form geometry (oracle sim_geo on
-// the pair's x/y), cost = (N+1) L + the risk / N partials in group order, min clearance, the
-// counts, and the main.py:175-180 selection
-// EX (UAM_OPT_EXACT_SUM_VOLUME): a path's VSlotX sums added as integers and their flags ORed,
-// each field rounded once (x_result), cost = (N+1) L + fl(S_risk) / N, nfz_sum = fl(S_psi)
-template <bool EX>
-__device__ __forceinline__ void v_final_wg(KParams p, KGrp kg, KOut out,
-                                           int32_t* __restrict__ best_f,
-                                           int32_t* __restrict__ best_l, int32_t e_risk,
-                                           int32_t e_psi) {
-    using Slot = std::conditional_t<EX, VSlotX, VSlot>;
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int D = kg.D, t = threadIdx.x;
-    double* s_cost = smem;
-    double* s_len = smem + 64 * D;
-    const int64_t q0 = (int64_t)blockIdx.x * 64;
-    const int qi = t / D, di = t - qi * D;
-    const bool bad = *kg.err != 0;  // an inconsistent sort (k_g_scatter / k_v_hist)
-    const Slot* slot = reinterpret_cast<const Slot*>(kg.slot);
-    if (q0 + qi < kg.n_pairs) {
-        const int64_t gp = (q0 + qi) * D + di;
-        const double* pr = kg.pairs + (q0 + qi) * 6;
-        const double x0 = pr[0], y0 = pr[1], xf = pr[3], yf = pr[4];
-        const UGeo u = kg.ugeo[di];
-        const double vx = x0 - xf, vy = y0 - yf;
-        const double sv = vx * vx + vy * vy;
-        const double h = sqrt(sv) * 0.5, h2 = sv * 0.25;
-        const bool ls = p.length_smooth != 0;
-        double L;
-        if (p.quirk_length) {
-            const double axx = p.anchor_mode ? p.anchor_x : x0;
-            const double ayy = p.anchor_mode ? p.anchor_y : y0;
-            const double dx = x0 - axx, dy = y0 - ayy;
-            const double n = sqrt(dx * dx + dy * dy);
-            L = (ls ? n * n : n) + (ls ? h2 * u.s2n : h * u.s1n);
-        } else {
-            L = ls ? h2 * u.s2a : h * u.s1a;
-        }
-        const double len = h * u.s1a;
-        const double ksum = (h > 0.0 && h < INFINITY) ? h * u.e12 + u.e3 : 0.0;
-        double cost = (double)(p.N + 1) * L, nsum = 0.0, cm = INFINITY;
-        int32_t nh = 0, off = 0, bel = 0;
-        X128 xc = {0, 0}, xn = {0, 0};
-        uint32_t xfl = 0;
-        for (int s = 0; s < kg.nseg; ++s) {
-            const Slot g = slot[(int64_t)s * kg.P + gp];
-            if constexpr (EX) {
-                xc = x_add(xc, X128{g.c_lo, g.c_hi});
-                xn = x_add(xn, X128{g.n_lo, g.n_hi});
-                xfl |= g.cnt >> 24;
-            } else {
-                cost = cost + g.cost;
-                nsum = nsum + g.psi;
-            }
-            cm = fmin(cm, g.cm);
-            nh += (int32_t)(g.cnt & 255u);
-            off += (int32_t)((g.cnt >> 8) & 255u);
-            bel += (int32_t)((g.cnt >> 16) & 255u);
-        }
-        if constexpr (EX) {  // one rounding per field, a true division
-            cost = cost + x_result(xc, xfl & 7u, e_risk) / (double)p.N;
-            nsum = x_result(xn, (xfl >> 3) & 7u, e_psi);
-        }
-        put_outputs(out, gp, bad, cost, L, len, ksum, nsum, cm, nh, off, bel);
-        s_cost[di * 64 + qi] = cost;
-        s_len[di * 64 + qi] = len;
-    }
-    __syncthreads();
-    put_selection(kg, bad, q0, t, s_cost, s_len, best_f, best_l);
-}
-__global__ __launch_bounds__(1024) void k_v_final(KParams p, KGrp kg, KOut out,
-                                                  int32_t* __restrict__ best_f,
-                                                  int32_t* __restrict__ best_l) {
-    v_final_wg<false>(p, kg, out, best_f, best_l, 0, 0);
-}
-__global__ __launch_bounds__(1024) void k_v_final_x(KParams p, KGrp kg, KOut out,
-                                                    int32_t* __restrict__ best_f,
-                                                    int32_t* __restrict__ best_l,
-                                                    const int32_t* __restrict__ scale) {
-    const int32_t e_risk = __builtin_amdgcn_readfirstlane(scale[0]);
-    const int32_t e_psi = __builtin_amdgcn_readfirstlane(scale[1]);
-    v_final_wg<true>(p, kg, out, best_f, best_l, e_risk, e_psi);
-}
-
+// closes the anonymous namespace opened above the device-side tables
 }  // namespace
 
 namespace {

@@ -372,11 +372,79 @@ int uam_eval_waypoints3d(uam_ctx* ctx, const uam_volume_desc* desc, const void* 
  * unset for the length); they need the cost / length output respectively (UAM_E_INVALID
  * otherwise).  A length does not depend on the profile, so among the profiles of one
  * displacement the rule's first index wins: best_length_idx is a multiple of A unless the rule's
- * zero quirk applies (a length of exactly 0 is replaced by whatever follows it). */
+ * zero quirk applies (a length of exactly 0 is replaced by whatever follows it).  That holds for
+ * this call only: under the vertical terms (uam_eval_generated3d_profiles_v, below) a length
+ * depends on the profile, best_length_idx selects among all D*A candidates, and best_fval_idx
+ * sees the climb through (N+1) L. */
 int uam_eval_generated3d_profiles(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol_dev,
                                   const double* pairs6_dev, int64_t n_pairs,
                                   const double* utab_dev, int32_t D, const double* ztab_dev,
                                   int32_t A, const uam_path_outputs* out, uam_stream stream);
+
+/* ---- The vertical terms: 3-D length, turn and climb rows ------------------------------------
+ * The two evaluations above form length_q, length and kin_sum from x/y alone, so a climb costs
+ * nothing but the risk it flies through.  The _v calls below charge it.  uam_vertical is plain
+ * data like uam_params:
+ *   z_scale      kappa, km of path length per metre of altitude change (1e-3: isotropic);
+ *   sin_climb    the largest climb per unit of 3-D path length, +inf = no limit;
+ *   sin_descent  the same for descending.
+ * For the waypoints p_j = (x_j, y_j, z_j), j = 0 .. N+1, with ls = length_smooth, ms =
+ * maxratio_smooth, quirk = quirk_length and the anchor as in uam_params:
+ *
+ *   L = quirk ? 0 + anchor term : 0;  length = kin_sum = climb_sum = 0
+ *   for j = 1 .. N+1:
+ *     dx = x_j - x_{j-1};  dy = y_j - y_{j-1};  dz = (z_j - z_{j-1}) * kappa
+ *     s  = ((0 + dx*dx) + dy*dy) + dz*dz;   n = sqrt(s)
+ *     length += n;   if (!quirk || j <= N)  L += ls ? n*n : n
+ *     nk = ms ? n*n : n
+ *     if j >= 2:  dt = ((0 + pdx*dx) + pdy*dy) + pdz*dz;  (c1, c2, c3) = kin_row(pn, nk, dt);
+ *                 kin_sum += c1;  kin_sum += c2;  kin_sum += c3
+ *     cu = fmax(0, dz - sin_climb*n);   cd = fmax(0, (-dz) - sin_descent*n)
+ *     climb_sum = (climb_sum + cu) + cd
+ *     pdx, pdy, pdz, pn = dx, dy, dz, nk
+ *
+ * with kin_row(pn, nk, dt) = (fmax(0, nk - r*pn), fmax(0, pn/r - nk), fmax(0, mincos - dt/(pn*nk)))
+ * as in the 2-D calls (r = maxratio, squared when ms; mincos = cos(maxalpha)).  The altitude
+ * difference is taken first and scaled by one product.  The anchor term stays x/y only: the
+ * anchor flies at p_0's altitude.  length_q = L, cost = (N+1) L + sum_j risk(voxel_j) / N as
+ * before; the risk, no-fly, clearance, off-volume and below-terrain outputs do not change.
+ * Every operation is rounded to float64, none is contracted.  fmax is C's: a NaN row counts 0;
+ * only the sums are output, so the sign of a zero row cannot show.
+ * With kappa = 0 and finite altitudes every output equals the call without _v bit for bit
+ * (s + 0*0 = s, dt + 0 = dt) and climb_sum is +0. */
+typedef struct {
+    uint32_t abi_version;   /* UAM_ABI_VERSION */
+    double z_scale;         /* km of path length per metre of altitude change; >= 0, finite */
+    double sin_climb;       /* largest climb per unit of 3-D path length; >= 0, +inf = no limit */
+    double sin_descent;     /* the same for descending */
+} uam_vertical;
+
+/* uam_eval_waypoints3d with the vertical terms (uam_last_kernel "K4e+v" / "K4ew+v", same bits;
+ * uam_last_group 0).  climb_sum_dev [P] receives climb_sum (NULL: not wanted); uam_path_outputs
+ * does not grow.  Failures as uam_eval_waypoints3d, in its order, with -- after
+ * UAM_OPT_EXACT_SUM_VOLUME's refusal and before n_paths -- UAM_E_INVALID for vert == NULL,
+ * UAM_E_VERSION for a wrong abi_version, UAM_E_INVALID for a NaN, negative or infinite z_scale
+ * and for a NaN or negative sin_climb / sin_descent. */
+int uam_eval_waypoints3d_v(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol_dev,
+                           const double* wp3_dev /* [P][W][3] (x km, y km, z m) */,
+                           int64_t n_paths, const uam_vertical* vert,
+                           const uam_path_outputs* out, double* climb_sum_dev /* [P] or NULL */,
+                           uam_stream stream);
+/* uam_eval_generated3d_profiles with the vertical terms: uam_eval_waypoints3d_v applied to
+ * uam_gen_paths3d's waypoints, bit for bit, in one kernel (uam_last_kernel "K4p+v").  The A
+ * profiles of a lateral candidate still share its x/y points and each waypoint's column, but no
+ * longer the geometry terms.  Here a length does depend on the profile: best_length_idx selects
+ * among all D*A candidates and need not be a multiple of A, and best_fval_idx sees the climb
+ * through (N+1) L.  ztab_dev == NULL with A = 1 is the straight climb with the vertical terms
+ * (uam_eval_generated3d itself has no such form).  Failures as uam_eval_generated3d_profiles,
+ * with the checks of vert where uam_eval_waypoints3d_v has them. */
+int uam_eval_generated3d_profiles_v(uam_ctx* ctx, const uam_volume_desc* desc,
+                                    const void* vol_dev, const double* pairs6_dev,
+                                    int64_t n_pairs, const double* utab_dev, int32_t D,
+                                    const double* ztab_dev, int32_t A, const uam_vertical* vert,
+                                    const uam_path_outputs* out,
+                                    double* climb_sum_dev /* [Q*D*A] or NULL */,
+                                    uam_stream stream);
 
 /* The packed volume (K4h), 256-B aligned sections:
  *   header  a 2-bit code per 8 x 8 columns (0: risk, psi_nfz +-0 in every layer and no no-fly
@@ -506,7 +574,8 @@ int uam_kernel_time(uam_ctx* ctx, double* ms_total, int64_t* launches);
  * "K2s+pack" / "K2s+skip" / "K2s" (segment-sorted raster, sequential sums), "K2+skip" / "K2"
  * (lane per path), "K2w" (wave per path), "K2d" (D > 16), "K3b", "K3", "K3d", "K4", "K4w";
  * "K4e" / "K4ew" (uam_eval_waypoints3d lane / wave per path), "K4p"
- * (uam_eval_generated3d_profiles); "" before the first call.  The string is static (never freed).  For benchmarks and tests:
+ * (uam_eval_generated3d_profiles), "K4e+v" / "K4ew+v" / "K4p+v" (their _v forms with the
+ * vertical terms); "" before the first call.  The string is static (never freed).  For benchmarks and tests:
  * which kernel a number belongs to. */
 const char* uam_last_kernel(const uam_ctx* ctx);
 
@@ -523,7 +592,8 @@ const char* uam_last_kernel(const uam_ctx* ctx);
  * on all 100k cfg3 pairs (bench.py parity.vs_sequential_order) -- they can differ only where
  * two candidates of a pair are within that rounding of each other.  A caller that needs the
  * sequential bits sets UAM_OPT_GROUP = 0 (K2s / K4).  uam_eval_waypoints3d and
- * uam_eval_generated3d_profiles (K4e / K4ew / K4p) always add sequentially: they report 0. */
+ * uam_eval_generated3d_profiles (K4e / K4ew / K4p) and their _v forms always add sequentially:
+ * they report 0. */
 int32_t uam_last_group(const uam_ctx* ctx);
 
 /* Context options: which kernel form runs (results never depend on them, except for the sum

@@ -4,13 +4,16 @@ cfg5 volume (1024^2 x 64 layers, 100k pairs, D = 5) for A in {1, 2, 4, 8} lift p
 the same work without sharing: A separate eval_generated3d calls on pairs whose end altitudes
 are shifted by the lift heights, once in the K4 form (no packed copy) and once in K4h.  The
 shifted pairs fly the straight climb at another height, not the lift's ramp: the comparison is
-of the work (A x Q x D paths through the same volume), not of the bits.
+of the work (A x Q x D paths through the same volume), not of the bits.  Beside each fused
+form its form with the vertical terms (K4p+v: 3-D length, turn and climb rows per profile), and
+for A = 1 the explicit forms K4e / K4e+v on the same waypoints.
 
 Times are HIP events on the launch stream around --steps calls after --warmup, the median of
 --repeats such windows.  One JSON line per measurement; needs an MI355X.
 
     python tools/time_profiles.py                  # the table
     python tools/time_profiles.py --only-fused 8   # one fused form alone (for rocprofv3)
+    python tools/time_profiles.py --only-fused 8 --vertical    # ... with the vertical terms
 """
 import argparse
 import json
@@ -31,6 +34,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--only-fused", type=int, default=0, metavar="A",
                     help="run only the fused call with A profiles (a profiler's target)")
+    ap.add_argument("--vertical", action="store_true",
+                    help="with --only-fused: the form with the vertical terms (K4p+v)")
     ap.add_argument("--pair-order", type=int, default=1, choices=(0, 1),
                     help="the pair_order option (K4 / K4p: pairs in a spatial order)")
     args = ap.parse_args()
@@ -39,7 +44,7 @@ def main():
 
     from uam_path_planning_amd import build, profiles
     from uam_path_planning_amd.arcs import arc_table
-    from uam_path_planning_amd.engine import Engine
+    from uam_path_planning_amd.engine import Engine, Vertical
     from uam_path_planning_amd.geometry import compile_map
     from uam_path_planning_amd.scenario import (CONFIGS, build_region_map, canonical_params,
                                                 canonical_spec, displacements, layer_weights,
@@ -89,6 +94,8 @@ def main():
                           "kernel": kernel}), flush=True)
 
     pairs = eng.tensor(pairs_host, torch.float64)
+    # isotropic, climbs and descents limited to 10 degrees: every term of the definition runs
+    vert = Vertical(1e-3, profiles.sin_of_angle(10.0), profiles.sin_of_angle(10.0))
     for A in ([args.only_fused] if args.only_fused else [1, 2, 4, 8]):
         zt = eng.tensor(profiles.stack(*[profiles.lift(N, h) for h in heights[:A]]),
                         torch.float64)
@@ -97,9 +104,23 @@ def main():
         def fused():
             eng.eval_generated3d_profiles(pairs, ut, zt, volume, outputs=outs)
 
-        t = timed(fused)
-        report("fused", A, t, eng.last_kernel())
+        def fused_v():
+            eng.eval_generated3d_profiles(pairs, ut, zt, volume, outputs=outs, vertical=vert)
+
+        if not (args.only_fused and args.vertical):
+            report("fused", A, timed(fused), eng.last_kernel())
+        if not args.only_fused or args.vertical:
+            report("fused+v", A, timed(fused_v), eng.last_kernel())
         del outs
+        if A == 1 and not args.only_fused:   # the explicit forms on the same waypoints
+            wp3 = eng.gen_paths3d(pairs, ut, zt)
+            eng.set_option("wave_max_paths", 0)
+            report("explicit", A, timed(lambda: eng.eval_waypoints3d(wp3, volume)),
+                   eng.last_kernel())
+            report("explicit+v", A,
+                   timed(lambda: eng.eval_waypoints3d(wp3, volume, vertical=vert)),
+                   eng.last_kernel())
+            del wp3
     if args.only_fused:
         return
 

@@ -73,6 +73,12 @@ class PathOutputs(ctypes.Structure):
                                          "below_terrain")]
 
 
+class Vertical(ctypes.Structure):
+    """uam_vertical: the 3-D length, turn and climb rows of the _v evaluations."""
+    _fields_ = [("abi_version", ctypes.c_uint32), ("z_scale", ctypes.c_double),
+                ("sin_climb", ctypes.c_double), ("sin_descent", ctypes.c_double)]
+
+
 class RefineParams(ctypes.Structure):
     _fields_ = [("n_outer", ctypes.c_int32), ("n_inner", ctypes.c_int32),
                 ("max_backtrack", ctypes.c_int32), ("memory", ctypes.c_int32),
@@ -163,6 +169,13 @@ SIGNATURES = {
                                                      ctypes.c_int64, _vp, ctypes.c_int32, _vp,
                                                      ctypes.c_int32,
                                                      ctypes.POINTER(PathOutputs), _vp]),
+    "uam_eval_waypoints3d_v": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp,
+                                              ctypes.c_int64, ctypes.POINTER(Vertical),
+                                              ctypes.POINTER(PathOutputs), _vp, _vp]),
+    "uam_eval_generated3d_profiles_v": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp,
+                                                       ctypes.c_int64, _vp, ctypes.c_int32, _vp,
+                                                       ctypes.c_int32, ctypes.POINTER(Vertical),
+                                                       ctypes.POINTER(PathOutputs), _vp, _vp]),
     "uam_volume_packed_bytes": (ctypes.c_int, [ctypes.POINTER(VolumeDesc),
                                                ctypes.POINTER(ctypes.c_int64)]),
     "uam_volume_pack": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp, _vp]),

@@ -15,7 +15,9 @@
 //   K3b                k_eval_pairs_k3b
 //   (K6, L-BFGS)       k_rf_push k_refine
 //   K2w                k_eval_wave
-//   K4e / K4ew / K4p   k_eval_waypoints3d k_gen_paths3d k_eval_profiles
+//   K4e / K4ew / K4p   k_eval_waypoints3d k_gen_paths3d k_eval_profiles; with the vertical terms
+//                      (+v) k_eval_waypoints3d_v and the KVert instances of k_eval_wave and
+//                      k_eval_profiles
 //   K7                 k_tm_points k_tm_sep k_reproject
 //   K8                 k_ccl_init_dem k_ccl_init_sub k_ccl_merge k_ccl_flatten k_ccl_count_roots
 //                      k_ccl_assign k_ccl_stats k_ccl_extents; ccl_tile.inc: k_ccl_tile
@@ -3581,28 +3583,53 @@ struct PathSrc3 {
     }
 };
 
-// XYZ (volume mode, GEN = false): wp is [P][W][3] and the altitude the stored z (K4ew); the
-// instances without it are unchanged.
-template <int MODE, bool GEN, bool XYZ = false>
+// The vertical terms of uam_eval_waypoints3d_v / uam_eval_generated3d_profiles_v (uam_vertical,
+// include/uampath.h): dz = (z_j - z_{j-1}) * zs enters the segment norm and the turn's dot
+// product, and each segment adds two climb rows.
+struct KVert {
+    double zs, sc, sd;  // z_scale, sin_climb, sin_descent
+    double* climb;      // climb_sum [P] (nullptr: not wanted)
+};
+
+// the wave forms' LDS doubles per path; VERT adds the altitudes [W] and the climb rows [W-1][2]
+template <bool VERT>
+__host__ __device__ constexpr int64_t ewave_doubles_v(int N) {
+    return ewave_doubles(N) + (VERT ? 3 * (int64_t)(N + 2) : 0);
+}
+
+// A kernel's optional trailing KVert argument (a parameter pack of zero or one): the instances
+// without it keep their argument list
+__device__ __forceinline__ KVert vert_of() { return KVert{}; }
+__device__ __forceinline__ const KVert& vert_of(const KVert& v) { return v; }
+
+// XYZ (volume mode, GEN = false): wp is [P][W][3] and the altitude the stored z (K4ew); with
+// XYZ, a trailing KVert argument (V = KVert): the vertical terms (K4ew+v).  The instances
+// without them are unchanged.
+template <int MODE, bool GEN, bool XYZ = false, class... V>
 __global__ __launch_bounds__(256) void k_eval_wave(KGeom g, KParams p, KRaster rs, KVolume vs,
                                                    const uint4* __restrict__ rec,
                                                    const double* __restrict__ wp,
                                                    const double* __restrict__ pairs,
                                                    const double* __restrict__ utab, int D,
-                                                   int64_t n_paths, KOut out) {
+                                                   int64_t n_paths, KOut out, V... vert) {
+    constexpr bool VERT = sizeof...(V) != 0;
+    static_assert(!VERT || (XYZ && sizeof...(V) == 1), "the vertical terms need XYZ waypoints");
+    [[maybe_unused]] const KVert v = vert_of(vert...);
     extern __shared__ double ew_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     const int64_t path = (int64_t)blockIdx.x * wpb + wave;
     if (path >= n_paths) return;  // whole wave
     const int N = p.N, W = N + 2;
     const bool ls = p.length_smooth != 0, ms = p.maxratio_smooth != 0;
-    double* px = ew_lds + (int64_t)wave * ewave_doubles(N);
+    double* px = ew_lds + (int64_t)wave * ewave_doubles_v<VERT>(N);
     double* py = px + W;
     double* lq = py + W;  // get_cost length term of the segment ending at j (anchor for j=0)
     double* sg = lq + W;  // true segment norm
     double* ph = sg + W;  // Phi_j / N
     double* ps = ph + W;  // no-fly psi_j
     double* kn = ps + W;  // kinematic rows [N][3]
+    double* pz = kn + 3 * N;  // VERT: altitudes [W]
+    double* cl = pz + W;      // VERT: climb rows [W-1][2]
     std::conditional_t<XYZ, PathSrc3, PathSrc<GEN>> src;
     if constexpr (XYZ) {
         src.wp = wp + path * (int64_t)W * 3;
@@ -3633,6 +3660,7 @@ __global__ __launch_bounds__(256) void k_eval_wave(KGeom g, KParams p, KRaster r
         src.at(j, x, y);
         px[j] = x;
         py[j] = y;
+        if constexpr (VERT) pz[j] = src.alt(j);
     }
     wave_sync();
     // geometry terms: lq = get_cost length term of the segment ending at j (anchor segment
@@ -3655,22 +3683,37 @@ __global__ __launch_bounds__(256) void k_eval_wave(KGeom g, KParams p, KRaster r
             sg[0] = 0.0;
         } else {
             const double dx = x - px[j - 1], dy = y - py[j - 1];
+            double dz = 0.0;
             double s = 0.0;
             s = s + dx * dx;
             s = s + dy * dy;
+            if constexpr (VERT) {
+                dz = (pz[j] - pz[j - 1]) * v.zs;
+                s = s + dz * dz;
+            }
             const double n = sqrt(s);
             sg[j] = n;
             lq[j] = (!p.quirk_length || j <= N) ? (ls ? n * n : n) : 0.0;
+            if constexpr (VERT) {  // vert_segment's climb rows
+                cl[2 * (j - 1)] = fmax(0.0, dz - v.sc * n);
+                cl[2 * (j - 1) + 1] = fmax(0.0, (-dz) - v.sd * n);
+            }
             if (j >= 2) {  // kinematic row k = j-2, recomputing the previous segment
                 const double pdx = px[j - 1] - px[j - 2], pdy = py[j - 1] - py[j - 2];
+                double pdz = 0.0;
                 double s2 = 0.0;
                 s2 = s2 + pdx * pdx;
                 s2 = s2 + pdy * pdy;
+                if constexpr (VERT) {
+                    pdz = (pz[j - 1] - pz[j - 2]) * v.zs;
+                    s2 = s2 + pdz * pdz;
+                }
                 const double n2 = sqrt(s2);
                 const double pn = ms ? n2 * n2 : n2, nk = ms ? n * n : n;
                 double dt = 0.0;
                 dt = dt + pdx * dx;
                 dt = dt + pdy * dy;
+                if constexpr (VERT) dt = dt + pdz * dz;
                 double c1, c2, c3;
                 kin_row(p, pn, nk, dt, c1, c2, c3);
                 kn[3 * (j - 2)] = c1;
@@ -3689,6 +3732,8 @@ __global__ __launch_bounds__(256) void k_eval_wave(KGeom g, KParams p, KRaster r
     // chains B (lane 0 cost = (N+1) L + the nonzero Φ/N terms, lane 2 no-fly sum) follow.
     // The serial length is max(gather latency, W) + nnz(Φ) adds instead of max(2W, 3N).
     const int nkn = wave_compact_nonzero(kn, 3 * N, lane);
+    int ncl = 0;  // VERT: the climb rows are a fifth chain A, on lane 4
+    if constexpr (VERT) ncl = wave_compact_nonzero(cl, 2 * (W - 1), lane);
     double hmax = -INFINITY, cmin = INFINITY;
     int nh = 0, off = 0, below = 0;
     int32_t* cells = out.cells ? out.cells + path * W : nullptr;
@@ -3751,8 +3796,8 @@ __global__ __launch_bounds__(256) void k_eval_wave(KGeom g, KParams p, KRaster r
     };
     issue(lane);
     // chains A, beside the gathers
-    const double* arr = lane == 0 ? lq : (lane == 1 ? sg : kn);
-    const int na = lane < 2 ? W : (lane == 3 ? nkn : 0);
+    const double* arr = lane == 0 ? lq : (lane == 1 ? sg : ((VERT && lane == 4) ? cl : kn));
+    const int na = lane < 2 ? W : (lane == 3 ? nkn : ((VERT && lane == 4) ? ncl : 0));
     double acc = 0.0;
 #pragma unroll 8
     for (int i = 0; i < na; ++i) acc = acc + arr[i];
@@ -3791,6 +3836,10 @@ __global__ __launch_bounds__(256) void k_eval_wave(KGeom g, KParams p, KRaster r
         if (out.min_clearance)
             out.min_clearance[path] = MODE == UAM_MODE_RASTER ? p.altitude - hmax : cmin;
         if (out.below_terrain) out.below_terrain[path] = below;
+    }
+    if constexpr (VERT) {
+        const double csum = __shfl(acc, 4, 64);
+        if (lane == 0 && v.climb) v.climb[path] = csum;
     }
 }
 
@@ -3880,14 +3929,120 @@ constexpr int prof_chunk() {
     return AB <= 2 ? 8 : 4;
 }
 
-template <int AB>
+// get_cost's anchor term (path_pass1's first block): x/y only, also under the vertical terms
+__device__ __forceinline__ double anchor_term(const KParams& p, double px, double py) {
+    const double ax = p.anchor_mode ? p.anchor_x : px;
+    const double ay = p.anchor_mode ? p.anchor_y : py;
+    const double dx = px - ax, dy = py - ay;
+    double s = 0.0;
+    s = s + dx * dx;
+    s = s + dy * dy;
+    const double n = sqrt(s);
+    return p.length_smooth ? n * n : n;
+}
+
+// A path's running sums under the vertical terms (include/uampath.h, uam_vertical)
+struct VertAcc {
+    double L, len, ksum, csum;  // get_cost's length term, true length, kinematic and climb sums
+    double pdz, pn;             // the previous segment's scaled climb and its (squared) norm
+};
+
+__device__ __forceinline__ void vert_begin(const KParams& p, double px, double py, VertAcc& a) {
+    a.L = 0.0;
+    if (p.quirk_length) a.L = a.L + anchor_term(p, px, py);
+    a.len = a.ksum = a.csum = 0.0;
+    a.pdz = a.pn = 0.0;
+}
+
+// Segment j (1 .. N+1): sxy = (0 + dx dx) + dy dy and dxy = (0 + pdx dx) + pdy dy are its x/y
+// parts (shared by the profiles of a lateral candidate), dz = (z_j - z_{j-1}) * z_scale.  One
+// sqrt, kin_row's divisions and two climb rows; shared by K4e+v and K4p+v, so their bits agree
+// (k_eval_wave's instance with a KVert forms the same terms across the wave).
+__device__ __forceinline__ void vert_segment(const KParams& p, const KVert& v, int j, double sxy,
+                                             double dxy, double dz, VertAcc& a) {
+    const double s = sxy + dz * dz;
+    const double n = sqrt(s);
+    a.len = a.len + n;
+    if (!p.quirk_length || j <= p.N) a.L = a.L + (p.length_smooth ? n * n : n);
+    const double nk = p.maxratio_smooth ? n * n : n;
+    if (j >= 2) {
+        const double dt = dxy + a.pdz * dz;
+        double c1, c2, c3;
+        kin_row(p, a.pn, nk, dt, c1, c2, c3);
+        a.ksum = a.ksum + c1;
+        a.ksum = a.ksum + c2;
+        a.ksum = a.ksum + c3;
+    }
+    const double cu = fmax(0.0, dz - v.sc * n);
+    const double cd = fmax(0.0, (-dz) - v.sd * n);
+    a.csum = (a.csum + cu) + cd;
+    a.pdz = dz;
+    a.pn = nk;
+}
+
+// K4e+v: k_eval_waypoints3d with the 3-D pass 1; pass 2 is eval_path's volume branch
+__global__ __launch_bounds__(256) void k_eval_waypoints3d_v(KParams p, KVolume vs, KVert v,
+                                                            const double* __restrict__ wp3,
+                                                            int64_t n_paths, KOut out) {
+    const int64_t path = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (path >= n_paths) return;
+    const int N = p.N, W = N + 2;
+    PathSrc3 src;
+    src.wp = wp3 + path * (int64_t)W * 3;
+    double px, py, pz = src.alt(0);
+    src.at(0, px, py);
+    VertAcc g1;
+    vert_begin(p, px, py, g1);
+    double pdx = 0.0, pdy = 0.0;
+    for (int j = 1; j < W; ++j) {
+        double qx, qy;
+        src.at(j, qx, qy);
+        const double qz = src.alt(j);
+        const double dx = qx - px, dy = qy - py;
+        double sxy = 0.0, dxy = 0.0;
+        sxy = sxy + dx * dx;
+        sxy = sxy + dy * dy;
+        dxy = dxy + pdx * dx;
+        dxy = dxy + pdy * dy;
+        vert_segment(p, v, j, sxy, dxy, (qz - pz) * v.zs, g1);
+        pdx = dx, pdy = dy;
+        px = qx, py = qy, pz = qz;
+    }
+    if (v.climb) v.climb[path] = g1.csum;
+    PathAcc a;
+    a.L = g1.L, a.len = g1.len, a.ksum = g1.ksum;
+    a.cost = (double)(N + 1) * a.L;
+    a.nsum = 0.0;
+    a.nh = 0, a.off = 0, a.below = 0;
+    a.hmax = -INFINITY;
+    a.cmin = INFINITY;
+    const double dN = (double)N;
+    int32_t* cells = out.cells ? out.cells + path * W : nullptr;
+    for (int j0 = 0; j0 < W; j0 += 8) {
+        Chunk<8> ch;
+        issue_chunk_vol<false, 8>(vs, nullptr, src, j0, W, cells, ch);
+        consume_chunk_vol<false, 8>(vs, ch, src, j0, W, dN, a);
+    }
+    write_path(out, p, UAM_MODE_VOLUME, path, a);
+}
+
+// A trailing KVert argument (V = KVert; K4p+v): the vertical terms.  The norm then depends on
+// the profile, so pass 1 keeps the shared part of a segment (the arc point, dx, dy, sxy, dxy)
+// and runs vert_segment for each of the A profiles (7 doubles of state each); its sums are
+// stored as soon as it ends and only (N+1) L goes on into pass 2, whose chunk arrays are not
+// live before.  The instances without it are unchanged.
+template <int AB, class... V>
 __global__ __launch_bounds__(256) void k_eval_profiles(KParams p, KVolume vs,
                                                        const double* __restrict__ pairs6,
                                                        int64_t n_pairs,
                                                        const double* __restrict__ utab, int D,
                                                        const double* __restrict__ ztab, int A,
                                                        int64_t n_waves, KOut out,
-                                                       const int32_t* __restrict__ order) {
+                                                       const int32_t* __restrict__ order,
+                                                       V... vert) {
+    constexpr bool VERT = sizeof...(V) != 0;
+    static_assert(sizeof...(V) <= 1, "at most one KVert");
+    [[maybe_unused]] const KVert v = vert_of(vert...);
     constexpr int PC = prof_chunk<AB>();
     // order (optional): slot -> pair, K4's spatial order of the pairs; workgroup b then takes
     // the waves of xcd_chunk(b), so the pairs sharing an XCD's L2 are spatial neighbours.
@@ -3909,17 +4064,6 @@ __global__ __launch_bounds__(256) void k_eval_profiles(KParams p, KVolume vs,
         src.x0 = pr[0], src.y0 = pr[1], src.za = pr[2];
         src.xf = pr[3], src.yf = pr[4], src.zb = pr[5];
         src.u = utab + (int64_t)d * N * 2;
-        PathAcc g1;
-        path_pass1<true>(p, src, nullptr, g1);
-        ProfAcc acc[AB];
-#pragma unroll
-        for (int a = 0; a < AB; ++a) {
-            acc[a].cost = (double)(N + 1) * g1.L;
-            acc[a].nsum = 0.0;
-            acc[a].cmin = INFINITY;
-            acc[a].nh = 0, acc[a].off = 0, acc[a].below = 0;
-        }
-        const double dN = (double)N;
         const int64_t path0 = (q * D + d) * A;
         // the altitude of waypoint j under profile a (recomputed when consumed: its operands
         // come from scalar loads, and holding PC x A of them would cost as many registers as
@@ -3928,6 +4072,59 @@ __global__ __launch_bounds__(256) void k_eval_profiles(KParams p, KVolume vs,
             return ztab ? profile_alt(src.za, src.zb, ztab + ((int64_t)a * W + j) * 3)
                         : src.alt(j);
         };
+        PathAcc g1;
+        ProfAcc acc[AB];
+        if constexpr (VERT) {
+            VertAcc ga[AB];
+            double pz[AB];
+            double px, py;
+            src.at(0, px, py);
+#pragma unroll
+            for (int a = 0; a < AB; ++a) {
+                vert_begin(p, px, py, ga[a]);
+                pz[a] = a < A ? alt(a, 0) : 0.0;
+            }
+            double pdx = 0.0, pdy = 0.0;
+            for (int j = 1; j < W; ++j) {
+                double qx, qy;
+                src.at(j, qx, qy);
+                const double dx = qx - px, dy = qy - py;
+                double sxy = 0.0, dxy = 0.0;
+                sxy = sxy + dx * dx;
+                sxy = sxy + dy * dy;
+                dxy = dxy + pdx * dx;
+                dxy = dxy + pdy * dy;
+#pragma unroll
+                for (int a = 0; a < AB; ++a) {
+                    if (a >= A) continue;
+                    const double qz = alt(a, j);
+                    vert_segment(p, v, j, sxy, dxy, (qz - pz[a]) * v.zs, ga[a]);
+                    pz[a] = qz;
+                }
+                pdx = dx, pdy = dy;
+                px = qx, py = qy;
+            }
+#pragma unroll
+            for (int a = 0; a < AB; ++a) {
+                acc[a].cost = (double)(N + 1) * ga[a].L;
+                if (a >= A) continue;
+                const int64_t gp = path0 + a;
+                if (out.length_q) out.length_q[gp] = ga[a].L;
+                if (out.length) out.length[gp] = ga[a].len;
+                if (out.kin_sum) out.kin_sum[gp] = ga[a].ksum;
+                if (v.climb) v.climb[gp] = ga[a].csum;
+            }
+        } else {
+            path_pass1<true>(p, src, nullptr, g1);
+        }
+#pragma unroll
+        for (int a = 0; a < AB; ++a) {
+            if constexpr (!VERT) acc[a].cost = (double)(N + 1) * g1.L;
+            acc[a].nsum = 0.0;
+            acc[a].cmin = INFINITY;
+            acc[a].nh = 0, acc[a].off = 0, acc[a].below = 0;
+        }
+        const double dN = (double)N;
         for (int j0 = 0; j0 < W; j0 += PC) {
             uint2 col[PC], vox[PC][AB];
             uint32_t inb[PC];
@@ -3983,9 +4180,11 @@ __global__ __launch_bounds__(256) void k_eval_profiles(KParams p, KVolume vs,
             if (a >= A) continue;
             const int64_t gp = path0 + a;
             if (out.cost) out.cost[gp] = acc[a].cost;
-            if (out.length_q) out.length_q[gp] = g1.L;
-            if (out.length) out.length[gp] = g1.len;
-            if (out.kin_sum) out.kin_sum[gp] = g1.ksum;
+            if constexpr (!VERT) {
+                if (out.length_q) out.length_q[gp] = g1.L;
+                if (out.length) out.length[gp] = g1.len;
+                if (out.kin_sum) out.kin_sum[gp] = g1.ksum;
+            }
             if (out.nfz_sum) out.nfz_sum[gp] = acc[a].nsum;
             if (out.min_clearance) out.min_clearance[gp] = acc[a].cmin;
             if (out.nfz_hits) out.nfz_hits[gp] = acc[a].nh;
@@ -3994,6 +4193,7 @@ __global__ __launch_bounds__(256) void k_eval_profiles(KParams p, KVolume vs,
         }
     }
 }
+
 
 // ----------------------------------------------------------------------------------------
 // K7: coordinate reference systems.  Transverse Mercator between
@@ -8571,17 +8771,42 @@ int uam_gen_paths3d(uam_ctx* ctx, const double* pairs6, int64_t n_pairs, const d
     return UAM_OK;
 }
 
-int uam_eval_waypoints3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
-                         const double* wp3, int64_t n_paths, const uam_path_outputs* out,
-                         uam_stream stream) {
+// uam_vertical as the kernels take it; checked after the context's own state and before every
+// other argument
+static int vertical_view(const uam_vertical* vert, double* climb, KVert* kv) {
+    if (!vert) return fail(UAM_E_INVALID, "vert is NULL");
+    if (vert->abi_version != UAM_ABI_VERSION)
+        return fail(UAM_E_VERSION, "uam_vertical.abi_version %u != %d", vert->abi_version,
+                    UAM_ABI_VERSION);
+    if (!(vert->z_scale >= 0.0) || std::isinf(vert->z_scale))
+        return fail(UAM_E_INVALID, "z_scale must be finite and >= 0");
+    if (!(vert->sin_climb >= 0.0) || !(vert->sin_descent >= 0.0))
+        return fail(UAM_E_INVALID, "sin_climb and sin_descent must be >= 0 (+inf: no limit)");
+    kv->zs = vert->z_scale;
+    kv->sc = vert->sin_climb;
+    kv->sd = vert->sin_descent;
+    kv->climb = climb;
+    return UAM_OK;
+}
+
+// uam_eval_waypoints3d (with_vert unset) and uam_eval_waypoints3d_v
+static int eval_waypoints3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                            const double* wp3, int64_t n_paths, const uam_vertical* vert,
+                            bool with_vert, const uam_path_outputs* out, double* climb,
+                            uam_stream stream) {
     if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
         const int st = device_status(ctx);
         if (st) return st;
     }
     int st = check_ctx(ctx, true);
     if (st) return st;
-    st = no_exact_volume(ctx, "uam_eval_waypoints3d");
+    st = no_exact_volume(ctx, with_vert ? "uam_eval_waypoints3d_v" : "uam_eval_waypoints3d");
     if (st) return st;
+    KVert kvert{};
+    if (with_vert) {
+        st = vertical_view(vert, climb, &kvert);
+        if (st) return st;
+    }
     if (n_paths < 0) return fail(UAM_E_INVALID, "n_paths < 0");
     if (n_paths == 0) return UAM_OK;
     KVolume kv;
@@ -8594,45 +8819,77 @@ int uam_eval_waypoints3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     ctx->last_group = 0;
-    const int64_t per_wave = ewave_doubles(ctx->kp.N) * (int64_t)sizeof(double);
+    const int64_t per_wave = (with_vert ? ewave_doubles_v<true>(ctx->kp.N)
+                                        : ewave_doubles_v<false>(ctx->kp.N)) *
+                             (int64_t)sizeof(double);
     if (want_wave(ctx, n_paths) && per_wave <= 65536) {  // launch_wave's shape
         const int wpb = (int)std::min<int64_t>(4, 65536 / per_wave);
         const int64_t blocks = (n_paths + wpb - 1) / wpb;
         if (blocks <= INT32_MAX) {
-            ctx->last_kernel = "K4ew";
+            ctx->last_kernel = with_vert ? "K4ew+v" : "K4ew";
             st = ktime_begin(ctx, s);
             if (st) return st;
             const KRaster kr{};
-            hipLaunchKernelGGL((k_eval_wave<UAM_MODE_VOLUME, false, true>), dim3((unsigned)blocks),
-                               dim3(64 * wpb), (size_t)(wpb * per_wave), s, ctx->kg, ctx->kp, kr,
-                               kv, nullptr, wp3, nullptr, nullptr, 1, n_paths, ko);
+            if (with_vert)
+                hipLaunchKernelGGL((k_eval_wave<UAM_MODE_VOLUME, false, true>),
+                                   dim3((unsigned)blocks), dim3(64 * wpb),
+                                   (size_t)(wpb * per_wave), s, ctx->kg, ctx->kp, kr, kv, nullptr,
+                                   wp3, nullptr, nullptr, 1, n_paths, ko, kvert);
+            else
+                hipLaunchKernelGGL((k_eval_wave<UAM_MODE_VOLUME, false, true>),
+                                   dim3((unsigned)blocks), dim3(64 * wpb),
+                                   (size_t)(wpb * per_wave), s, ctx->kg, ctx->kp, kr, kv, nullptr,
+                                   wp3, nullptr, nullptr, 1, n_paths, ko);
             HIP_TRY(hipGetLastError());
             return ktime_end(ctx, s);
         }
     }
     const int64_t blocks = (n_paths + 255) / 256;
     if (blocks > INT32_MAX) return fail(UAM_E_INVALID, "batch too large");
-    ctx->last_kernel = "K4e";
+    ctx->last_kernel = with_vert ? "K4e+v" : "K4e";
     st = ktime_begin(ctx, s);
     if (st) return st;
-    hipLaunchKernelGGL(k_eval_waypoints3d, dim3((unsigned)blocks), dim3(256), 0, s, ctx->kg,
-                       ctx->kp, kv, wp3, n_paths, ko);
+    if (with_vert)
+        hipLaunchKernelGGL(k_eval_waypoints3d_v, dim3((unsigned)blocks), dim3(256), 0, s, ctx->kp,
+                           kv, kvert, wp3, n_paths, ko);
+    else
+        hipLaunchKernelGGL(k_eval_waypoints3d, dim3((unsigned)blocks), dim3(256), 0, s, ctx->kg,
+                           ctx->kp, kv, wp3, n_paths, ko);
     HIP_TRY(hipGetLastError());
     return ktime_end(ctx, s);
 }
 
-int uam_eval_generated3d_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
-                                  const double* pairs6, int64_t n_pairs, const double* utab,
-                                  int32_t D, const double* ztab, int32_t A,
-                                  const uam_path_outputs* out, uam_stream stream) {
+int uam_eval_waypoints3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                         const double* wp3, int64_t n_paths, const uam_path_outputs* out,
+                         uam_stream stream) {
+    return eval_waypoints3d(ctx, vd, vol, wp3, n_paths, nullptr, false, out, nullptr, stream);
+}
+
+int uam_eval_waypoints3d_v(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                           const double* wp3, int64_t n_paths, const uam_vertical* vert,
+                           const uam_path_outputs* out, double* climb_sum, uam_stream stream) {
+    return eval_waypoints3d(ctx, vd, vol, wp3, n_paths, vert, true, out, climb_sum, stream);
+}
+
+// uam_eval_generated3d_profiles (with_vert unset) and uam_eval_generated3d_profiles_v
+static int eval_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                         const double* pairs6, int64_t n_pairs, const double* utab, int32_t D,
+                         const double* ztab, int32_t A, const uam_vertical* vert, bool with_vert,
+                         const uam_path_outputs* out, double* climb, uam_stream stream) {
     if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
         const int st = device_status(ctx);
         if (st) return st;
     }
     int st = check_ctx(ctx, true);
     if (st) return st;
-    st = no_exact_volume(ctx, "uam_eval_generated3d_profiles");
+    st = no_exact_volume(ctx, with_vert ? "uam_eval_generated3d_profiles_v"
+                                        : "uam_eval_generated3d_profiles");
     if (st) return st;
+    KVert kvert{};
+    if (with_vert) {
+        st = vertical_view(vert, climb, &kvert);
+        if (st) return st;
+    }
     st = profile_dims(n_pairs, D, ztab, A);
     if (st) return st;
     if (n_pairs == 0) return UAM_OK;
@@ -8653,7 +8910,7 @@ int uam_eval_generated3d_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const
     const int64_t n_waves = (n_pairs + 63) / 64 * D;
     const int64_t blocks = (n_waves + 3) / 4;
     if (blocks > INT32_MAX) return fail(UAM_E_INVALID, "batch too large");
-    ctx->last_kernel = "K4p";
+    ctx->last_kernel = with_vert ? "K4p+v" : "K4p";
     ctx->last_group = 0;
     // K4's pair order over the volume's x/y extent (results do not depend on it)
     const int32_t* order = nullptr;
@@ -8667,8 +8924,16 @@ int uam_eval_generated3d_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const
     st = ktime_begin(ctx, s);
     if (st) return st;
 #define UAM_PROFILES(AB_)                                                                      \
-    hipLaunchKernelGGL((k_eval_profiles<AB_>), dim3((unsigned)blocks), dim3(256), 0, s,       \
-                       ctx->kp, kv, pairs6, n_pairs, utab, D, ztab, A, n_waves, ko, order)
+    do {                                                                                       \
+        if (with_vert)                                                                         \
+            hipLaunchKernelGGL((k_eval_profiles<AB_>), dim3((unsigned)blocks), dim3(256), 0,   \
+                               s, ctx->kp, kv, pairs6, n_pairs, utab, D, ztab, A, n_waves, ko, \
+                               order, kvert);                                                  \
+        else                                                                                   \
+            hipLaunchKernelGGL((k_eval_profiles<AB_>), dim3((unsigned)blocks), dim3(256), 0,   \
+                               s, ctx->kp, kv, pairs6, n_pairs, utab, D, ztab, A, n_waves, ko, \
+                               order);                                                         \
+    } while (0)
     if (A == 1)
         UAM_PROFILES(1);
     else if (A == 2)
@@ -8685,8 +8950,8 @@ int uam_eval_generated3d_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const
         st = order_done(ctx, s);
         if (st) return st;
     }
-    // main.py:175-180 over the pair's D * A candidates in index order c = d * A + a (every
-    // profile of a displacement stores the same length)
+    // main.py:175-180 over the pair's D * A candidates in index order c = d * A + a (without
+    // the vertical terms every profile of a displacement stores the same length)
     const dim3 g2(grid_for(n_pairs, 256, INT32_MAX));
     if (best_f)
         hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.cost, n_pairs, D * A, 1, best_f);
@@ -8694,6 +8959,23 @@ int uam_eval_generated3d_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const
         hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.length, n_pairs, D * A, 0, best_l);
     HIP_TRY(hipGetLastError());
     return UAM_OK;
+}
+
+int uam_eval_generated3d_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                                  const double* pairs6, int64_t n_pairs, const double* utab,
+                                  int32_t D, const double* ztab, int32_t A,
+                                  const uam_path_outputs* out, uam_stream stream) {
+    return eval_profiles(ctx, vd, vol, pairs6, n_pairs, utab, D, ztab, A, nullptr, false, out,
+                         nullptr, stream);
+}
+
+int uam_eval_generated3d_profiles_v(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                                    const double* pairs6, int64_t n_pairs, const double* utab,
+                                    int32_t D, const double* ztab, int32_t A,
+                                    const uam_vertical* vert, const uam_path_outputs* out,
+                                    double* climb_sum, uam_stream stream) {
+    return eval_profiles(ctx, vd, vol, pairs6, n_pairs, utab, D, ztab, A, vert, true, out,
+                         climb_sum, stream);
 }
 
 static int refine_memory(const uam_refine_params* rp) {

@@ -116,6 +116,21 @@ class VolumeGeo:
 
 
 @dataclass
+class Vertical:
+    """The vertical terms of eval_waypoints3d / eval_generated3d_profiles (uam_vertical):
+    z_scale km of path length per metre of altitude change (1e-3: isotropic), sin_climb /
+    sin_descent the largest climb / descent per unit of 3-D path length (inf: no limit;
+    profiles.sin_of_angle gives one from an angle)."""
+    z_scale: float
+    sin_climb: float = float("inf")
+    sin_descent: float = float("inf")
+
+    def as_struct(self):
+        return _lib.Vertical(_lib.ABI_VERSION, float(self.z_scale), float(self.sin_climb),
+                             float(self.sin_descent))
+
+
+@dataclass
 class RiskVolume:
     geo: VolumeGeo
     buf: object = field(repr=False)     # the device buffer (uam_volume_shape bytes)
@@ -368,7 +383,8 @@ class Engine:
         """Which path evaluation the last eval_generated / eval_generated3d ran (uam_last_kernel:
         "K2h+pack", "K2hx+pack" (the exact sums), "K2g+pack", "K4h+pack", "K4hx+pack" (the
         volume's exact sums), "K2s+pack", "K2+skip", "K2w", "K3b", ...), or the last
-        eval_waypoints3d ("K4e" / "K4ew") / eval_generated3d_profiles ("K4p")."""
+        eval_waypoints3d ("K4e" / "K4ew") / eval_generated3d_profiles ("K4p"); with vertical=
+        "K4e+v" / "K4ew+v" / "K4p+v"."""
         return self.lib.uam_last_kernel(self._ctx).decode()
 
     def last_group(self):
@@ -592,9 +608,21 @@ class Engine:
                                             _ptr(wp3), self.stream), "uam_gen_paths3d")
         return wp3
 
-    def eval_waypoints3d(self, wp3, volume, want_cells=False):
+    def _climb_sum(self, o, P):
+        """The climb_sum output of a _v call: the caller's (outputs["climb_sum"]) or a new one."""
+        torch = _torch()
+        if "climb_sum" not in o:
+            o["climb_sum"] = self.empty((P,), torch.float64)
+        elif o["climb_sum"].numel() < P:
+            raise ValueError(f"outputs['climb_sum'] holds {o['climb_sum'].numel()} entries, "
+                             f"this batch needs {P}")
+        return o["climb_sum"]
+
+    def eval_waypoints3d(self, wp3, volume, want_cells=False, vertical=None):
         """wp3 [P, N+2, 3] float64 (x km, y km, z m) against the volume's voxels
-        (uam_eval_waypoints3d: the oracle's eval_paths3d bit for bit).  Reads volume.buf only."""
+        (uam_eval_waypoints3d: the oracle's eval_paths3d bit for bit).  Reads volume.buf only.
+        vertical (a Vertical): the 3-D length, turn and climb rows (uam_eval_waypoints3d_v);
+        the result then holds climb_sum too."""
         torch = _torch()
         W = self.params.N + 2
         w = self.tensor(wp3, torch.float64)
@@ -604,17 +632,26 @@ class Engine:
         w = w.reshape(-1, W, 3)
         P = w.shape[0]
         o, s = self._outputs(P, W, _lib.MODE_VOLUME, want_cells, False)
+        if vertical is not None:
+            climb = self._climb_sum(o, P)
+            _lib.check(self.lib.uam_eval_waypoints3d_v(
+                self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf), _ptr(w), P,
+                ctypes.byref(vertical.as_struct()), ctypes.byref(s), _ptr(climb), self.stream),
+                "uam_eval_waypoints3d_v")
+            return o
         _lib.check(self.lib.uam_eval_waypoints3d(
             self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf), _ptr(w), P,
             ctypes.byref(s), self.stream), "uam_eval_waypoints3d")
         return o
 
     def eval_generated3d_profiles(self, pairs6, utab, ztab, volume, want_cells=False,
-                                  outputs=None):
+                                  outputs=None, vertical=None):
         """eval_waypoints3d of gen_paths3d's waypoints in one kernel, with the selection over
         each pair's D*A candidates (uam_eval_generated3d_profiles): path p = (q*D + d)*A + a,
         best_fval_idx / best_length_idx [Q] hold the candidate c = d*A + a.  Reads volume.buf
-        only."""
+        only.  vertical (a Vertical): the 3-D length, turn and climb rows
+        (uam_eval_generated3d_profiles_v); the lengths and both selections then depend on the
+        profile, and the result holds climb_sum too."""
         pr, ut, zt, Q, D, A = self._profile_inputs(pairs6, utab, ztab)
         W = self.params.N + 2
         if outputs is not None:
@@ -622,6 +659,13 @@ class Engine:
             _check_outputs(o, Q * D * A, Q, W)
         else:
             o, s = self._outputs(Q * D * A, W, _lib.MODE_VOLUME, want_cells, False, n_pairs=Q)
+        if vertical is not None:
+            climb = self._climb_sum(o, Q * D * A)
+            _lib.check(self.lib.uam_eval_generated3d_profiles_v(
+                self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf), _ptr(pr), Q,
+                _ptr(ut), D, _ptr(zt), A, ctypes.byref(vertical.as_struct()), ctypes.byref(s),
+                _ptr(climb), self.stream), "uam_eval_generated3d_profiles_v")
+            return o
         _lib.check(self.lib.uam_eval_generated3d_profiles(
             self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf), _ptr(pr), Q,
             _ptr(ut), D, _ptr(zt), A, ctypes.byref(s), self.stream),

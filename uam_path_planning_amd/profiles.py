@@ -5,7 +5,8 @@ pair (x0, y0, z0, xf, yf, zf) under profile a flies at
 
     z_j = (z0 * ztab[a, j, 0] + zf * ztab[a, j, 1]) + ztab[a, j, 2]
 
-(include/uampath.h: two products, their sum, then the third coefficient, each rounded).  The
+(include/uampath.h: two products, their sum, then the third coefficient, each rounded;
+sin_of_angle() gives the climb limits of engine.Vertical from an angle).  The
 helpers below build common rows with t_j = j / (N+1); their own rounding is not normative, any
 [N+2, 3] array is a valid profile.  Rows 0 and N+1 are exactly (1, 0, 0) and (0, 1, 0), so a
 path starts and ends at the pair's own altitudes, bit for bit.
@@ -55,6 +56,17 @@ def lift(N, height_m, ramp=0.25):
     t = _t(N)
     w = _ramp(t, ramp)
     return _finish(np.stack([1.0 - t, t, w * float(height_m)], axis=1))
+
+
+def sin_of_angle(degrees):
+    """sin of a climb (or descent) angle in degrees, for Vertical.sin_climb / sin_descent: the
+    largest altitude change per unit of 3-D path length, both in the length's unit (the
+    altitude change scaled by Vertical.z_scale).  0 <= degrees <= 90; 90 gives 1, which no
+    segment exceeds (use inf for "no limit")."""
+    d = float(degrees)
+    if not 0.0 <= d <= 90.0:
+        raise ValueError(f"climb angle = {d} degrees must be in [0, 90]")
+    return 1.0 if d == 90.0 else float(np.sin(np.deg2rad(d)))
 
 
 def stack(*tables):

@@ -785,6 +785,59 @@ int uam_volume_sum_scale(uam_ctx* ctx, const uam_volume_desc* desc, const void* 
                          int32_t* scale_dev, uam_stream stream);
 int uam_set_volume_sum_scale(uam_ctx* ctx, const int32_t* scale_dev);
 
+/* ---- Altitude-profile candidates on the packed, sorted volume (K4hp) -------------------------
+ * uam_eval_generated3d_profiles walks vol_dev one lane per lateral candidate at every batch
+ * size.  This call takes the profile table's altitudes through K4h's form instead: the
+ * (path, group) items sorted on the altitude band and tile of their middle waypoint at the
+ * profile's own z, gathers from packed_dev (uam_volume_pack), grouped partial sums, the
+ * geometry in the similarity form.  Layout as uam_eval_generated3d_profiles: path p =
+ * (q*D + d)*A + a, candidate c = d*A + a, 1 <= A <= 8, D <= 16.  vol_dev is not read (NULL is
+ * allowed).
+ *
+ * Definition (normative).  Every float64 operation is rounded, none is contracted.  G =
+ * UAM_OPT_GROUP (G >= 1), W = N + 2.
+ *   points     x/y of waypoint j are uam_gen_paths3d's: the pair's own end points at j = 0 and
+ *              j = N+1, the arc formula in between (K4h's operations).  z_j follows the table
+ *              rule (z0 * ztab[a][j][0] + zf * ztab[a][j][1]) + ztab[a][j][2].
+ *              NULL-table rule: ztab_dev == NULL (A must be 1) means uam_eval_generated3d's
+ *              straight climb z0 + (zf - z0) * ((double)j / (double)(N+1)); the call then runs
+ *              K4h's own kernels and gives uam_eval_generated3d's K4h bits (uam_last_kernel
+ *              "K4h+pack" / "K4hx+pack").
+ *   geometry   length_q, length and kin_sum are K4h's similarity-form values of (q, d) (oracle
+ *              sim_geo, orc_eval_generated_h), identical for the A profiles.
+ *   cost       group order: cost = ((N+1) L + P_0) + P_1 + ... with P_k the sum from +0.0, in
+ *              waypoint order, of (double)risk_j / (double)N over the waypoints j in
+ *              [k G, min((k+1) G, W)) that lie inside the volume by their own (x, y, z).
+ *   nfz_sum    the same group order from +0.0 with (double)psi_j as the term (the oracle's gacc
+ *              on the profile's voxels).
+ *   nfz_hits, offmap, below_terrain, min_clearance: per path, exactly as uam_eval_waypoints3d
+ *              defines them; min_clearance is +inf when no waypoint lies inside the volume.
+ *   selections best_fval_idx and best_length_idx follow uam_argmin's rule over the pair's D*A
+ *              candidates in index order c; they need the cost / length output respectively.
+ *   reporting  uam_last_group reports G; uam_last_kernel "K4hp+pack" ("K4hpx+pack": exact form).
+ * Exact form: with UAM_OPT_EXACT_SUM_VOLUME = 1 the call uses the exact volume sums above (the
+ * same term, 128-bit sum, single rounding, side flags and volume scale as K4h's exact form):
+ * cost = (double)(N+1) L + fl(S_risk) / (double)N, nfz_sum = fl(S_psi), every other output as
+ * above.  The bits then do not depend on G, the chunk, the terrain form, tile bits, band, curve,
+ * the batch size or the sharding.  UAM_E_STATE when no volume sum scale is set.
+ * Dispatch: the call has a sum order of its own, so it is never falling back to K4p, K4 or
+ * K4w, at any batch size: UAM_OPT_SORTED_MIN_PATHS and UAM_OPT_WAVE_MAX_PATHS do not apply, and
+ * a path's bits do not depend on the batch it is in.  Every case it does not take is
+ * UAM_E_INVALID with its reason (uam_last_error), raised on the host before any launch or
+ * allocation, the context staying usable: no packed_dev; UAM_OPT_GROUP = 0; maxratio_smooth;
+ * UAM_OPT_K2G_SIM = 0; D > 16; A outside [1, 8] or a NULL table with A != 1; N > 4096; cells or
+ * g_rows requested; a unit-arc table (48 KiB), profile table (40 KiB) or packed header (64 KiB)
+ * over its LDS share; more (tile, band) bins, (path, group) items (Q D A groups >= 2^31) or scan
+ * blocks than the sort holds; a packed copy K4h stands aside for; packed_dev / vol_dev not
+ * 256-B, pairs6_dev / utab_dev not 16-B or ztab_dev not 8-B aligned.  The sort's device check
+ * applies as for K4h (uam_device_status).  The vertical terms have no such form (the similarity
+ * form is not scale-free once the altitude differences enter the norm): there is no _v variant. */
+int uam_eval_generated3d_profiles_h(uam_ctx* ctx, const uam_volume_desc* desc,
+                                    const void* vol_dev, const void* packed_dev,
+                                    const double* pairs6_dev, int64_t n_pairs,
+                                    const double* utab_dev, int32_t D, const double* ztab_dev,
+                                    int32_t A, const uam_path_outputs* out, uam_stream stream);
+
 /* Workspace bytes uam_refine needs for n_paths (after uam_set_geometry/uam_set_params). */
 int64_t uam_refine_workspace_bytes(uam_ctx* ctx, int64_t n_paths,
                                    const uam_refine_params* params);

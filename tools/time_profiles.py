@@ -4,7 +4,9 @@ cfg5 volume (1024^2 x 64 layers, 100k pairs, D = 5) for A in {1, 2, 4, 8} lift p
 the same work without sharing: A separate eval_generated3d calls on pairs whose end altitudes
 are shifted by the lift heights, once in the K4 form (no packed copy) and once in K4h.  The
 shifted pairs fly the straight climb at another height, not the lift's ramp: the comparison is
-of the work (A x Q x D paths through the same volume), not of the bits.  Beside each fused
+of the work (A x Q x D paths through the same volume), not of the bits.  Last, the same lift
+tables in the sorted form on the packed copy (K4hp, packed=True): one call that flies the
+profiles themselves and selects over D x A, where the K4h column is a stand-in.  Beside each fused
 form its form with the vertical terms (K4p+v: 3-D length, turn and climb rows per profile), and
 for A = 1 the explicit forms K4e / K4e+v on the same waypoints.
 
@@ -142,6 +144,18 @@ def main():
 
             t = timed(separate)
             report("separate " + form, A, t, eng.last_kernel())
+    del outs
+    # the profiles themselves in the sorted form (the volume is packed by now)
+    for A in (1, 2, 4, 8):
+        zt = eng.tensor(profiles.stack(*[profiles.lift(N, h) for h in heights[:A]]),
+                        torch.float64)
+        outs = eng.outputs(Q * D * A, W, n_pairs=Q)
+
+        def packed():
+            eng.eval_generated3d_profiles(pairs, ut, zt, volume, outputs=outs, packed=True)
+
+        report("packed", A, timed(packed), eng.last_kernel())
+        del outs
 
 
 if __name__ == "__main__":

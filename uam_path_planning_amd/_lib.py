@@ -169,6 +169,10 @@ SIGNATURES = {
                                                      ctypes.c_int64, _vp, ctypes.c_int32, _vp,
                                                      ctypes.c_int32,
                                                      ctypes.POINTER(PathOutputs), _vp]),
+    "uam_eval_generated3d_profiles_h": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp,
+                                                       _vp, ctypes.c_int64, _vp, ctypes.c_int32,
+                                                       _vp, ctypes.c_int32,
+                                                       ctypes.POINTER(PathOutputs), _vp]),
     "uam_eval_waypoints3d_v": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp,
                                               ctypes.c_int64, ctypes.POINTER(Vertical),
                                               ctypes.POINTER(PathOutputs), _vp, _vp]),

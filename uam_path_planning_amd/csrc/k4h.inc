@@ -340,6 +340,8 @@ __global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
 // ones as side flags.  One body for both forms, in the kernel itself: moved into an inlined
 // function, the EX = false instantiations no longer allocated the registers they had (DESIGN
 // §10), so the exact form is this kernel's third template flag and vs.xscale its scale.
+// k_vp_eval (k4hp.inc) is a copy of this body with the altitude from the profile table (a body
+// of its own for the same reason): a fix to the phases here belongs there too.
 template <int CH, bool TE, bool EX = false>  // TE: the terrain in the entry (UAM_OPT_K4H_TERRAIN 1)
 __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(KParams p, KVol4 vs,
                                                                               KGrp kg) {

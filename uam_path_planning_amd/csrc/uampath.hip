@@ -35,11 +35,13 @@
 //   sum_scale.inc      k_sum_scale_init k_sum_scale
 //   k4h.inc            K4h: k_volume_pack_planes k_volume_pack_t4 k_volume_codes k_v_hist
 //                      k_v_eval (k_v_eval_x) k_v_final k_v_final_x
+//   k4hp.inc           K4hp: k_vp_hist k_vp_eval (k_vp_eval_x) k_vp_final k_vp_final_x
+//                      k_vp_sel_check
 //   struct uam_ctx and its helpers; then the C ABI (include/uampath.h) with the launches'
 //   static helpers between its entry points: context, geometry, params, K1; K2w launch; the
-//   option table; pair-order scratch and K2s launch; the grouped plan (K2g / K2h / K4h);
-//   PackDims and eval_generated's dispatch; raster, volume, 3-D profile, refinement, CRS,
-//   polygon and RCCL entry points.
+//   option table; pair-order scratch and K2s launch; the grouped plan (K2g / K2h / K4h / K4hp);
+//   PackDims and eval_generated's dispatch; raster, volume, 3-D profile (K4hp's entry point
+//   among them), refinement, CRS, polygon and RCCL entry points.
 //
 // Numerics: float64 throughout, compiled with -ffp-contract=off so every product and sum is a
 // separately rounded IEEE operation in the reference's order (problem.py, quadratic_obstacle.py,
@@ -6268,6 +6270,9 @@ __global__ __launch_bounds__(1024) void k_g_final(KParams p, KGrp kg, KOut out,
 // K4h: packed volume, k_volume_pack_planes / _t4, k_volume_codes, k_v_hist, k_v_eval, k_v_final*
 #include "k4h.inc"
 
+// K4hp: the altitude profiles on the packed, sorted volume, k_vp_hist, k_vp_eval, k_vp_final*
+#include "k4hp.inc"
+
 // closes the anonymous namespace opened above the device-side tables
 }  // namespace
 
@@ -6325,6 +6330,7 @@ struct uam_ctx {
     bool k2h_hist_attr = false, k4h_hist_attr = false;  // k_g_hist's and k_v_hist's, likewise
     bool k2g_attrs = false;     // K2g dynamic-LDS attributes raised on this context's device
     bool k4h_attrs = false;     // the same for K4h
+    bool k4hp_attrs = false, k4hp_hist_attr = false;  // and for K4hp (k_vp_eval, k_vp_hist)
     void* d_ord = nullptr;      // pair_order scratch (grow-only)
     uint16_t* d_tkey = nullptr; // K2g: sort key of each tile (curve order), for tkey_bits/curve
     int tkey_bits = -1, tkey_curve = -1;
@@ -7498,6 +7504,8 @@ struct GPlan {
     const char* needs;        // how the exact form's refusals begin
     const int32_t* scale;     // the exact form's sum scale (null: none set)
     bool seeds;               // the histogram launch forms each path's seed (kg.lbp / kg.ubp)
+    bool must;                // a call with a sum order of its own (uam_eval_generated3d_
+                              // profiles_h): as the exact forms, sorted or an error
     HEvalXFn hevx;
     HFinalXFn finx;
     int64_t ncnt, nsb;        // counts ([bins][G_NBK]) and scan blocks
@@ -7513,7 +7521,7 @@ struct GPlan {
 // the exact forms never stand aside for another sum order: a batch they do not take is an
 // error with its reason (at every size: UAM_OPT_SORTED_MIN_PATHS does not apply)
 static int grouped_no(const GPlan& pl, const char* why) {
-    return pl.exact ? fail(UAM_E_INVALID, "%s: %s", pl.needs, why) : 0;
+    return pl.exact || pl.must ? fail(UAM_E_INVALID, "%s: %s", pl.needs, why) : 0;
 }
 
 // A family's tile bits for a batch of n_items over nx x ny cells in nbands bands: returns the
@@ -7553,11 +7561,12 @@ static int volume_tiles(const uam_ctx* ctx, int32_t, int32_t, int32_t nbands, in
 // What every sorted form shares: the item and bin counts, the scan blocks, the 256-B aligned
 // scratch sizes (slot / seed: the family's bytes per item / per path) and KGrp's common fields.
 // Reads pl->sim (set by the caller: it decides the bins).  Returns as grouped_plan does.
+// A: K4hp's profiles per lateral candidate, inside the path index (P = Q D A; kg.D stays D).
 static int grouped_sizes(uam_ctx* ctx, GPlan* pl, const double* pairs, int64_t n_pairs,
                          const double* utab, int32_t D, int32_t nx, int32_t ny, int32_t nbands,
-                         GTilesFn tiles_of, size_t slot, size_t seed) {
+                         GTilesFn tiles_of, size_t slot, size_t seed, int32_t A = 1) {
     const int G = ctx->k2g_group;
-    const int64_t W = ctx->kp.N + 2, P = n_pairs * D;
+    const int64_t W = ctx->kp.N + 2, P = n_pairs * D * A;
     const int nseg = (int)((W + G - 1) / G);
     const int64_t n_items = P * nseg;
     if (n_items >= INT32_MAX) return grouped_no(*pl, "more than 2^31 (path, group) items");
@@ -7851,26 +7860,37 @@ static int launch_grouped(uam_ctx* ctx, const KRaster& kr, const void* rec, cons
     return st ? st : 1;
 }
 
+// What K4h and K4hp both refuse, in the order a caller sees it (one list, so the two plans do
+// not diverge): the reason, or null.  (UAM_OPT_GROUP is at most G_MAXLEN by the option table.)
+static const char* volume_refusal(const uam_ctx* ctx, const KVol4& kv, const KOut& ko, int32_t D) {
+    const int G = ctx->k2g_group;
+    if (G < 1) return "UAM_OPT_GROUP is 0";
+    if (G > G_MAXLEN) return "UAM_OPT_GROUP exceeds the longest group";
+    if (ko.cells || ko.g_rows) return "cells or g_rows requested";
+    if (D > 16) return "D > 16";
+    if (ctx->kp.maxratio_smooth) return "maxratio_smooth is set";
+    if (!ctx->k2g_sim) return "UAM_OPT_K2G_SIM is 0";
+    if (!kv.pk) return "the packed copy is 4 GiB or larger, or a layer or side holds 2^24 entries";
+    if (ctx->kp.N > 4096) return "N > 4096";
+    return nullptr;
+}
+
 // the sequence a volume batch takes (K4h): as grouped_plan
 static int grouped_plan3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
-                          const double* utab, int32_t D, const KOut& ko, GPlan* pl) {
+                          const double* utab, int32_t D, const KOut& ko, GPlan* pl,
+                          bool must = false) {
     const int G = ctx->k2g_group;
     const bool exact = ctx->exact_sum_vol != 0;
     *pl = GPlan{};
     pl->vol = pl->sim = true;
     pl->exact = exact;
-    pl->needs = "UAM_OPT_EXACT_SUM_VOLUME needs K4h";
+    pl->must = must;
+    pl->needs = must ? "uam_eval_generated3d_profiles_h needs K4h"
+                     : "UAM_OPT_EXACT_SUM_VOLUME needs K4h";
     pl->scale = exact ? ctx->vol_sum_scale : nullptr;
     auto no = [&](const char* why) { return grouped_no(*pl, why); };
-    if (G < 1 || G > G_MAXLEN) return no("UAM_OPT_GROUP is 0");
-    if (ko.cells || ko.g_rows) return no("cells or g_rows requested");
-    if (D > 16) return no("D > 16");
-    if (ctx->kp.maxratio_smooth) return no("maxratio_smooth is set");
-    if (!ctx->k2g_sim) return no("UAM_OPT_K2G_SIM is 0");
-    if (!kv.pk)
-        return no("the packed copy is 4 GiB or larger, or a layer or side holds 2^24 entries");
-    if (ctx->kp.N > 4096) return no("N > 4096");
-    if (!exact && n_pairs * D < ctx->k2s_min) return 0;
+    if (const char* why = volume_refusal(ctx, kv, ko, D)) return no(why);
+    if (!exact && !must && n_pairs * D < ctx->k2s_min) return 0;
     if (n_pairs > INT32_MAX / D) return no("more than 2^31 paths");
     const size_t ubytes = (size_t)D * ctx->kp.N * 16;
     if (ubytes > (size_t)G_UTAB_LDS) return no("the unit-arc table exceeds its LDS share");
@@ -7923,9 +7943,9 @@ static int grouped_plan3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, i
 // with its reason, raised before any launch.
 static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
                             const double* utab, int32_t D, const KOut& ko, int32_t* best_f,
-                            int32_t* best_l, hipStream_t s) {
+                            int32_t* best_l, hipStream_t s, bool must = false) {
     GPlan pl;
-    int st = grouped_plan3d(ctx, kv, pairs6, n_pairs, utab, D, ko, &pl);
+    int st = grouped_plan3d(ctx, kv, pairs6, n_pairs, utab, D, ko, &pl, must);
     if (st <= 0) return st;
     if (pl.exact && !pl.scale)
         return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM_VOLUME is on and no volume sum scale is set "
@@ -7954,6 +7974,135 @@ static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6,
     if (st) return st;
     ctx->last_group = pl.kg.G;
     ctx->last_kernel = pl.exact ? "K4hx+pack" : "K4h+pack";
+    st = order_done(ctx, s);
+    return st ? st : 1;
+}
+
+// K4hp (uam_eval_generated3d_profiles_h): K4h's plan with the profile inside the path index.
+// The call has a sum order of its own, so every batch it does not take is an error (pl->must):
+// returns 1 or < 0, never 0.
+using VPEvalFn = void (*)(KParams, KVol4, KGrp, KProf);
+struct VPGrid {  // the histogram launch's grid: the volume's view and the profiles
+    KVol4 kv;
+    KProf kf;
+};
+
+static void volume_profile_hist(uam_ctx* ctx, const KGrp& kg, const void* g, size_t lds,
+                                hipStream_t s) {
+    const VPGrid* vg = (const VPGrid*)g;
+    hipLaunchKernelGGL(k_vp_hist, dim3(G_NBK), dim3(1024), lds, s, ctx->kp, vg->kv, kg, vg->kf);
+}
+
+static int grouped_plan3dp(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
+                           const double* utab, int32_t D, int32_t A, const KOut& ko, GPlan* pl,
+                           VPEvalFn* vpev) {
+    const int G = ctx->k2g_group;
+    const bool exact = ctx->exact_sum_vol != 0;
+    *pl = GPlan{};
+    pl->vol = pl->sim = true;
+    pl->exact = exact;
+    pl->must = true;
+    pl->needs = "uam_eval_generated3d_profiles_h needs K4hp";
+    pl->scale = exact ? ctx->vol_sum_scale : nullptr;
+    auto no = [&](const char* why) { return grouped_no(*pl, why); };
+    if (const char* why = volume_refusal(ctx, kv, ko, D)) return no(why);
+    const int64_t W = ctx->kp.N + 2, npad = G + 16;  // k_vp_eval's padding slots
+    const size_t ubytes = (size_t)D * ctx->kp.N * 16;
+    if (ubytes > (size_t)G_UTAB_LDS) return no("the unit-arc table exceeds its LDS share");
+    if ((size_t)A * W * 24 > (size_t)VPK_ZTAB_LDS)
+        return no("the profile table exceeds its LDS share");
+    if ((size_t)kv.hwords * 4 > (size_t)VPK_HDR_LDS)
+        return no("the packed header exceeds its LDS share");
+    int st = grouped_sizes(ctx, pl, pairs6, n_pairs, utab, D, kv.nx, kv.ny, kv.nbands,
+                           volume_tiles, exact ? sizeof(VSlotX) : sizeof(VSlot), 8, A);
+    if (st <= 0) return st;
+    // K4h's shape: 3 workgroups per CU through the LDS floor, 7 gathers in flight
+    pl->lds = std::max((size_t)(D * ctx->kp.N + npad) * 16 +
+                           (size_t)(((A * W + npad) * 3 + 1) & ~(int64_t)1) * 8 +
+                           (size_t)(ctx->k4h_te ? kv.bnd_off : kv.hwords) * 4,
+                       (size_t)std::min(ctx->k2g_lds ? ctx->k2g_lds : 40000, 160 * 1024));
+    if (pl->lds > 160 * 1024) return no("the arc rows, profile rows and header exceed the LDS");
+    pl->bs = 256;
+    pl->seeds = ctx->k2h_lbs > 0 && !ctx->k4h_te;
+    pl->hist_dyn = (size_t)kv.hwords * 4 + ubytes;
+    const int chl = ctx->k2g_chunk ? ctx->k2g_chunk : 7;
+    static const VPEvalFn vevals[10] = {k_vp_eval<6, false>, k_vp_eval<7, false>,
+                                        k_vp_eval<8, false>,  k_vp_eval<11, false>,
+                                        k_vp_eval<16, false>, k_vp_eval<6, true>,
+                                        k_vp_eval<7, true>,   k_vp_eval<8, true>,
+                                        k_vp_eval<11, true>,  k_vp_eval<16, true>};
+    static const VPEvalFn vevalsx[10] = {k_vp_eval_x<6, false>, k_vp_eval_x<7, false>,
+                                         k_vp_eval_x<8, false>,  k_vp_eval_x<11, false>,
+                                         k_vp_eval_x<16, false>, k_vp_eval_x<6, true>,
+                                         k_vp_eval_x<7, true>,   k_vp_eval_x<8, true>,
+                                         k_vp_eval_x<11, true>,  k_vp_eval_x<16, true>};
+    const int vi = (chl <= 6 ? 0 : chl == 7 ? 1 : chl <= 8 ? 2 : chl == 11 ? 3 : 4) +
+                   (ctx->k4h_te ? 5 : 0);
+    *vpev = exact ? vevalsx[vi] : vevals[vi];
+    if (pl->lds > 64 * 1024) {
+        st = raise_lds(&ctx->k4hp_attrs, 160 * 1024, vevals, vevalsx);
+        if (st) return st;
+    }
+    return 1;
+}
+
+static int launch_grouped3dp(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
+                             const double* utab, int32_t D, const double* ztab, int32_t A,
+                             const KOut& ko, int32_t* best_f, int32_t* best_l, hipStream_t s) {
+    GPlan pl;
+    VPEvalFn vpev = nullptr;
+    int st = grouped_plan3dp(ctx, kv, pairs6, n_pairs, utab, D, A, ko, &pl, &vpev);
+    if (st <= 0) return st;
+    if (pl.exact && !pl.scale)
+        return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM_VOLUME is on and no volume sum scale is set "
+                                 "(uam_volume_sum_scale, uam_set_volume_sum_scale)");
+    char* w = nullptr;
+    st = order_scratch(ctx, pl.bytes, s, &w);
+    if (st) return st;
+    st = tile_keys(ctx, pl.kg.tbits, ctx->k2g_curve, s);
+    if (st) return st;
+    pl.kg.tkey = ctx->d_tkey;
+    grouped_carve(&pl, w);
+    st = err_word(ctx, &pl.kg);
+    if (st) return st;
+    st = ktime_begin(ctx, s);
+    if (st) return st;
+    if (pl.kg.seed_lds) {
+        static const VPEvalFn hist[1] = {k_vp_hist};
+        st = raise_lds(&ctx->k4hp_hist_attr, G_HIST_DYN_MAX, hist);
+        if (st) return st;
+    }
+    VPGrid vg{kv, KProf{}};
+    vg.kf.ztab = ztab;
+    vg.kf.A = A;
+    magic_div((uint32_t)A, &vg.kf.m_a, &vg.kf.sh_a);
+    if (pl.exact) vg.kv.xscale = pl.scale;
+    const KGrp& kg = pl.kg;
+    grouped_sort(ctx, pl, volume_profile_hist, &vg, s);
+    hipLaunchKernelGGL(vpev, dim3((unsigned)((kg.n_items + pl.bs - 1) / pl.bs)), dim3(pl.bs),
+                       pl.lds, s, ctx->kp, vg.kv, kg, vg.kf);
+    const dim3 gfin((unsigned)(((int64_t)kg.P + 255) / 256));
+    if (pl.exact)
+        hipLaunchKernelGGL(k_vp_final_x, gfin, dim3(256), 0, s, ctx->kp, kg, vg.kf, ko, pl.scale);
+    else
+        hipLaunchKernelGGL(k_vp_final, gfin, dim3(256), 0, s, ctx->kp, kg, vg.kf, ko);
+    // uam_argmin's rule over the pair's D * A candidates, as K4p
+    if (best_f || best_l) {
+        const dim3 g2(grid_for(n_pairs, 256, INT32_MAX));
+        if (best_f)
+            hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.cost, n_pairs, D * A, 1, best_f);
+        if (best_l)
+            hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.length, n_pairs, D * A, 0,
+                               best_l);
+        hipLaunchKernelGGL(k_vp_sel_check, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0,
+                           s, kg.err, n_pairs, best_f, best_l);
+    }
+    if (hipGetLastError() != hipSuccess)
+        return fail(UAM_E_HIP, "grouped volume profile evaluation launch");
+    st = ktime_end(ctx, s);
+    if (st) return st;
+    ctx->last_group = kg.G;
+    ctx->last_kernel = pl.exact ? "K4hpx+pack" : "K4hp+pack";
     st = order_done(ctx, s);
     return st ? st : 1;
 }
@@ -8629,6 +8778,21 @@ int uam_volume_pack(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol, vo
     return UAM_OK;
 }
 
+// the packed copy as K4h / K4hp read it, with the sort key's altitude bands
+static void packed_view(const uam_ctx* ctx, const uam_volume_desc* vd, const void* packed,
+                        KVol4* k4) {
+    VpkDims v;
+    vpk_dims(vd, &v);
+    vpk_kvol(vd, v, packed, k4);
+    int zs = 0;  // altitude bands: at most 16, or UAM_OPT_K4H_BAND layers each
+    if (ctx->k4h_band > 0) {
+        while ((1 << zs) < ctx->k4h_band) ++zs;
+    }
+    while ((vd->nz - 1) >> zs >= 16) ++zs;
+    k4->zshift = zs;
+    k4->nbands = ((vd->nz - 1) >> zs) + 1;
+}
+
 // The failures, in the order a caller sees them: an earlier call's device check; the context
 // (NULL, no geometry, no params); the exact form without packed_dev; n_pairs / D (n_pairs == 0
 // then returns UAM_OK); the volume descriptor; pairs6 / utab NULL; with packed_dev its
@@ -8663,16 +8827,7 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
     if (packed) {
         if ((uintptr_t)packed & 255) return fail(UAM_E_INVALID, "packed volume not 256-B aligned");
         KVol4 k4{};
-        VpkDims v;
-        vpk_dims(vd, &v);
-        vpk_kvol(vd, v, packed, &k4);
-        int zs = 0;  // altitude bands: at most 16, or UAM_OPT_K4H_BAND layers each
-        if (ctx->k4h_band > 0) {
-            while ((1 << zs) < ctx->k4h_band) ++zs;
-        }
-        while ((vd->nz - 1) >> zs >= 16) ++zs;
-        k4.zshift = zs;
-        k4.nbands = ((vd->nz - 1) >> zs) + 1;
+        packed_view(ctx, vd, packed, &k4);
         if (exact || !want_wave(ctx, n_pairs * D)) {
             st = launch_grouped3d(ctx, k4, pairs6, n_pairs, utab, D, ko, best_f, best_l,
                                   (hipStream_t)stream);
@@ -8976,6 +9131,56 @@ int uam_eval_generated3d_profiles_v(uam_ctx* ctx, const uam_volume_desc* vd, con
                                     double* climb_sum, uam_stream stream) {
     return eval_profiles(ctx, vd, vol, pairs6, n_pairs, utab, D, ztab, A, vert, true, out,
                          climb_sum, stream);
+}
+
+// The profiles on the packed, sorted volume (K4hp; K4h itself for the straight climb).  A sum
+// order of its own: sorted at every batch size or an error, never K4p / K4 / K4w.  Failures, in
+// order: an earlier call's device check; the context; the dimensions (profile_dims; n_pairs ==
+// 0 then returns UAM_OK); the descriptor; pairs6 / utab NULL; a selection without its output;
+// no packed_dev; misaligned buffers; the plan's refusals (grouped_plan3dp / grouped_plan3d);
+// UAM_E_STATE without a scale in the exact form.  All before any launch or allocation.
+int uam_eval_generated3d_profiles_h(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                                    const void* packed, const double* pairs6, int64_t n_pairs,
+                                    const double* utab, int32_t D, const double* ztab, int32_t A,
+                                    const uam_path_outputs* out, uam_stream stream) {
+    if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
+        const int st = device_status(ctx);
+        if (st) return st;
+    }
+    int st = check_ctx(ctx, true);
+    if (st) return st;
+    st = profile_dims(n_pairs, D, ztab, A);
+    if (st) return st;
+    if (n_pairs == 0) return UAM_OK;
+    KVolume kv;
+    st = make_kvolume(vd, &kv);
+    if (st) return st;
+    if (!pairs6 || !utab) return fail(UAM_E_INVALID, "pointer is NULL");
+    const KOut ko = make_kout(out);
+    int32_t* best_f = out ? out->best_fval_idx : nullptr;
+    int32_t* best_l = out ? out->best_length_idx : nullptr;
+    if ((best_f && !ko.cost) || (best_l && !ko.length))
+        return fail(UAM_E_INVALID,
+                    "best_fval_idx needs the cost output, best_length_idx the length output");
+    if (!packed)
+        return fail(UAM_E_INVALID, "uam_eval_generated3d_profiles_h needs K4hp: no packed_dev");
+    if ((uintptr_t)packed & 255) return fail(UAM_E_INVALID, "packed volume not 256-B aligned");
+    if (vol && ((uintptr_t)vol & 255))
+        return fail(UAM_E_INVALID, "volume buffer not 256-B aligned");
+    if (((uintptr_t)pairs6 & 15) || ((uintptr_t)utab & 15) || ((uintptr_t)ztab & 7))
+        return fail(UAM_E_INVALID, "pairs6_dev / utab_dev not 16-B or ztab_dev not 8-B aligned");
+    DeviceGuard dg(ctx->device);
+    KVol4 k4{};
+    packed_view(ctx, vd, packed, &k4);
+    if (!ztab)  // the straight climb: K4h's own kernels and bits (last_kernel "K4h+pack")
+        st = launch_grouped3d(ctx, k4, pairs6, n_pairs, utab, D, ko, best_f, best_l,
+                              (hipStream_t)stream, true);
+    else
+        st = launch_grouped3dp(ctx, k4, pairs6, n_pairs, utab, D, ztab, A, ko, best_f, best_l,
+                               (hipStream_t)stream);
+    if (st < 0) return st;
+    if (st != 1) return fail(UAM_E_INVALID, "uam_eval_generated3d_profiles_h: not taken");
+    return UAM_OK;
 }
 
 static int refine_memory(const uam_refine_params* rp) {

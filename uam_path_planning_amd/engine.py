@@ -549,6 +549,22 @@ class Engine:
         volume.sum_scale_version = volume.buf._version
         return volume
 
+    def _fresh_packed(self, volume, need=False):
+        """The derived copies K4h / K4hp read, brought up to date with volume.buf: the packed copy
+        rebuilt when torch's version counter moved since it was made (need: made when there is
+        none), and with the "exact_sum_volume" option on the volume's sum scale computed once per
+        voxel state and set on the context."""
+        if volume.packed is None:
+            if need:
+                self.volume_pack(volume)
+        elif volume.buf._version != volume.packed_version:
+            self.volume_pack(volume)   # the voxels changed since the copy: K4h reads only it
+        if self._exact_sum_volume:   # the exact sums' scale: computed once per voxel state
+            if volume.sum_scale is None or volume.buf._version != volume.sum_scale_version:
+                self.volume_sum_scale(volume)
+            _lib.check(self.lib.uam_set_volume_sum_scale(self._ctx, _ptr(volume.sum_scale)),
+                       "uam_set_volume_sum_scale")
+
     def eval_generated3d(self, pairs6, utab, volume, outputs=None):
         """pairs6 [Q, 6] = (x0, y0, z0, xf, yf, zf) (km, km, m); path p = q*D + d."""
         torch = _torch()
@@ -564,13 +580,7 @@ class Engine:
         else:
             o, s = self._outputs(Q * D, self.params.N + 2, _lib.MODE_VOLUME, False, False,
                                  n_pairs=Q)
-        if volume.packed is not None and volume.buf._version != volume.packed_version:
-            self.volume_pack(volume)   # the voxels changed since the copy: K4h reads only it
-        if self._exact_sum_volume:   # the exact sums' scale: computed once per voxel state
-            if volume.sum_scale is None or volume.buf._version != volume.sum_scale_version:
-                self.volume_sum_scale(volume)
-            _lib.check(self.lib.uam_set_volume_sum_scale(self._ctx, _ptr(volume.sum_scale)),
-                       "uam_set_volume_sum_scale")
+        self._fresh_packed(volume)
         _lib.check(self.lib.uam_eval_generated3d(
             self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf),
             _ptr(volume.packed), _ptr(pr), Q, _ptr(ut), D, ctypes.byref(s), self.stream),
@@ -645,13 +655,21 @@ class Engine:
         return o
 
     def eval_generated3d_profiles(self, pairs6, utab, ztab, volume, want_cells=False,
-                                  outputs=None, vertical=None):
+                                  outputs=None, vertical=None, packed=False):
         """eval_waypoints3d of gen_paths3d's waypoints in one kernel, with the selection over
         each pair's D*A candidates (uam_eval_generated3d_profiles): path p = (q*D + d)*A + a,
         best_fval_idx / best_length_idx [Q] hold the candidate c = d*A + a.  Reads volume.buf
         only.  vertical (a Vertical): the 3-D length, turn and climb rows
         (uam_eval_generated3d_profiles_v); the lengths and both selections then depend on the
-        profile, and the result holds climb_sum too."""
+        profile, and the result holds climb_sum too.
+        packed=True: the sorted form on volume.packed (uam_eval_generated3d_profiles_h, "K4hp":
+        grouped sums in UAM_OPT_GROUP order, the geometry in the similarity form, exact sums
+        with the "exact_sum_volume" option) at every batch size or a ValueError with its reason.
+        The copy is packed first when there is none and repacked when the voxels changed, by
+        eval_generated3d's rules.  It has no vertical form."""
+        if packed and vertical is not None:
+            raise ValueError("packed=True has no vertical form: the similarity-form geometry "
+                             "is not scale-free under the vertical terms")
         pr, ut, zt, Q, D, A = self._profile_inputs(pairs6, utab, ztab)
         W = self.params.N + 2
         if outputs is not None:
@@ -659,6 +677,13 @@ class Engine:
             _check_outputs(o, Q * D * A, Q, W)
         else:
             o, s = self._outputs(Q * D * A, W, _lib.MODE_VOLUME, want_cells, False, n_pairs=Q)
+        if packed:
+            self._fresh_packed(volume, need=True)
+            _lib.check(self.lib.uam_eval_generated3d_profiles_h(
+                self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf),
+                _ptr(volume.packed), _ptr(pr), Q, _ptr(ut), D, _ptr(zt), A, ctypes.byref(s),
+                self.stream), "uam_eval_generated3d_profiles_h")
+            return o
         if vertical is not None:
             climb = self._climb_sum(o, Q * D * A)
             _lib.check(self.lib.uam_eval_generated3d_profiles_v(

@@ -831,12 +831,62 @@ int uam_set_volume_sum_scale(uam_ctx* ctx, const int32_t* scale_dev);
  * blocks than the sort holds; a packed copy K4h stands aside for; packed_dev / vol_dev not
  * 256-B, pairs6_dev / utab_dev not 16-B or ztab_dev not 8-B aligned.  The sort's device check
  * applies as for K4h (uam_device_status).  The vertical terms have no such form (the similarity
- * form is not scale-free once the altitude differences enter the norm): there is no _v variant. */
+ * form is not scale-free once the altitude differences enter the norm): there is no _v variant
+ * of this definition; uam_eval_generated3d_profiles_hv below keeps the sorted sums and takes the
+ * geometry per path. */
 int uam_eval_generated3d_profiles_h(uam_ctx* ctx, const uam_volume_desc* desc,
                                     const void* vol_dev, const void* packed_dev,
                                     const double* pairs6_dev, int64_t n_pairs,
                                     const double* utab_dev, int32_t D, const double* ztab_dev,
                                     int32_t A, const uam_path_outputs* out, uam_stream stream);
+
+/* ---- Vertical terms for the profiles on the packed, sorted volume (K4hp+v) --------------------
+ * uam_eval_generated3d_profiles_h's sorted sums with uam_vertical's geometry: the call that both
+ * charges altitude changes and reads packed_dev.  The sort and the evaluation are K4hp's,
+ * unchanged (they never look at the geometry terms); the output launch walks each path's W
+ * waypoints once, sequentially, as uam_eval_generated3d_profiles_v does.  Arguments as
+ * uam_eval_generated3d_profiles_h, plus vert and climb_sum_dev [Q*D*A] (NULL: not wanted);
+ * uam_path_outputs does not grow.  vol_dev is not read (NULL is allowed).
+ *
+ * Definition (normative).  Layout as K4hp: p = (q*D + d)*A + a, c = d*A + a, 1 <= A <= 8,
+ * D <= 16.  Every float64 operation is rounded, none is contracted.  G = UAM_OPT_GROUP, W = N + 2.
+ *   points     K4hp's: x/y are uam_gen_paths3d's, z_j follows the table rule; ztab_dev == NULL
+ *              with A = 1 is the straight climb z0 + (zf - z0) * ((double)j / (double)(N+1)).
+ *   geometry   length_q, length, kin_sum and climb_sum are the uam_vertical loop above over those
+ *              points, sequentially, j = 1 .. N+1: the bits uam_eval_generated3d_profiles_v gives
+ *              for the same inputs.  They differ among the A profiles of a lateral candidate.
+ *   cost       K4hp's group order with the 3-D L as the base: cost = ((N+1) L + P_0) + P_1 + ...
+ *              with P_k as in K4hp's section.
+ *   nfz_sum, nfz_hits, offmap, below_terrain, min_clearance: K4hp's, bit for bit; the vertical
+ *              terms do not touch them.
+ *   selections uam_argmin's rule over the pair's D A candidates on the new cost and the new
+ *              length; best_length_idx need not be a multiple of A.
+ *   kappa = 0  with finite altitudes length_q, length and kin_sum equal
+ *              uam_eval_generated3d_profiles' sequential x/y bits (not K4hp's similarity-form
+ *              bits), and climb_sum is +0.
+ *   reporting  uam_last_group reports G; uam_last_kernel "K4hpv+pack" ("K4hpxv+pack": exact
+ *              form), with or without a table.
+ * Exact form: with UAM_OPT_EXACT_SUM_VOLUME = 1, cost = (double)(N+1) L + fl(S_risk) / (double)N
+ * and nfz_sum = fl(S_psi) as in K4hp's exact form; the bits then do not depend on G, the batch or
+ * the sharding.  UAM_E_STATE when no volume sum scale is set.
+ * Dispatch: as K4hp, sorted at every batch size or UAM_E_INVALID with its reason before any
+ * launch or allocation; a path's bits do not depend on the batch it is in.  The refusals are
+ * K4hp's, their messages prefixed "uam_eval_generated3d_profiles_hv needs K4hpv", with two
+ * differences: maxratio_smooth is taken (the sequential rows handle it as in
+ * uam_eval_generated3d_profiles_v), and UAM_OPT_K2G_SIM is not read (no similarity form is
+ * used).  vert is checked where uam_eval_generated3d_profiles_v checks it, after the context and
+ * before the dimensions: UAM_E_INVALID for vert == NULL, UAM_E_VERSION for a wrong abi_version,
+ * UAM_E_INVALID for a NaN, negative or infinite z_scale and for a NaN or negative sin_climb /
+ * sin_descent.  On a failed sort check (uam_device_status) climb_sum is NaN like the other
+ * float64 outputs. */
+int uam_eval_generated3d_profiles_hv(uam_ctx* ctx, const uam_volume_desc* desc,
+                                     const void* vol_dev, const void* packed_dev,
+                                     const double* pairs6_dev, int64_t n_pairs,
+                                     const double* utab_dev, int32_t D, const double* ztab_dev,
+                                     int32_t A, const uam_vertical* vert,
+                                     const uam_path_outputs* out,
+                                     double* climb_sum_dev /* [Q*D*A] or NULL */,
+                                     uam_stream stream);
 
 /* Workspace bytes uam_refine needs for n_paths (after uam_set_geometry/uam_set_params). */
 int64_t uam_refine_workspace_bytes(uam_ctx* ctx, int64_t n_paths,

@@ -8,7 +8,9 @@ of the work (A x Q x D paths through the same volume), not of the bits.  Last, t
 tables in the sorted form on the packed copy (K4hp, packed=True): one call that flies the
 profiles themselves and selects over D x A, where the K4h column is a stand-in.  Beside each fused
 form its form with the vertical terms (K4p+v: 3-D length, turn and climb rows per profile), and
-for A = 1 the explicit forms K4e / K4e+v on the same waypoints.
+for A = 1 the explicit forms K4e / K4e+v on the same waypoints.  --vertical alone times the
+calls that charge the climb side by side: K4p+v, then on the packed copy K4hp (no vertical
+terms), K4hp+v (eval_generated3d_profiles_hv) and K4hp+v's exact form.
 
 Times are HIP events on the launch stream around --steps calls after --warmup, the median of
 --repeats such windows.  One JSON line per measurement; needs an MI355X.
@@ -16,6 +18,7 @@ Times are HIP events on the launch stream around --steps calls after --warmup, t
     python tools/time_profiles.py                  # the table
     python tools/time_profiles.py --only-fused 8   # one fused form alone (for rocprofv3)
     python tools/time_profiles.py --only-fused 8 --vertical    # ... with the vertical terms
+    python tools/time_profiles.py --vertical       # K4p+v beside K4hp, K4hp+v and its exact form
 """
 import argparse
 import json
@@ -37,7 +40,8 @@ def main():
     ap.add_argument("--only-fused", type=int, default=0, metavar="A",
                     help="run only the fused call with A profiles (a profiler's target)")
     ap.add_argument("--vertical", action="store_true",
-                    help="with --only-fused: the form with the vertical terms (K4p+v)")
+                    help="with --only-fused: the form with the vertical terms (K4p+v); alone: "
+                         "the vertical comparison, K4p+v / K4hp / K4hp+v / K4hp+v exact")
     ap.add_argument("--pair-order", type=int, default=1, choices=(0, 1),
                     help="the pair_order option (K4 / K4p: pairs in a spatial order)")
     args = ap.parse_args()
@@ -109,12 +113,13 @@ def main():
         def fused_v():
             eng.eval_generated3d_profiles(pairs, ut, zt, volume, outputs=outs, vertical=vert)
 
-        if not (args.only_fused and args.vertical):
+        if not args.vertical:
             report("fused", A, timed(fused), eng.last_kernel())
         if not args.only_fused or args.vertical:
             report("fused+v", A, timed(fused_v), eng.last_kernel())
         del outs
-        if A == 1 and not args.only_fused:   # the explicit forms on the same waypoints
+        # the explicit forms on the same waypoints
+        if A == 1 and not args.only_fused and not args.vertical:
             wp3 = eng.gen_paths3d(pairs, ut, zt)
             eng.set_option("wave_max_paths", 0)
             report("explicit", A, timed(lambda: eng.eval_waypoints3d(wp3, volume)),
@@ -124,6 +129,27 @@ def main():
                    eng.last_kernel())
             del wp3
     if args.only_fused:
+        return
+    if args.vertical:   # the vertical comparison alone: K4p+v above, then K4hp, K4hp+v and its
+        #                 exact form on the packed copy
+        eng.volume_pack(volume)
+        for A in (1, 2, 4, 8):
+            zt = eng.tensor(profiles.stack(*[profiles.lift(N, h) for h in heights[:A]]),
+                            torch.float64)
+            outs = eng.outputs(Q * D * A, W, n_pairs=Q)
+
+            def packed():
+                eng.eval_generated3d_profiles(pairs, ut, zt, volume, outputs=outs, packed=True)
+
+            def packed_v():
+                eng.eval_generated3d_profiles_hv(pairs, ut, zt, volume, vert, outputs=outs)
+
+            report("packed", A, timed(packed), eng.last_kernel())
+            report("packed+v", A, timed(packed_v), eng.last_kernel())
+            eng.set_option("exact_sum_volume", 1)
+            report("packed+v exact", A, timed(packed_v), eng.last_kernel())
+            eng.set_option("exact_sum_volume", 0)
+            del outs
         return
 
     # the same work without sharing: A calls on pairs with shifted end altitudes

@@ -180,6 +180,11 @@ SIGNATURES = {
                                                        ctypes.c_int64, _vp, ctypes.c_int32, _vp,
                                                        ctypes.c_int32, ctypes.POINTER(Vertical),
                                                        ctypes.POINTER(PathOutputs), _vp, _vp]),
+    "uam_eval_generated3d_profiles_hv": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp,
+                                                        _vp, ctypes.c_int64, _vp, ctypes.c_int32,
+                                                        _vp, ctypes.c_int32,
+                                                        ctypes.POINTER(Vertical),
+                                                        ctypes.POINTER(PathOutputs), _vp, _vp]),
     "uam_volume_packed_bytes": (ctypes.c_int, [ctypes.POINTER(VolumeDesc),
                                                ctypes.POINTER(ctypes.c_int64)]),
     "uam_volume_pack": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp, _vp, _vp]),

@@ -36,12 +36,12 @@
 //   k4h.inc            K4h: k_volume_pack_planes k_volume_pack_t4 k_volume_codes k_v_hist
 //                      k_v_eval (k_v_eval_x) k_v_final k_v_final_x
 //   k4hp.inc           K4hp: k_vp_hist k_vp_eval (k_vp_eval_x) k_vp_final k_vp_final_x
-//                      k_vp_sel_check
+//                      k_vp_sel_check; K4hp+v: k_vp_final_v k_vp_final_xv
 //   struct uam_ctx and its helpers; then the C ABI (include/uampath.h) with the launches'
 //   static helpers between its entry points: context, geometry, params, K1; K2w launch; the
 //   option table; pair-order scratch and K2s launch; the grouped plan (K2g / K2h / K4h / K4hp);
-//   PackDims and eval_generated's dispatch; raster, volume, 3-D profile (K4hp's entry point
-//   among them), refinement, CRS, polygon and RCCL entry points.
+//   PackDims and eval_generated's dispatch; raster, volume, 3-D profile (K4hp's and K4hp+v's
+//   entry points among them), refinement, CRS, polygon and RCCL entry points.
 //
 // Numerics: float64 throughout, compiled with -ffp-contract=off so every product and sum is a
 // separately rounded IEEE operation in the reference's order (problem.py, quadratic_obstacle.py,
@@ -7784,6 +7784,35 @@ static void grouped_final(uam_ctx* ctx, const GPlan& pl, const KOut& ko, int32_t
         hipLaunchKernelGGL(pl.fin, grid, dim3(64 * D), lds, s, ctx->kp, pl.kg, ko, best_f, best_l);
 }
 
+// K4hp's and K4hp+v's: one thread per path (vert: the sequential 3-D geometry, k_vp_final_v /
+// k_vp_final_xv), then uam_argmin's rule over the pair's C = D * A candidates, as K4p, and the
+// sort check's mark on the selections
+static void profile_final(uam_ctx* ctx, const GPlan& pl, const KProf& kf, const KVert* vert,
+                          const KOut& ko, int32_t* best_f, int32_t* best_l, int32_t C,
+                          hipStream_t s) {
+    const KGrp& kg = pl.kg;
+    const int64_t n_pairs = kg.n_pairs;
+    const dim3 gfin((unsigned)(((int64_t)kg.P + 255) / 256));
+    if (vert && pl.exact)
+        hipLaunchKernelGGL(k_vp_final_xv, gfin, dim3(256), 0, s, ctx->kp, kg, kf, *vert, ko,
+                           pl.scale);
+    else if (vert)
+        hipLaunchKernelGGL(k_vp_final_v, gfin, dim3(256), 0, s, ctx->kp, kg, kf, *vert, ko);
+    else if (pl.exact)
+        hipLaunchKernelGGL(k_vp_final_x, gfin, dim3(256), 0, s, ctx->kp, kg, kf, ko, pl.scale);
+    else
+        hipLaunchKernelGGL(k_vp_final, gfin, dim3(256), 0, s, ctx->kp, kg, kf, ko);
+    if (best_f || best_l) {
+        const dim3 g2(grid_for(n_pairs, 256, INT32_MAX));
+        if (best_f)
+            hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.cost, n_pairs, C, 1, best_f);
+        if (best_l)
+            hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.length, n_pairs, C, 0, best_l);
+        hipLaunchKernelGGL(k_vp_sel_check, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0,
+                           s, kg.err, n_pairs, best_f, best_l);
+    }
+}
+
 // K2g launch (segment-grouped raster evaluation); returns 1 if launched, 0 if the batch is not
 // one it takes (the caller runs K2s / K2).  Needs the packed raster.  Scratch: the pair-order
 // scratch (order_scratch), so two streams sharing the context serialise on it.
@@ -7862,14 +7891,17 @@ static int launch_grouped(uam_ctx* ctx, const KRaster& kr, const void* rec, cons
 
 // What K4h and K4hp both refuse, in the order a caller sees it (one list, so the two plans do
 // not diverge): the reason, or null.  (UAM_OPT_GROUP is at most G_MAXLEN by the option table.)
-static const char* volume_refusal(const uam_ctx* ctx, const KVol4& kv, const KOut& ko, int32_t D) {
+// vert (K4hp+v): the geometry comes from the sequential rows of the output launch, which take
+// maxratio_smooth, and no similarity form is used, so UAM_OPT_K2G_SIM is not read.
+static const char* volume_refusal(const uam_ctx* ctx, const KVol4& kv, const KOut& ko, int32_t D,
+                                  bool vert = false) {
     const int G = ctx->k2g_group;
     if (G < 1) return "UAM_OPT_GROUP is 0";
     if (G > G_MAXLEN) return "UAM_OPT_GROUP exceeds the longest group";
     if (ko.cells || ko.g_rows) return "cells or g_rows requested";
     if (D > 16) return "D > 16";
-    if (ctx->kp.maxratio_smooth) return "maxratio_smooth is set";
-    if (!ctx->k2g_sim) return "UAM_OPT_K2G_SIM is 0";
+    if (!vert && ctx->kp.maxratio_smooth) return "maxratio_smooth is set";
+    if (!vert && !ctx->k2g_sim) return "UAM_OPT_K2G_SIM is 0";
     if (!kv.pk) return "the packed copy is 4 GiB or larger, or a layer or side holds 2^24 entries";
     if (ctx->kp.N > 4096) return "N > 4096";
     return nullptr;
@@ -7878,18 +7910,19 @@ static const char* volume_refusal(const uam_ctx* ctx, const KVol4& kv, const KOu
 // the sequence a volume batch takes (K4h): as grouped_plan
 static int grouped_plan3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
                           const double* utab, int32_t D, const KOut& ko, GPlan* pl,
-                          bool must = false) {
+                          bool must = false, bool vert = false) {
     const int G = ctx->k2g_group;
     const bool exact = ctx->exact_sum_vol != 0;
     *pl = GPlan{};
     pl->vol = pl->sim = true;
     pl->exact = exact;
     pl->must = must;
-    pl->needs = must ? "uam_eval_generated3d_profiles_h needs K4h"
-                     : "UAM_OPT_EXACT_SUM_VOLUME needs K4h";
+    pl->needs = vert   ? "uam_eval_generated3d_profiles_hv needs K4hpv"
+                : must ? "uam_eval_generated3d_profiles_h needs K4h"
+                       : "UAM_OPT_EXACT_SUM_VOLUME needs K4h";
     pl->scale = exact ? ctx->vol_sum_scale : nullptr;
     auto no = [&](const char* why) { return grouped_no(*pl, why); };
-    if (const char* why = volume_refusal(ctx, kv, ko, D)) return no(why);
+    if (const char* why = volume_refusal(ctx, kv, ko, D, vert)) return no(why);
     if (!exact && !must && n_pairs * D < ctx->k2s_min) return 0;
     if (n_pairs > INT32_MAX / D) return no("more than 2^31 paths");
     const size_t ubytes = (size_t)D * ctx->kp.N * 16;
@@ -7941,11 +7974,14 @@ static int grouped_plan3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, i
 // UAM_OPT_EXACT_SUM_VOLUME: the exact form (k_v_eval_x / k_v_final_x, 48-B slots) at every batch
 // size; it never stands aside for another sum order, so a batch K4h does not take is an error
 // with its reason, raised before any launch.
+// vert (uam_eval_generated3d_profiles_hv with no table): the sort and k_v_eval as they are, then
+// K4hp+v's output launch on the straight climb in place of k_v_final.
 static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
                             const double* utab, int32_t D, const KOut& ko, int32_t* best_f,
-                            int32_t* best_l, hipStream_t s, bool must = false) {
+                            int32_t* best_l, hipStream_t s, bool must = false,
+                            const KVert* vert = nullptr) {
     GPlan pl;
-    int st = grouped_plan3d(ctx, kv, pairs6, n_pairs, utab, D, ko, &pl, must);
+    int st = grouped_plan3d(ctx, kv, pairs6, n_pairs, utab, D, ko, &pl, must, vert != nullptr);
     if (st <= 0) return st;
     if (pl.exact && !pl.scale)
         return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM_VOLUME is on and no volume sum scale is set "
@@ -7968,12 +8004,20 @@ static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6,
     }
     grouped_sort(ctx, pl, volume_hist, &kv, s);
     grouped_eval(ctx, pl, kv, s);
-    grouped_final(ctx, pl, ko, best_f, best_l, s);
+    if (vert) {
+        KProf kf{};  // no table: one profile, the straight climb
+        kf.A = 1;
+        magic_div(1u, &kf.m_a, &kf.sh_a);
+        profile_final(ctx, pl, kf, vert, ko, best_f, best_l, D, s);
+    } else {
+        grouped_final(ctx, pl, ko, best_f, best_l, s);
+    }
     if (hipGetLastError() != hipSuccess) return fail(UAM_E_HIP, "grouped volume evaluation launch");
     st = ktime_end(ctx, s);
     if (st) return st;
     ctx->last_group = pl.kg.G;
-    ctx->last_kernel = pl.exact ? "K4hx+pack" : "K4h+pack";
+    ctx->last_kernel = vert ? (pl.exact ? "K4hpxv+pack" : "K4hpv+pack")
+                            : pl.exact ? "K4hx+pack" : "K4h+pack";
     st = order_done(ctx, s);
     return st ? st : 1;
 }
@@ -7995,17 +8039,18 @@ static void volume_profile_hist(uam_ctx* ctx, const KGrp& kg, const void* g, siz
 
 static int grouped_plan3dp(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
                            const double* utab, int32_t D, int32_t A, const KOut& ko, GPlan* pl,
-                           VPEvalFn* vpev) {
+                           VPEvalFn* vpev, bool vert = false) {
     const int G = ctx->k2g_group;
     const bool exact = ctx->exact_sum_vol != 0;
     *pl = GPlan{};
     pl->vol = pl->sim = true;
     pl->exact = exact;
     pl->must = true;
-    pl->needs = "uam_eval_generated3d_profiles_h needs K4hp";
+    pl->needs = vert ? "uam_eval_generated3d_profiles_hv needs K4hpv"
+                     : "uam_eval_generated3d_profiles_h needs K4hp";
     pl->scale = exact ? ctx->vol_sum_scale : nullptr;
     auto no = [&](const char* why) { return grouped_no(*pl, why); };
-    if (const char* why = volume_refusal(ctx, kv, ko, D)) return no(why);
+    if (const char* why = volume_refusal(ctx, kv, ko, D, vert)) return no(why);
     const int64_t W = ctx->kp.N + 2, npad = G + 16;  // k_vp_eval's padding slots
     const size_t ubytes = (size_t)D * ctx->kp.N * 16;
     if (ubytes > (size_t)G_UTAB_LDS) return no("the unit-arc table exceeds its LDS share");
@@ -8048,10 +8093,12 @@ static int grouped_plan3dp(uam_ctx* ctx, const KVol4& kv, const double* pairs6, 
 
 static int launch_grouped3dp(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
                              const double* utab, int32_t D, const double* ztab, int32_t A,
-                             const KOut& ko, int32_t* best_f, int32_t* best_l, hipStream_t s) {
+                             const KOut& ko, int32_t* best_f, int32_t* best_l, hipStream_t s,
+                             const KVert* vert = nullptr) {
     GPlan pl;
     VPEvalFn vpev = nullptr;
-    int st = grouped_plan3dp(ctx, kv, pairs6, n_pairs, utab, D, A, ko, &pl, &vpev);
+    int st = grouped_plan3dp(ctx, kv, pairs6, n_pairs, utab, D, A, ko, &pl, &vpev,
+                             vert != nullptr);
     if (st <= 0) return st;
     if (pl.exact && !pl.scale)
         return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM_VOLUME is on and no volume sum scale is set "
@@ -8081,28 +8128,14 @@ static int launch_grouped3dp(uam_ctx* ctx, const KVol4& kv, const double* pairs6
     grouped_sort(ctx, pl, volume_profile_hist, &vg, s);
     hipLaunchKernelGGL(vpev, dim3((unsigned)((kg.n_items + pl.bs - 1) / pl.bs)), dim3(pl.bs),
                        pl.lds, s, ctx->kp, vg.kv, kg, vg.kf);
-    const dim3 gfin((unsigned)(((int64_t)kg.P + 255) / 256));
-    if (pl.exact)
-        hipLaunchKernelGGL(k_vp_final_x, gfin, dim3(256), 0, s, ctx->kp, kg, vg.kf, ko, pl.scale);
-    else
-        hipLaunchKernelGGL(k_vp_final, gfin, dim3(256), 0, s, ctx->kp, kg, vg.kf, ko);
-    // uam_argmin's rule over the pair's D * A candidates, as K4p
-    if (best_f || best_l) {
-        const dim3 g2(grid_for(n_pairs, 256, INT32_MAX));
-        if (best_f)
-            hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.cost, n_pairs, D * A, 1, best_f);
-        if (best_l)
-            hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.length, n_pairs, D * A, 0,
-                               best_l);
-        hipLaunchKernelGGL(k_vp_sel_check, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0,
-                           s, kg.err, n_pairs, best_f, best_l);
-    }
+    profile_final(ctx, pl, vg.kf, vert, ko, best_f, best_l, D * A, s);
     if (hipGetLastError() != hipSuccess)
         return fail(UAM_E_HIP, "grouped volume profile evaluation launch");
     st = ktime_end(ctx, s);
     if (st) return st;
     ctx->last_group = kg.G;
-    ctx->last_kernel = pl.exact ? "K4hpx+pack" : "K4hp+pack";
+    ctx->last_kernel = vert ? (pl.exact ? "K4hpxv+pack" : "K4hpv+pack")
+                            : pl.exact ? "K4hpx+pack" : "K4hp+pack";
     st = order_done(ctx, s);
     return st ? st : 1;
 }
@@ -9139,16 +9172,26 @@ int uam_eval_generated3d_profiles_v(uam_ctx* ctx, const uam_volume_desc* vd, con
 // 0 then returns UAM_OK); the descriptor; pairs6 / utab NULL; a selection without its output;
 // no packed_dev; misaligned buffers; the plan's refusals (grouped_plan3dp / grouped_plan3d);
 // UAM_E_STATE without a scale in the exact form.  All before any launch or allocation.
-int uam_eval_generated3d_profiles_h(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
-                                    const void* packed, const double* pairs6, int64_t n_pairs,
-                                    const double* utab, int32_t D, const double* ztab, int32_t A,
-                                    const uam_path_outputs* out, uam_stream stream) {
+// with_vert: uam_eval_generated3d_profiles_hv (K4hp+v), the same sorted sums with the geometry
+// per path under the vertical terms; vert is checked after the context, as K4p+v's, and the
+// refusals name that call.
+static int eval_profiles_h(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                           const void* packed, const double* pairs6, int64_t n_pairs,
+                           const double* utab, int32_t D, const double* ztab, int32_t A,
+                           const uam_vertical* vert, bool with_vert, const uam_path_outputs* out,
+                           double* climb, uam_stream stream) {
     if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
         const int st = device_status(ctx);
         if (st) return st;
     }
     int st = check_ctx(ctx, true);
     if (st) return st;
+    KVert kvert{};
+    if (with_vert) {
+        st = vertical_view(vert, climb, &kvert);
+        if (st) return st;
+    }
+    const KVert* kvp = with_vert ? &kvert : nullptr;
     st = profile_dims(n_pairs, D, ztab, A);
     if (st) return st;
     if (n_pairs == 0) return UAM_OK;
@@ -9163,7 +9206,9 @@ int uam_eval_generated3d_profiles_h(uam_ctx* ctx, const uam_volume_desc* vd, con
         return fail(UAM_E_INVALID,
                     "best_fval_idx needs the cost output, best_length_idx the length output");
     if (!packed)
-        return fail(UAM_E_INVALID, "uam_eval_generated3d_profiles_h needs K4hp: no packed_dev");
+        return fail(UAM_E_INVALID, "%s: no packed_dev",
+                    with_vert ? "uam_eval_generated3d_profiles_hv needs K4hpv"
+                              : "uam_eval_generated3d_profiles_h needs K4hp");
     if ((uintptr_t)packed & 255) return fail(UAM_E_INVALID, "packed volume not 256-B aligned");
     if (vol && ((uintptr_t)vol & 255))
         return fail(UAM_E_INVALID, "volume buffer not 256-B aligned");
@@ -9172,15 +9217,33 @@ int uam_eval_generated3d_profiles_h(uam_ctx* ctx, const uam_volume_desc* vd, con
     DeviceGuard dg(ctx->device);
     KVol4 k4{};
     packed_view(ctx, vd, packed, &k4);
-    if (!ztab)  // the straight climb: K4h's own kernels and bits (last_kernel "K4h+pack")
+    if (!ztab)  // the straight climb: K4h's own kernels and bits (last_kernel "K4h+pack");
+                // with_vert: K4h's sort and evaluation, K4hp+v's output launch
         st = launch_grouped3d(ctx, k4, pairs6, n_pairs, utab, D, ko, best_f, best_l,
-                              (hipStream_t)stream, true);
+                              (hipStream_t)stream, true, kvp);
     else
         st = launch_grouped3dp(ctx, k4, pairs6, n_pairs, utab, D, ztab, A, ko, best_f, best_l,
-                               (hipStream_t)stream);
+                               (hipStream_t)stream, kvp);
     if (st < 0) return st;
     if (st != 1) return fail(UAM_E_INVALID, "uam_eval_generated3d_profiles_h: not taken");
     return UAM_OK;
+}
+
+int uam_eval_generated3d_profiles_h(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                                    const void* packed, const double* pairs6, int64_t n_pairs,
+                                    const double* utab, int32_t D, const double* ztab, int32_t A,
+                                    const uam_path_outputs* out, uam_stream stream) {
+    return eval_profiles_h(ctx, vd, vol, packed, pairs6, n_pairs, utab, D, ztab, A, nullptr, false,
+                           out, nullptr, stream);
+}
+
+int uam_eval_generated3d_profiles_hv(uam_ctx* ctx, const uam_volume_desc* vd, const void* vol,
+                                     const void* packed, const double* pairs6, int64_t n_pairs,
+                                     const double* utab, int32_t D, const double* ztab, int32_t A,
+                                     const uam_vertical* vert, const uam_path_outputs* out,
+                                     double* climb_sum, uam_stream stream) {
+    return eval_profiles_h(ctx, vd, vol, packed, pairs6, n_pairs, utab, D, ztab, A, vert, true,
+                           out, climb_sum, stream);
 }
 
 static int refine_memory(const uam_refine_params* rp) {

@@ -383,8 +383,9 @@ class Engine:
         """Which path evaluation the last eval_generated / eval_generated3d ran (uam_last_kernel:
         "K2h+pack", "K2hx+pack" (the exact sums), "K2g+pack", "K4h+pack", "K4hx+pack" (the
         volume's exact sums), "K2s+pack", "K2+skip", "K2w", "K3b", ...), or the last
-        eval_waypoints3d ("K4e" / "K4ew") / eval_generated3d_profiles ("K4p"); with vertical=
-        "K4e+v" / "K4ew+v" / "K4p+v"."""
+        eval_waypoints3d ("K4e" / "K4ew") / eval_generated3d_profiles ("K4p"; packed=True:
+        "K4hp+pack", "K4hpx+pack" with the exact sums); with vertical= "K4e+v" / "K4ew+v" /
+        "K4p+v"; eval_generated3d_profiles_hv: "K4hpv+pack", "K4hpxv+pack" with the exact sums."""
         return self.lib.uam_last_kernel(self._ctx).decode()
 
     def last_group(self):
@@ -666,10 +667,13 @@ class Engine:
         grouped sums in UAM_OPT_GROUP order, the geometry in the similarity form, exact sums
         with the "exact_sum_volume" option) at every batch size or a ValueError with its reason.
         The copy is packed first when there is none and repacked when the voxels changed, by
-        eval_generated3d's rules.  It has no vertical form."""
+        eval_generated3d's rules.  It has no vertical form: eval_generated3d_profiles_hv is the
+        sorted call with the vertical terms, a definition of its own."""
         if packed and vertical is not None:
             raise ValueError("packed=True has no vertical form: the similarity-form geometry "
-                             "is not scale-free under the vertical terms")
+                             "is not scale-free under the vertical terms; "
+                             "eval_generated3d_profiles_hv keeps the sorted sums and takes the "
+                             "geometry per path")
         pr, ut, zt, Q, D, A = self._profile_inputs(pairs6, utab, ztab)
         W = self.params.N + 2
         if outputs is not None:
@@ -695,6 +699,36 @@ class Engine:
             self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf), _ptr(pr), Q,
             _ptr(ut), D, _ptr(zt), A, ctypes.byref(s), self.stream),
             "uam_eval_generated3d_profiles")
+        return o
+
+    def eval_generated3d_profiles_hv(self, pairs6, utab, ztab, volume, vertical, outputs=None):
+        """The altitude-profile candidates on volume.packed with the vertical terms
+        (uam_eval_generated3d_profiles_hv, "K4hpv+pack"; "K4hpxv+pack" with the
+        "exact_sum_volume" option): eval_generated3d_profiles(packed=True)'s sort, gathers and
+        grouped (or exact) sums, with length_q, length, kin_sum and climb_sum formed per path
+        under vertical (a Vertical) as eval_generated3d_profiles(vertical=) forms them, and both
+        selections over each pair's D*A candidates on the new cost and length.  Sorted at every
+        batch size or a ValueError with its reason; maxratio_smooth is taken and the "k2g_sim"
+        option is not read.  ztab=None: A = 1, the straight climb.  The copy is packed first when
+        there is none and repacked when the voxels changed, by eval_generated3d's rules.  Returns
+        the usual dict plus climb_sum (outputs["climb_sum"] when the caller provides one)."""
+        if vertical is None:
+            raise ValueError("eval_generated3d_profiles_hv needs a Vertical; without one the "
+                             "call is eval_generated3d_profiles(..., packed=True)")
+        pr, ut, zt, Q, D, A = self._profile_inputs(pairs6, utab, ztab)
+        W = self.params.N + 2
+        if outputs is not None:
+            o, s = outputs
+            _check_outputs(o, Q * D * A, Q, W)
+        else:
+            o, s = self._outputs(Q * D * A, W, _lib.MODE_VOLUME, False, False, n_pairs=Q)
+        climb = self._climb_sum(o, Q * D * A)
+        self._fresh_packed(volume, need=True)
+        _lib.check(self.lib.uam_eval_generated3d_profiles_hv(
+            self._ctx, ctypes.byref(volume.geo.as_struct()), _ptr(volume.buf),
+            _ptr(volume.packed), _ptr(pr), Q, _ptr(ut), D, _ptr(zt), A,
+            ctypes.byref(vertical.as_struct()), ctypes.byref(s), _ptr(climb), self.stream),
+            "uam_eval_generated3d_profiles_hv")
         return o
 
     def gen_paths(self, pairs, utab):

@@ -147,11 +147,11 @@ def min_area_rect(points):
     return box.reshape(4, 2)
 
 
-def dem_polygons(dem, rdesc, threshold=0.0, unit=1000.0, pp=None):
-    """load_dem_polygons_from_geotiff + process_polygons -> [n, 4, 2] int64 rectangles."""
+def dem_polygons(dem, rdesc, threshold=0.0, unit=1000.0, pp=None, cap=4096):
+    """load_dem_polygons_from_geotiff + process_polygons -> [n, 4, 2] int64 rectangles
+    (at most cap of them)."""
     d = np.ascontiguousarray(dem, dtype=np.float32)
     pp = pp or polyproc()
-    cap = 4096
     out = np.zeros((cap, 4, 2), np.int64)
     n = lib().orc_dem_polygons(_ptr(d, _f32p), ctypes.byref(rdesc), ctypes.c_float(threshold),
                                ctypes.c_double(unit), ctypes.byref(pp),

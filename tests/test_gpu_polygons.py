@@ -1,7 +1,10 @@
 """GPU land polygons (K8, uam_dem_polygons) against the oracle
 (orc_dem_polygons): rectangles and their order bit-exact (integer metres).  The oracle is pinned
 through test_polygons_cpu.py (its cv2 restatement on the reference's populated_area output, and
-the DEM route == the vector route on exact polygons)."""
+the DEM route == the vector route on exact polygons) and test_polygons_topology_cpu.py (its
+labelling against the flood-fill reference of polygons_ref.py).  The masks here are smooth
+terrain; the labelling on adversarial masks (polygons_masks.py: checkerboard, spiral, rings,
+noise, all 512 tile-corner patterns, cuts at tile edges) is in test_gpu_polygons_topology.py."""
 import numpy as np
 import pytest
 

@@ -27,5 +27,6 @@ ASAN_OPTIONS=detect_leaks=0:halt_on_error=1:verify_asan_link_order=0 \
 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 UAM_LIB_PATH=$OUT/libuampath.so UAM_ORACLE_LIB=$OUT/liboracle.so \
 python -m pytest -x -q -p no:cacheprovider -m "not gpu" \
-    tests/test_polygons_cpu.py tests/test_oracle_golden.py tests/test_refine_cpu.py \
+    tests/test_polygons_cpu.py tests/test_polygons_topology_cpu.py \
+    tests/test_oracle_golden.py tests/test_refine_cpu.py \
     tests/test_crs_cpu.py tests/test_host_cpu.py tests/test_map_generation_cpu.py "$@"

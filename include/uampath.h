@@ -575,7 +575,8 @@ int uam_kernel_time(uam_ctx* ctx, double* ms_total, int64_t* launches);
  * (lane per path), "K2w" (wave per path), "K2d" (D > 16), "K3b", "K3", "K3d", "K4", "K4w";
  * "K4e" / "K4ew" (uam_eval_waypoints3d lane / wave per path), "K4p"
  * (uam_eval_generated3d_profiles), "K4e+v" / "K4ew+v" / "K4p+v" (their _v forms with the
- * vertical terms); "" before the first call.  The string is static (never freed).  For benchmarks and tests:
+ * vertical terms); "K9" (uam_route_field) / "K9t" (uam_route_paths); "" before the first call.
+ * The string is static (never freed).  For benchmarks and tests:
  * which kernel a number belongs to. */
 const char* uam_last_kernel(const uam_ctx* ctx);
 
@@ -680,6 +681,12 @@ enum {
     UAM_OPT_EXACT_SUM = 23,       /* 0 (default) / 1: exact, order-independent raster sums (below) */
     UAM_OPT_EXACT_SUM_VOLUME = 24 /* 0 (default) / 1: the same for the volume, K4h (below) */
 };
+/* The route seeds' two options ("Route seeds" below) are keys of uam_set_option / uam_get_option
+ * like the ones above, kept apart from the evaluation options' list (25 and 26 stay
+ * unassigned): the tile edge in cells, 16, 32 (default) or 64, and the sweeps inside a tile per
+ * round, 1..256 (default 16).  No output depends on either. */
+#define UAM_OPT_K9_TILE 27
+#define UAM_OPT_K9_INNER 28
 int uam_set_option(uam_ctx* ctx, int32_t option, int64_t value);
 int uam_get_option(const uam_ctx* ctx, int32_t option, int64_t* value);
 
@@ -887,6 +894,115 @@ int uam_eval_generated3d_profiles_hv(uam_ctx* ctx, const uam_volume_desc* desc,
                                      const uam_path_outputs* out,
                                      double* climb_sum_dev /* [Q*D*A] or NULL */,
                                      uam_stream stream);
+
+/* ---- Route seeds (K9): cost-to-go field of a goal and traced paths on the record raster ------
+ * Every candidate the calls above score or refine is one of the D circular arcs.  These calls
+ * give a path of another shape: the cheapest 8-connected route over the raster's cells from any
+ * start to a goal, resampled to the N+2 waypoints uam_eval_waypoints and uam_refine take.  One
+ * field serves every query that shares the goal: uam_route_field is a per-goal SETUP call like
+ * uam_raster_pack (it may synchronise the stream: the host reads a convergence word between
+ * rounds), uam_route_paths is asynchronous.
+ *
+ * Definition (normative; independent statement: tests/route_ref.py).  Every float64 operation
+ * is rounded separately, in the order written (no fused multiply-add).
+ *   cells      a point maps to a cell by uam_raster_desc's rule; the centre of cell (ix, iy) is
+ *              (x0 + (ix + 0.5)*dx, y_top - (iy + 0.5)*dy).  Directions k = 0..7 are
+ *              (dix, diy) = E(1,0), NE(1,-1), N(0,-1), NW(-1,-1), W(-1,0), SW(-1,1), S(0,1),
+ *              SE(1,1); step lengths L_k = dx (E/W), dy (N/S), sqrt(dx*dx + dy*dy) (diagonals).
+ *   cell cost  c_v = 1.0 + lambda * (double)phi_v (the record's float32 phi).  A cell is
+ *              blocked0 when (flags_v & block_flags) != 0, or c_v is not finite, or c_v is not
+ *              > 0 (NaN, +-inf and very negative phi all land here).  A cell is blocked when a
+ *              blocked0 cell lies within Chebyshev distance inflate of it (cells outside the
+ *              raster do not count); inflate = 0: blocked = blocked0.  Otherwise it is free.
+ *   edges      between free neighbours u, v in one of the 8 directions; a diagonal step also
+ *              needs both cells orthogonally adjacent to it free (a one-cell-wide diagonal wall
+ *              is a wall; no path cuts a corner).  w(u,v) = (0.5 * (c_u + c_v)) * L_k, symmetric.
+ *   field      for a goal point with cell g: dist[g] = 0 when g is on the raster and free;
+ *              elsewhere dist[v] = the minimum over edge paths g = v_0, .., v_n = v of the left
+ *              fold fl(fl(fl(0 + w_01) + w_12) + ..); +inf for blocked and unreachable cells,
+ *              and everywhere when g is blocked or off the raster.  fl(a + w) is monotone in a,
+ *              so this minimum is the one fixed point of d[v] = min(d[v], fl(d[u] + w(u,v)))
+ *              started from +inf / 0: the bits do not depend on the relaxation order, the tile
+ *              edge or the sweeps per round.
+ *   next hop   uint8 per cell, formed after convergence: 8 at the goal cell, 255 where dist is
+ *              +inf, else the lowest k whose neighbour u_k = v + (dix, diy)_k has an edge to v
+ *              with fl(dist[u_k] + w(u_k, v)) == dist[v].
+ *   path       for a query (start point, goal index): status, tested in this order,
+ *                4  the goal index is outside [0, n_goals), or the goal is off the raster or
+ *                   blocked;
+ *                1  the start is off the raster or in a blocked cell;
+ *                2  the goal is unreachable from the start's cell s (dist[s] = +inf, g free);
+ *                3  the walk along next from s visited nx*ny cells without reaching g (possible
+ *                   only when huge costs absorb small weights and equal dist values form a
+ *                   cycle; also a next value that is no direction or leads off the raster, which
+ *                   uam_route_field never writes);
+ *                0  ok.
+ *              steps = the number of cells the walk visited, s and g included (1 when s = g); 0
+ *              for a nonzero status.  Vertices: V_0 = the start point itself, then the centres
+ *              of the visited cells strictly between s and g, V_m = the goal point itself (s = g
+ *              or adjacent cells: the straight segment, m = 1).  S_0 = 0, S_i = S_{i-1} +
+ *              sqrt(ex*ex + ey*ey) with e = V_i - V_{i-1}, sequentially.  Waypoints p_0 = V_0 and
+ *              p_{N+1} = V_m, copied; for j = 1..N: t = S_m * ((double)j / (double)(N+1)); i =
+ *              the first index >= the previous waypoint's i (1 at j = 1) with S_i > t, m if there
+ *              is none; u = (t - S_{i-1}) / (S_i - S_{i-1}), 0 if the denominator is not > 0;
+ *              p_j = V_{i-1} + u * (V_i - V_{i-1}) per component.  By the corner rule every
+ *              waypoint of a status-0 path lies in a free cell.  For a nonzero status the
+ *              waypoints are the straight line p_j = start + (goal - start) * ((double)j /
+ *              (double)(N+1)) with the end points copied (a goal index out of range: every
+ *              waypoint is the start point), so a downstream call never reads garbage.
+ *
+ * uam_route_params: lambda finite and >= 0; inflate 0..8; max_rounds >= 0 bounds the relaxation
+ * rounds of one goal, 0 = nx*ny (each round settles at least the cells whose best path crosses
+ * one more tile border than the round before).
+ * uam_route_field: the fields of n_goals goals (goals_dev [n_goals][2]) into dist_dev
+ * [n_goals][ny][nx] f64 and next_dev [n_goals][ny][nx] u8; workspace_dev holds
+ * uam_route_workspace_bytes(desc, params) bytes, 256-B aligned (the cost plane, shared by the
+ * goals, and the active-tile sets).  The goals are relaxed one after the other: label-correcting
+ * rounds over the set of active tiles, one ordinary launch per round, the host reading the next
+ * round's tile count after each.  rounds_out (host, may be NULL): the rounds of all goals
+ * together; uam_route_visits: the tiles those rounds visited.  uam_last_kernel: "K9".
+ * Failures: UAM_E_INVALID before any launch or allocation for ctx / desc / params / a buffer
+ * NULL, a bad descriptor, lambda NaN, infinite or negative, inflate outside [0, 8], max_rounds
+ * < 0, n_goals < 1 or n_goals * nx * ny >= 2^40, a workspace too small or misaligned;
+ * UAM_E_VERSION for a wrong abi_version; UAM_E_STATE, the message naming max_rounds, when a field
+ * has not converged within max_rounds rounds -- the outputs are then unspecified and the context
+ * stays usable.
+ * uam_route_paths: Q queries (starts_dev [Q][2], goal_idx_dev [Q]) against next_dev as
+ * uam_route_field wrote it for the same desc, rec_dev, params (the start's blocking is read from
+ * rec_dev) and goals_dev, into wp_dev [Q][N+2][2], status_dev [Q] and steps_dev [Q] (or NULL);
+ * N from uam_set_params (UAM_E_STATE without it).  One lane per query, two sequential walks
+ * bounded by nx*ny steps: seed generation, not a per-step call.  uam_last_kernel: "K9t".
+ * The _host calls take host pointers and run, without a GPU, the same inline functions as the
+ * kernels (cell cost, blocking, edge weight, next-hop choice, trace and resample; the field's
+ * minimum by a heap Dijkstra).
+ * UAM_OPT_K9_TILE (16, 32 (default), 64) and UAM_OPT_K9_INNER (1..256) choose the tile edge and
+ * the sweeps inside a tile per round; no output depends on them (rounds and visits do). */
+typedef struct {
+    uint32_t abi_version; /* UAM_ABI_VERSION */
+    double lambda;        /* weight of phi in the cell cost; finite, >= 0 */
+    uint32_t block_flags; /* UAM_FLAG_* bits that block a cell */
+    int32_t inflate;      /* cells of clearance around a blocked0 cell, 0..8 */
+    int32_t max_rounds;   /* 0 = nx*ny */
+} uam_route_params;
+int64_t uam_route_workspace_bytes(const uam_raster_desc* desc, const uam_route_params* params);
+int uam_route_field(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec_dev,
+                    const uam_route_params* params, const double* goals_dev, int32_t n_goals,
+                    double* dist_dev, uint8_t* next_dev, void* workspace_dev,
+                    int64_t workspace_bytes, int32_t* rounds_out, uam_stream stream);
+int64_t uam_route_visits(const uam_ctx* ctx);
+int uam_route_paths(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec_dev,
+                    const uam_route_params* params, const uint8_t* next_dev,
+                    const double* goals_dev, int32_t n_goals, const double* starts_dev,
+                    const int32_t* goal_idx_dev, int64_t n_queries, double* wp_dev,
+                    int32_t* status_dev, int32_t* steps_dev, uam_stream stream);
+int uam_route_field_host(const uam_raster_desc* desc, const void* rec,
+                         const uam_route_params* params, const double* goals, int32_t n_goals,
+                         double* dist, uint8_t* next);
+int uam_route_paths_host(const uam_raster_desc* desc, const void* rec,
+                         const uam_route_params* params, const uint8_t* next,
+                         const double* goals, int32_t n_goals, const double* starts,
+                         const int32_t* goal_idx, int64_t n_queries, int32_t N, double* wp,
+                         int32_t* status, int32_t* steps);
 
 /* Workspace bytes uam_refine needs for n_paths (after uam_set_geometry/uam_set_params). */
 int64_t uam_refine_workspace_bytes(uam_ctx* ctx, int64_t n_paths,

@@ -1,0 +1,92 @@
+"""Time the route seeds (K9) on the cfg3 raster: uam_route_field per UAM_OPT_K9_TILE x
+UAM_OPT_K9_INNER (host wall ms of the whole call, rounds, tile visits, visits per tile) for a
+goal near the centre and one in a corner, checking that every setting gives the same bits, then
+uam_route_paths at --queries starts.  One JSON line per measurement.
+usage: python tools/time_route.py [--R R] [--queries Q] [--lam L] [--inflate I]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+COMBOS = [(t, i) for t in (16, 32, 64) for i in (4, 16, 32, 64)] + [
+    (32, 1), (32, 128), (32, 256), (64, 128), (64, 256)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--R", type=int, default=4096)
+    ap.add_argument("--queries", type=int, default=100000)
+    ap.add_argument("--lam", type=float, default=1.0)
+    ap.add_argument("--inflate", type=int, default=0)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+
+    from uam_path_planning_amd.engine import Engine
+    from uam_path_planning_amd.geometry import compile_map
+    from uam_path_planning_amd.scenario import (build_region_map, canonical_params,
+                                                canonical_spec, raster_geo)
+    from uam_path_planning_amd.synthetic import random_pairs, synthetic_dem
+
+    spec = canonical_spec(nfz_polygons=64)
+    eng = Engine(0)
+    eng.set_geometry(compile_map(build_region_map(spec)))
+    eng.set_params(canonical_params(spec, N=80, anchor=tuple(spec["x_start"])))
+    raster = eng.raster_build(raster_geo(a.R), synthetic_dem(a.R), packed=False)
+
+    def free_near(x, y):
+        """The first point on a fixed ray from (x, y) outside every no-fly shape."""
+        for k in range(200):
+            p = np.array([[x + 0.37 * k, y - 0.29 * k]])
+            pe = eng.eval_points(torch.tensor(p, device="cuda"), want=("psi_raw", "collide"))
+            if float(pe["psi_raw"][0]) == 0 and int(pe["collide"][0]) == 0:
+                return p[0]
+        raise RuntimeError("no free goal found")
+
+    goals = {"centre": free_near(30.0, -10.0), "corner": free_near(0.4, 19.6)}
+    print(json.dumps({"goals": {k: v.tolist() for k, v in goals.items()}}), flush=True)
+    first = {}
+    for tile, inner in COMBOS:
+        for name, g in goals.items():
+            eng.set_option("k9_tile", tile)
+            eng.set_option("k9_inner", inner)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f = eng.route_field(raster, g.reshape(1, 2), lam=a.lam, inflate=a.inflate)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            ntiles = ((a.R + tile - 1) // tile) ** 2
+            if name not in first:
+                first[name] = (f.dist.clone(), f.next.clone())
+            same = bool(torch.equal(f.dist.view(torch.int64), first[name][0].view(torch.int64))
+                        and torch.equal(f.next, first[name][1]))
+            print(json.dumps({"tile": tile, "inner": inner, "goal": name, "ms": round(ms, 2),
+                              "rounds": f.rounds, "visits": f.visits,
+                              "visits_per_tile": round(f.visits / ntiles, 2),
+                              "reachable_cells": int(torch.isfinite(f.dist).sum()),
+                              "same_bits_as_first": same}), flush=True)
+    eng.set_option("k9_tile", 32)
+    eng.set_option("k9_inner", 16)
+    f = eng.route_field(raster, goals["centre"].reshape(1, 2), lam=a.lam, inflate=a.inflate)
+    s = eng.tensor(random_pairs(a.queries, seed=5)[:, :2], torch.float64)
+    gi = eng.tensor(np.zeros(a.queries, dtype=np.int32), torch.int32)
+    eng.route_paths(f, s, gi)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    o = eng.route_paths(f, s, gi)
+    e1.record()
+    torch.cuda.synchronize()
+    st = o["status"].cpu().numpy()
+    steps = o["steps"].cpu().numpy()
+    print(json.dumps({"route_paths_queries": a.queries, "ms": round(e0.elapsed_time(e1), 3),
+                      "status_counts": {int(k): int((st == k).sum()) for k in np.unique(st)},
+                      "steps_mean": float(steps[st == 0].mean()) if (st == 0).any() else None,
+                      "steps_max": int(steps.max())}))
+
+
+if __name__ == "__main__":
+    main()

@@ -26,6 +26,8 @@ OPTIONS = {"group": 1, "sorted_min_paths": 2, "k2s_segments": 3, "wave_max_paths
            "k2g_chunk": 13, "k2g_curve": 14, "k2g_sim": 15, "k4h_band": 17,
            "k2h_lb_stride": 19, "k2h_terrain": 20, "k4h_terrain": 21,
            "test_sort_fault": 22, "exact_sum": 23, "exact_sum_volume": 24}
+# the route seeds' options (K9; UAM_OPT_K9_TILE / UAM_OPT_K9_INNER), which no output depends on
+ROUTE_OPTIONS = {"k9_tile": 27, "k9_inner": 28}
 INEQ_HALFPLANE, INEQ_ELLIPSE, INEQ_AXIS = 0, 1, 2
 MODE_ANALYTIC, MODE_RASTER, MODE_VOLUME = 0, 1, 2
 FLAG_NFZ, FLAG_MASK, FLAG_NODATA = 1, 2, 4
@@ -77,6 +79,13 @@ class Vertical(ctypes.Structure):
     """uam_vertical: the 3-D length, turn and climb rows of the _v evaluations."""
     _fields_ = [("abi_version", ctypes.c_uint32), ("z_scale", ctypes.c_double),
                 ("sin_climb", ctypes.c_double), ("sin_descent", ctypes.c_double)]
+
+
+class RouteParams(ctypes.Structure):
+    """uam_route_params: the cell cost, blocking and round bound of the route seeds (K9)."""
+    _fields_ = [("abi_version", ctypes.c_uint32), ("lam", ctypes.c_double),
+                ("block_flags", ctypes.c_uint32), ("inflate", ctypes.c_int32),
+                ("max_rounds", ctypes.c_int32)]
 
 
 class RefineParams(ctypes.Structure):
@@ -208,6 +217,22 @@ SIGNATURES = {
     "uam_dem_polygons": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(RasterDesc), ctypes.c_float,
                                         ctypes.c_double, ctypes.POINTER(PolyprocParams), _vp,
                                         ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _vp]),
+    "uam_route_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(RasterDesc),
+                                                   ctypes.POINTER(RouteParams)]),
+    "uam_route_field": (ctypes.c_int, [_vp, ctypes.POINTER(RasterDesc), _vp,
+                                       ctypes.POINTER(RouteParams), _vp, ctypes.c_int32, _vp, _vp,
+                                       _vp, ctypes.c_int64, _i32p, _vp]),
+    "uam_route_visits": (ctypes.c_int64, [_vp]),
+    "uam_route_paths": (ctypes.c_int, [_vp, ctypes.POINTER(RasterDesc), _vp,
+                                       ctypes.POINTER(RouteParams), _vp, _vp, ctypes.c_int32, _vp,
+                                       _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "uam_route_field_host": (ctypes.c_int, [ctypes.POINTER(RasterDesc), _vp,
+                                            ctypes.POINTER(RouteParams), _vp, ctypes.c_int32, _vp,
+                                            _vp]),
+    "uam_route_paths_host": (ctypes.c_int, [ctypes.POINTER(RasterDesc), _vp,
+                                            ctypes.POINTER(RouteParams), _vp, _vp, ctypes.c_int32,
+                                            _vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp,
+                                            _vp]),
     "uam_refine_workspace_bytes": (ctypes.c_int64, [_vp, ctypes.c_int64,
                                                     ctypes.POINTER(RefineParams)]),
     "uam_refine": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.POINTER(RefineParams), _vp,

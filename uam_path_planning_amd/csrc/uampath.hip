@@ -55,6 +55,7 @@
 // tables are read with wave-uniform addresses (scalar cache) in the analytic mode.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -6273,6 +6274,9 @@ __global__ __launch_bounds__(1024) void k_g_final(KParams p, KGrp kg, KOut out,
 // K4hp: the altitude profiles on the packed, sorted volume, k_vp_hist, k_vp_eval, k_vp_final*
 #include "k4hp.inc"
 
+// K9: route seeds, k_route_cost, k_route_init, k_route_relax, k_route_next, k_route_trace
+#include "k9_route.inc"
+
 // closes the anonymous namespace opened above the device-side tables
 }  // namespace
 
@@ -6376,6 +6380,13 @@ struct uam_ctx {
     const int32_t* sum_scale = nullptr;  // uam_set_sum_scale: the caller's device words
     int exact_sum_vol = 0;      // UAM_OPT_EXACT_SUM_VOLUME: K4h's voxel sums as exact integers
     const int32_t* vol_sum_scale = nullptr;  // uam_set_volume_sum_scale: the caller's words
+    int k9_tile = 32;           // K9 tile edge (UAM_OPT_K9_TILE: 16, 32, 64)
+    int k9_inner = 16;          // K9 sweeps inside a tile per round (UAM_OPT_K9_INNER: 1..256;
+                                // cfg3 4096^2 at tile 32, centre / corner goal: 4 87 / 64 ms,
+                                // 16 65 / 40, 32 69 / 42, 64 76 / 48)
+    bool k9_attrs = false;      // k_route_relax<64>'s dynamic-LDS attribute raised
+    int32_t* h_route = nullptr; // page-locked words the active-tile counts are copied to
+    int64_t route_visits = 0;   // uam_route_visits: tiles the last uam_route_field visited
 
 };
 
@@ -6579,6 +6590,7 @@ void uam_ctx_destroy(uam_ctx* ctx) {
     if (ctx->devarena) dev_arena_free(ctx->devarena);
     if (ctx->d_tmtab) (void)hipFree(ctx->d_tmtab);
     if (ctx->h_err) (void)hipHostFree(ctx->h_err);
+    if (ctx->h_route) (void)hipHostFree(ctx->h_route);
     delete ctx;
 }
 
@@ -7156,6 +7168,11 @@ static const OptDef kOptions[] = {
     {UAM_OPT_EXACT_SUM, UAM_OPT_MEMBER(exact_sum), opt_01, "UAM_OPT_EXACT_SUM %lld is not 0 or 1"},
     {UAM_OPT_EXACT_SUM_VOLUME, UAM_OPT_MEMBER(exact_sum_vol), opt_01,
      "UAM_OPT_EXACT_SUM_VOLUME %lld is not 0 or 1"},
+    {UAM_OPT_K9_TILE, UAM_OPT_MEMBER(k9_tile),
+     [](int64_t v) { return v == 16 || v == 32 || v == 64; },
+     "UAM_OPT_K9_TILE %lld not 16, 32 or 64"},
+    {UAM_OPT_K9_INNER, UAM_OPT_MEMBER(k9_inner), [](int64_t v) { return v >= 1 && v <= 256; },
+     "UAM_OPT_K9_INNER %lld outside [1, 256]"},
 };
 #undef UAM_OPT_MEMBER
 
@@ -9244,6 +9261,186 @@ int uam_eval_generated3d_profiles_hv(uam_ctx* ctx, const uam_volume_desc* vd, co
                                      double* climb_sum, uam_stream stream) {
     return eval_profiles_h(ctx, vd, vol, packed, pairs6, n_pairs, utab, D, ztab, A, vert, true,
                            out, climb_sum, stream);
+}
+
+// ---- K9: route seeds (k9_route.inc) -----------------------------------------------------------
+// the descriptor and the parameters checked and folded into the kernels' KRoute
+static int route_setup(const uam_raster_desc* desc, const uam_route_params* p, KRoute* g) {
+    if (!p) return fail(UAM_E_INVALID, "route params is NULL");
+    if (p->abi_version != UAM_ABI_VERSION)
+        return fail(UAM_E_VERSION, "route params abi_version %u != %d", p->abi_version,
+                    UAM_ABI_VERSION);
+    KRaster kr{};
+    const int st = make_kraster(desc, &kr);
+    if (st) return st;
+    if (!(p->lambda >= 0.0) || !(p->lambda < r9_inf()))
+        return fail(UAM_E_INVALID, "route lambda must be finite and >= 0");
+    if (p->inflate < 0 || p->inflate > R9_INFLATE_MAX)
+        return fail(UAM_E_INVALID, "route inflate %d outside [0, %d]", p->inflate,
+                    R9_INFLATE_MAX);
+    if (p->max_rounds < 0) return fail(UAM_E_INVALID, "route max_rounds %d < 0", p->max_rounds);
+    g->nx = kr.nx, g->ny = kr.ny;
+    g->x0 = kr.x0, g->y_top = kr.y_top, g->dx = kr.dx, g->dy = kr.dy;
+    g->inv_dx = kr.inv_dx, g->inv_dy = kr.inv_dy;
+    r9_set_lengths(g);
+    g->lambda = p->lambda;
+    g->block_flags = p->block_flags;
+    g->inflate = p->inflate;
+    return UAM_OK;
+}
+
+static int route_goals_ok(const KRoute& g, int32_t n_goals) {
+    if (n_goals < 1) return fail(UAM_E_INVALID, "route n_goals %d < 1", n_goals);
+    if ((int64_t)n_goals * g.nx * g.ny >= ((int64_t)1 << 40))
+        return fail(UAM_E_INVALID, "route fields of 2^40 or more cells");
+    return UAM_OK;
+}
+
+int64_t uam_route_workspace_bytes(const uam_raster_desc* desc, const uam_route_params* params) {
+    KRoute g{};
+    if (route_setup(desc, params, &g)) return -1;
+    return r9_workspace(g.nx, g.ny).bytes;
+}
+
+int64_t uam_route_visits(const uam_ctx* ctx) { return ctx ? ctx->route_visits : 0; }
+
+int uam_route_field(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
+                    const uam_route_params* params, const double* goals, int32_t n_goals,
+                    double* dist, uint8_t* next, void* workspace, int64_t workspace_bytes,
+                    int32_t* rounds_out, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    KRoute g{};
+    int st = route_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_goals_ok(g, n_goals))) return st;
+    if (!rec || !goals || !dist || !next || !workspace)
+        return fail(UAM_E_INVALID,
+                    "uam_route_field: rec / goals / dist / next / workspace is NULL");
+    const R9Ws ws = r9_workspace(g.nx, g.ny);
+    if (workspace_bytes < ws.bytes)
+        return fail(UAM_E_INVALID, "route workspace %lld bytes < %lld", (long long)workspace_bytes,
+                    (long long)ws.bytes);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)dist & 7))
+        return fail(UAM_E_INVALID, "route workspace not 256-B or dist not 8-B aligned");
+    DeviceGuard dg(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int T = ctx->k9_tile, inner = ctx->k9_inner;
+    if (T == 64) {
+        void (*const big[])(const double*, double*, KRoute, int, int, const int32_t*, uint32_t*,
+                            uint32_t*, int32_t*, int32_t*, int, int) = {k_route_relax<64>};
+        if ((st = raise_lds(&ctx->k9_attrs, 2 * 66 * 66 * (int)sizeof(double), big))) return st;
+    }
+    if (!ctx->h_route) HIP_TRY(hipHostMalloc((void**)&ctx->h_route, 64, hipHostMallocDefault));
+    char* base = (char*)workspace;
+    double* c = (double*)(base + ws.c_off);
+    uint32_t* flags = (uint32_t*)(base + ws.flags_off);
+    int32_t* lists = (int32_t*)(base + ws.lists_off);
+    int32_t* ctl = (int32_t*)(base + ws.ctl_off);
+    const int ntx = r9_tiles(g.nx, T), nty = r9_tiles(g.ny, T), nt = ntx * nty;
+    const int64_t cells = (int64_t)g.nx * g.ny;
+    const int64_t max_rounds = params->max_rounds ? params->max_rounds : cells;
+    const int grid = grid_for(cells, R9_THREADS, 1 << 16);
+    ctx->last_kernel = "K9";
+    ctx->route_visits = 0;
+    hipLaunchKernelGGL(k_route_cost, dim3(grid), dim3(R9_THREADS), 0, s, (const uint4*)rec, g, c);
+    HIP_TRY(hipGetLastError());
+    int64_t rounds = 0;
+    for (int32_t gi = 0; gi < n_goals; ++gi) {
+        double* d = dist + (int64_t)gi * cells;
+        const double* goal = goals + 2 * (int64_t)gi;
+        hipLaunchKernelGGL(k_route_init, dim3(grid), dim3(R9_THREADS), 0, s, c, g, goal, d, T, ntx,
+                           nt, flags, lists, ctl);
+        HIP_TRY(hipGetLastError());
+        int cur = 0;
+        for (int64_t r = 0;; ++r) {
+            // the active tiles of this round (the one word the host waits for)
+            HIP_TRY(hipMemcpyAsync(ctx->h_route, ctl + cur, sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            const int32_t n = *(volatile int32_t*)ctx->h_route;
+            if (n < 0 || n > nt)
+                return fail(UAM_E_HIP, "route field: active-tile count %d outside [0, %d]", n, nt);
+            if (n == 0) break;
+            if (r >= max_rounds)
+                return fail(UAM_E_STATE,
+                            "route field of goal %d has not converged within max_rounds = %lld "
+                            "rounds (%d tiles still active)", gi, (long long)max_rounds, n);
+            if (T == 16)
+                route_relax_launch<16>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
+            else if (T == 32)
+                route_relax_launch<32>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
+            else
+                route_relax_launch<64>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
+            HIP_TRY(hipGetLastError());
+            ++rounds;
+            ctx->route_visits += n;
+            cur ^= 1;
+        }
+        hipLaunchKernelGGL(k_route_next, dim3(grid), dim3(R9_THREADS), 0, s, c, d, g, goal,
+                           next + (int64_t)gi * cells);
+        HIP_TRY(hipGetLastError());
+    }
+    if (rounds_out) *rounds_out = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
+    return UAM_OK;
+}
+
+int uam_route_paths(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
+                    const uam_route_params* params, const uint8_t* next, const double* goals,
+                    int32_t n_goals, const double* starts, const int32_t* goal_idx,
+                    int64_t n_queries, double* wp, int32_t* status, int32_t* steps,
+                    uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
+    KRoute g{};
+    int st = route_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_goals_ok(g, n_goals))) return st;
+    if (n_queries < 0) return fail(UAM_E_INVALID, "route n_queries < 0");
+    if (n_queries == 0) return UAM_OK;
+    if (!rec || !next || !goals || !starts || !goal_idx || !wp || !status)
+        return fail(UAM_E_INVALID, "uam_route_paths: a buffer is NULL");
+    if (n_queries >= ((int64_t)1 << 31) * R9_THREADS)
+        return fail(UAM_E_INVALID, "route n_queries too large");
+    DeviceGuard dg(ctx->device);
+    const int64_t blocks = (n_queries + R9_THREADS - 1) / R9_THREADS;
+    hipLaunchKernelGGL(k_route_trace, dim3((unsigned)blocks), dim3(R9_THREADS), 0,
+                       (hipStream_t)stream, g, (const uint4*)rec, next, goals, n_goals, starts,
+                       goal_idx, n_queries, ctx->kp.N, wp, status, steps);
+    HIP_TRY(hipGetLastError());
+    ctx->last_kernel = "K9t";
+    return UAM_OK;
+}
+
+int uam_route_field_host(const uam_raster_desc* desc, const void* rec,
+                         const uam_route_params* params, const double* goals, int32_t n_goals,
+                         double* dist, uint8_t* next) {
+    KRoute g{};
+    int st = route_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_goals_ok(g, n_goals))) return st;
+    if (!rec || !goals || !dist || !next)
+        return fail(UAM_E_INVALID, "uam_route_field_host: rec / goals / dist / next is NULL");
+    r9_field_host(g, (const uint4*)rec, goals, n_goals, dist, next);
+    return UAM_OK;
+}
+
+int uam_route_paths_host(const uam_raster_desc* desc, const void* rec,
+                         const uam_route_params* params, const uint8_t* next,
+                         const double* goals, int32_t n_goals, const double* starts,
+                         const int32_t* goal_idx, int64_t n_queries, int32_t N, double* wp,
+                         int32_t* status, int32_t* steps) {
+    KRoute g{};
+    int st = route_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_goals_ok(g, n_goals))) return st;
+    if (n_queries < 0 || N < 0) return fail(UAM_E_INVALID, "route n_queries or N < 0");
+    if (n_queries == 0) return UAM_OK;
+    if (!rec || !next || !goals || !starts || !goal_idx || !wp || !status)
+        return fail(UAM_E_INVALID, "uam_route_paths_host: a buffer is NULL");
+    for (int64_t q = 0; q < n_queries; ++q)
+        r9_trace(g, (const uint4*)rec, next, goals, n_goals, starts, goal_idx, q, N, wp, status,
+                 steps);
+    return UAM_OK;
 }
 
 static int refine_memory(const uam_refine_params* rp) {

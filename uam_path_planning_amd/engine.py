@@ -149,6 +149,43 @@ class RiskVolume:
     sum_scale_version: int = field(repr=False, default=-1)
 
 
+@dataclass
+class RouteField:
+    """The cost-to-go fields of some goals on a cost raster (Engine.route_field, K9;
+    include/uampath.h "Route seeds"): dist [G, ny, nx] float64 (+inf: blocked or unreachable),
+    next [G, ny, nx] uint8 (direction 0..7 = E, NE, N, NW, W, SW, S, SE; 8 = the goal cell;
+    255 = no route), goals [G, 2], rounds = relaxation rounds of all goals together, visits =
+    tiles those rounds visited.  rec and the parameters are kept for route_paths (the start's
+    blocking is read from rec).  Device tensors from route_field, numpy arrays from
+    route_field_host.  A derived, untracked product of rec: rebuild it when rec changes."""
+    geo: RasterGeo
+    goals: object = field(repr=False)
+    dist: object = field(repr=False)
+    next: object = field(repr=False)
+    rounds: int = 0
+    visits: int = 0
+    rec: object = field(default=None, repr=False)
+    lam: float = 1.0
+    block_flags: int = _lib.FLAG_NFZ
+    inflate: int = 0
+
+    def params(self, max_rounds=0):
+        return _route_params(self.lam, self.block_flags, self.inflate, max_rounds)
+
+
+def _route_params(lam, block_flags, inflate, max_rounds):
+    return _lib.RouteParams(_lib.ABI_VERSION, float(lam), int(block_flags), int(inflate),
+                            int(max_rounds))
+
+
+def _host_rec(rec, geo):
+    """A record raster as contiguous 16-B records on the host ([ny, nx, 4] 32-bit words)."""
+    r = np.ascontiguousarray(rec)
+    if r.dtype.itemsize != 4 or r.size != geo.ny * geo.nx * 4:
+        raise ValueError(f"rec must hold [{geo.ny}, {geo.nx}, 4] 32-bit words")
+    return r
+
+
 def _ptr(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
@@ -404,9 +441,11 @@ class Engine:
         "k2g_chunk", "k2g_curve", "k2g_sim", "k4h_band", "k2h_lb_stride", "k2h_terrain",
         "k4h_terrain", "test_sort_fault" (tests only), "exact_sum" (1: K2h's raster sums as
         exact integers, independent of the group length -- "K2hx+pack") and "exact_sum_volume"
-        (1: the same for K4h's voxel sums in eval_generated3d -- "K4hx+pack")."""
-        _lib.check(self.lib.uam_set_option(self._ctx, _lib.OPTIONS[name], int(value)),
-                   "uam_set_option")
+        (1: the same for K4h's voxel sums in eval_generated3d -- "K4hx+pack"); "k9_tile" (16,
+        32, 64) and "k9_inner" (1..256; _lib.ROUTE_OPTIONS): route_field's tile edge and sweeps
+        per round, which its outputs do not depend on."""
+        key = _lib.ROUTE_OPTIONS[name] if name in _lib.ROUTE_OPTIONS else _lib.OPTIONS[name]
+        _lib.check(self.lib.uam_set_option(self._ctx, key, int(value)), "uam_set_option")
         if name == "exact_sum":
             self._exact_sum = bool(int(value))
         elif name == "exact_sum_volume":
@@ -414,8 +453,8 @@ class Engine:
 
     def get_option(self, name):
         v = ctypes.c_int64()
-        _lib.check(self.lib.uam_get_option(self._ctx, _lib.OPTIONS[name], ctypes.byref(v)),
-                   "uam_get_option")
+        key = _lib.ROUTE_OPTIONS[name] if name in _lib.ROUTE_OPTIONS else _lib.OPTIONS[name]
+        _lib.check(self.lib.uam_get_option(self._ctx, key, ctypes.byref(v)), "uam_get_option")
         return v.value
 
     def _outputs(self, P, W, mode, want_cells, want_g, n_pairs=None):
@@ -801,6 +840,94 @@ class Engine:
         _lib.check(self.lib.uam_refine(self._ctx, _ptr(z), P, ctypes.byref(st), _ptr(ws), nbytes,
                                        _ptr(out["cost"]), _ptr(out["infeas"]), _ptr(out["iters"]),
                                        self.stream), "uam_refine")
+        return out
+
+    # -- route seeds (K9) -------------------------------------------------------------------
+    def route_field(self, raster, goals, lam=1.0, block_flags=_lib.FLAG_NFZ, inflate=0,
+                    max_rounds=0):
+        """The cost-to-go fields of goals [G, 2] on raster (uam_route_field): a per-goal setup
+        product like the packed copy -- the call waits for the stream between its rounds.  Cell
+        cost 1 + lam * phi, cells with a block_flags bit (or a non-finite or non-positive cost)
+        blocked, inflate cells of clearance around them; max_rounds 0 = nx*ny.  Returns a
+        RouteField; raises UamError when a field has not converged within max_rounds."""
+        torch = _torch()
+        geo = raster.geo
+        g = self.tensor(goals, torch.float64).reshape(-1, 2)
+        G = g.shape[0]
+        rp = _route_params(lam, block_flags, inflate, max_rounds)
+        gs = geo.as_struct()
+        nbytes = self.lib.uam_route_workspace_bytes(ctypes.byref(gs), ctypes.byref(rp))
+        ws = None if nbytes < 0 else self.empty(((nbytes + 255) // 256, 256), torch.uint8)
+        dist = self.empty((G, geo.ny, geo.nx), torch.float64)
+        nxt = self.empty((G, geo.ny, geo.nx), torch.uint8)
+        rounds = ctypes.c_int32()
+        _lib.check(self.lib.uam_route_field(
+            self._ctx, ctypes.byref(gs), _ptr(raster.rec), ctypes.byref(rp), _ptr(g), G,
+            _ptr(dist), _ptr(nxt), _ptr(ws), max(nbytes, 0), ctypes.byref(rounds), self.stream),
+            "uam_route_field")
+        return RouteField(geo, g, dist, nxt, rounds.value,
+                          int(self.lib.uam_route_visits(self._ctx)), raster.rec, float(lam),
+                          int(block_flags), int(inflate))
+
+    def route_paths(self, field, starts, goal_idx):
+        """Seed paths through a RouteField (uam_route_paths): starts [Q, 2], goal_idx [Q] into
+        field.goals.  Returns {"wp" [Q, N+2, 2], "status" [Q], "steps" [Q]} (device tensors);
+        status 0 ok, 1 start off the raster or blocked, 2 goal unreachable, 3 walk too long,
+        4 bad goal -- a nonzero status leaves the straight line in wp.  wp is what
+        eval_waypoints and refine take."""
+        torch = _torch()
+        s = self.tensor(starts, torch.float64).reshape(-1, 2)
+        gi = self.tensor(goal_idx, torch.int32).reshape(-1)
+        Q = s.shape[0]
+        if gi.shape[0] != Q:
+            raise ValueError(f"{Q} starts but {gi.shape[0]} goal indices")
+        N = self.params.N
+        out = {"wp": self.empty((Q, N + 2, 2), torch.float64),
+               "status": self.empty((Q,), torch.int32), "steps": self.empty((Q,), torch.int32)}
+        rp = field.params()
+        _lib.check(self.lib.uam_route_paths(
+            self._ctx, ctypes.byref(field.geo.as_struct()), _ptr(field.rec), ctypes.byref(rp),
+            _ptr(field.next), _ptr(field.goals), field.goals.shape[0], _ptr(s), _ptr(gi), Q,
+            _ptr(out["wp"]), _ptr(out["status"]), _ptr(out["steps"]), self.stream),
+            "uam_route_paths")
+        return out
+
+    @staticmethod
+    def route_field_host(geo, rec, goals, lam=1.0, block_flags=_lib.FLAG_NFZ, inflate=0):
+        """route_field on the host (uam_route_field_host; needs no GPU): the definition applied
+        by the inline functions the kernels run, the minimum by a heap Dijkstra.  rec: numpy
+        [ny, nx, 4] 32-bit words.  Returns a RouteField of numpy arrays (rounds 0)."""
+        r = _host_rec(rec, geo)
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 2)
+        G = g.shape[0]
+        dist = np.empty((G, geo.ny, geo.nx), dtype=np.float64)
+        nxt = np.empty((G, geo.ny, geo.nx), dtype=np.uint8)
+        rp = _route_params(lam, block_flags, inflate, 0)
+        _lib.check(_lib.load().uam_route_field_host(
+            ctypes.byref(geo.as_struct()), r.ctypes.data, ctypes.byref(rp), g.ctypes.data, G,
+            dist.ctypes.data, nxt.ctypes.data), "uam_route_field_host")
+        return RouteField(geo, g, dist, nxt, 0, 0, r, float(lam), int(block_flags), int(inflate))
+
+    @staticmethod
+    def route_paths_host(field, starts, goal_idx, N):
+        """route_paths on the host (uam_route_paths_host; needs no GPU) for a RouteField of
+        numpy arrays; N interior waypoints.  Returns {"wp", "status", "steps"} numpy arrays."""
+        s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 2)
+        gi = np.ascontiguousarray(goal_idx, dtype=np.int32).reshape(-1)
+        Q = s.shape[0]
+        if gi.shape[0] != Q:
+            raise ValueError(f"{Q} starts but {gi.shape[0]} goal indices")
+        N = int(N)
+        out = {"wp": np.empty((Q, max(N, 0) + 2, 2), dtype=np.float64),
+               "status": np.empty((Q,), dtype=np.int32), "steps": np.empty((Q,), dtype=np.int32)}
+        rp = field.params()
+        nxt = np.ascontiguousarray(field.next, dtype=np.uint8)
+        goals = np.ascontiguousarray(field.goals, dtype=np.float64)
+        _lib.check(_lib.load().uam_route_paths_host(
+            ctypes.byref(field.geo.as_struct()), _host_rec(field.rec, field.geo).ctypes.data,
+            ctypes.byref(rp), nxt.ctypes.data, goals.ctypes.data, goals.shape[0], s.ctypes.data,
+            gi.ctypes.data, Q, N, out["wp"].ctypes.data, out["status"].ctypes.data,
+            out["steps"].ctypes.data), "uam_route_paths_host")
         return out
 
     # -- coordinate reference systems (K7; SURVEY §8(f) ranks 3-4) --------------------------

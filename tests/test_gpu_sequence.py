@@ -1,0 +1,408 @@
+"""One long-lived context under mixed call sequences: every output of every call still equals the
+oracle, bit for bit (ulp-level for the CRS reprojection), whatever the context ran before.
+
+A context carries state from call to call -- the shared grow-only scratch that every sorted form
+and pair order carves its own way and nobody clears, the cached tile-key table, the grow-only
+K7 tables, the tables set_params / set_geometry rebuild, the K8 arenas behind thread-local
+pointers, the side streams with their one fork / join event pair, the per-context "attributes
+raised" flags and the borrowed sum scales -- while every other parity test starts from a new
+context and makes one kind of call on it.  A launch that reads a word the current call did not
+write sees zeros there and the previous call's data here.
+
+  * test_sequence_is_bit_exact: the drawn sequences of sequence_cases.py (13-14 calls: large
+    then small on the scratch, raster -> volume -> analytic -> raster, a tile-key rewrite, N and
+    the map changed between calls, two rasters, exact sums on and off, K7 tables grown then
+    reused), each call into buffers 64 entries longer than it needs, filled with markers
+    beforehand: no marker left in what the call owns, every marker left behind it;
+  * test_replay_after_everything: the first sorted call of seed 0 again after the whole
+    sequence, and on a new context;
+  * test_sorted_forms_on_two_streams: two streams on one context, the second call growing the
+    scratch and rewriting the tile keys while the first is pending;
+  * test_two_contexts_interleaved: two contexts alive at once.
+
+UAM_SEQ_SEEDS=a:b widens the default seeds 0-7.  Reference rules: those of the per-family tests
+(test_gpu_fuzz.py, test_gpu_exact_sum*.py, test_gpu_profiles_h.py, test_gpu_crs.py,
+test_gpu_polygons_topology.py)."""
+import os
+
+import numpy as np
+import pytest
+
+import sequence_cases as S
+from test_gpu_k2h import _check_pack
+from test_gpu_polygons_topology import _gpu as _gpu_polygons, _verify as _verify_polygons
+from test_gpu_profiles import _same
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+GUARD = 64
+MARK_I32 = 0x5A5A5A5A
+MARK_F64 = 0x7FF85A5A5A5A5A5A   # a quiet NaN no arithmetic produces
+
+
+def _seeds():
+    v = os.environ.get("UAM_SEQ_SEEDS", "0:8")
+    a, b = (int(x) for x in v.split(":"))
+    return list(range(a, b))
+
+
+def _raw(t):
+    """A tensor's words as the markers are compared: uint64 for float64, int32 as it is."""
+    a = t.cpu().numpy()
+    return a.view(np.uint64) if a.dtype == np.float64 else a
+
+
+class Run:
+    """One context and the oracle's side of what it was told so far."""
+
+    def __init__(self, oracle_mod, start):
+        from uam_path_planning_amd import build
+        from uam_path_planning_amd.engine import Engine
+
+        if not torch.cuda.is_available():
+            pytest.fail("GPU tests need an MI355X")
+        build.build_library()
+        self.O = oracle_mod
+        self.e = Engine(0)
+        # the library's own batch-size thresholds, as a new context has them
+        self.defaults = {k: self.e.get_option(k) for k in ("sorted_min_paths", "wave_max_paths")}
+        self.ref = S.Reference(oracle_mod, start)
+        self.rasters = {}
+        self.vol = None
+        self.geometry(start)
+
+    # -- state ------------------------------------------------------------------------------
+    def geometry(self, g):
+        from uam_path_planning_amd.geometry import compile_map
+        from uam_path_planning_amd.scenario import build_region_map
+
+        self.spec = S.spec_of(g)
+        self.e.set_geometry(compile_map(build_region_map(self.spec)))
+        self.params(g["params"])
+
+    def params(self, p):
+        from uam_path_planning_amd.engine import PathParams
+
+        self.e.set_params(PathParams(**S.path_params(self.spec, p)))
+
+    def options(self, step):
+        for k, v in S.options_of(step, self.defaults).items():
+            self.e.set_option(k, v)
+
+    # -- the calls ----------------------------------------------------------------------------
+    def k1(self, s):
+        from uam_path_planning_amd.engine import RasterGeo
+
+        nx, ny, x0, yt, dx, dy = s["geo"]
+        geo = RasterGeo(nx=nx, ny=ny, x0=x0, y_top=yt, dx=dx, dy=dy, nodata=-9999.0,
+                        dem_threshold=s["thr"])
+        self.e.set_option("k1_rows", s["k1_rows"])
+        raster = self.e.raster_build(geo, S.dem_of(s), summary=False)
+        self.e.raster_summary(raster, 0, packed=True)
+        want = self.ref.k1(s)
+        np.testing.assert_array_equal(raster.rec.cpu().numpy(), want.view(np.int32))
+        _check_pack(raster, want)
+        self.rasters[s["raster"]] = raster
+        if self.vol is not None and self.vol[0][0] == s["raster"]:
+            self.vol = None
+
+    def volume(self, s):
+        from uam_path_planning_amd.scenario import layer_weights
+
+        key = (s["raster"], s["nz"])
+        v, _ = self.ref.volume(s)
+        if self.vol is None or self.vol[0] != key:
+            nz = s["nz"]
+            vol = self.e.volume_build(self.rasters[s["raster"]], nz, 0.0, 640.0 / nz,
+                                      layer_weights(nz))
+            self.e.volume_pack(vol)
+            np.testing.assert_array_equal(vol.vox.cpu().numpy(), v["vox"].view(np.int32))
+            np.testing.assert_array_equal(vol.cols.cpu().numpy(), v["cols"].view(np.int32))
+            self.vol = (key, vol)
+        return self.vol[1]
+
+    def guarded(self, s):
+        """The step's output buffers, GUARD entries (rows) longer than the call needs, every
+        tensor filled with its marker."""
+        P, W = s["Q"] * s["D"] * s.get("A", 1), s["N"] + 2
+        cells = s["kind"] == "raster_exact" or bool(s.get("cells"))
+        o, st = self.e.outputs(P + GUARD, W, n_pairs=s["Q"] + GUARD, want_cells=cells)
+        for t in o.values():
+            if t.dtype == torch.float64:
+                t.view(torch.int64).fill_(MARK_F64)
+            else:
+                t.fill_(MARK_I32)
+        return o, st
+
+    def call(self, s, outputs):
+        """The evaluating step s on the context (its options set first); returns the buffers."""
+        e, k = self.e, s["kind"]
+        self.options(s)
+        pairs, ut = S.pairs_of(s), S.utab_of(s)
+        try:
+            if k == "analytic":
+                return e.eval_generated(pairs, ut, raster=None, outputs=outputs)
+            if k in S.RASTER_KINDS:
+                cells = k == "raster_exact" or s["cells"]
+                return e.eval_generated(pairs, ut, raster=self.rasters[s["raster"]],
+                                        want_cells=cells, outputs=outputs)
+            vol = self.volume(s)
+            if k == "profiles":
+                return e.eval_generated3d_profiles(pairs, ut, S.ztab_of(s), vol, packed=True,
+                                                   outputs=outputs)
+            return e.eval_generated3d(pairs, ut, vol, outputs=outputs)
+        finally:   # exact sums on, then off again
+            e.set_option("exact_sum", 0)
+            e.set_option("exact_sum_volume", 0)
+
+    def check(self, s, o):
+        """The outputs o of step s (buffers from guarded()) against the oracle, by the rule of
+        the step's family test; returns the words the call wrote."""
+        e = self.e
+        kernel, group = e.last_kernel(), e.last_group()
+        forced, fgroup = self.ref.forced(s)
+        if forced is not None:   # no silent fall-back behind a right answer
+            assert (kernel, group) == (forced, fgroup)
+        else:
+            assert group == 0 and not kernel.startswith(("K2h", "K2g")), kernel
+        want = self.ref.expect(s, kernel, group)
+        P, Q, W = s["Q"] * s["D"] * s.get("A", 1), s["Q"], s["N"] + 2
+        bits = s["kind"] in ("profiles", "raster_exact") or s.get("exact")
+        for key, w in want.items():
+            n = Q if key in S.BEST_KEYS else P * W if key == "cells" else P
+            raw = _raw(o[key]).reshape(-1)
+            got = o[key].cpu().numpy().reshape(-1)[:n].reshape(w.shape)
+            mark = np.uint64(MARK_F64) if raw.dtype == np.uint64 else np.int32(MARK_I32)
+            assert not (raw[:n] == mark).any(), f"{key}: entries the call never wrote"
+            if bits:
+                _same(got, w, key)
+            else:
+                np.testing.assert_array_equal(got, w, err_msg=key)
+        for key, t in o.items():   # (the buffers the call does not write too)
+            raw = _raw(t)
+            mark = np.uint64(MARK_F64) if raw.dtype == np.uint64 else np.int32(MARK_I32)
+            assert (raw[-GUARD:] == mark).all(), f"{key}: written past the batch"
+        e.synchronize()   # a failed device check of the call surfaces here
+        return {key: _raw(o[key]).reshape(-1)[:w.size].copy() for key, w in want.items()}
+
+    def reproject(self, s):
+        from uam_path_planning_amd._lib import GeoGridDesc
+        from uam_path_planning_amd.engine import RasterGeo
+
+        src, (n, _, lon0, lat_top, dlon, dlat), (nx, ny, x0, yt, dx, dy) = S.reproject_inputs(s)
+        gg = GeoGridDesc(n, n, lon0, lat_top, dlon, dlat, -9999.0, 0)
+        geo = RasterGeo(nx=nx, ny=ny, x0=x0, y_top=yt, dx=dx, dy=dy)
+        got = self.e.reproject_dem(src, gg, geo, 1000.0, s["resample"]).cpu().numpy()
+        want = self.ref.reproject(s)
+        assert (want == -9999.0).any() and (want != -9999.0).any()
+        if s["resample"] == 0:
+            np.testing.assert_array_equal(got, want)
+        else:
+            np.testing.assert_array_max_ulp(got, want, maxulp=1)
+
+    def polygons(self, s):
+        import polygons_masks as M
+
+        kind = "divided" if s["divided"] else "small"
+        mask, prm, pieces = M.case(s["mask"], kind)
+        dem = M.dem_of(mask)
+        got = _gpu_polygons(self.e, dem, 0.0, prm)
+        _verify_polygons(self.O, got, (s["mask"], kind), dem, 0.0, prm, pieces)
+
+    def step(self, s):
+        """One step of a sequence; an evaluating step returns the words of its outputs."""
+        k = s["kind"]
+        if k == "geometry":
+            self.ref.geometry(s)
+            self.geometry(s)
+        elif k == "params":
+            self.ref.params(s["params"])
+            self.params(s["params"])
+        elif k in ("k1", "reproject", "polygons"):
+            getattr(self, k)(s)
+        else:
+            o = self.call(s, self.guarded(s))
+            return self.check(s, o)
+
+
+_seed0 = {}   # the seed-0 run, kept for test_replay_after_everything
+
+
+def _run_sequence(oracle_mod, seed):
+    steps = S.draw(seed)
+    run = Run(oracle_mod, steps.start)
+    first = None
+    for i, s in enumerate(steps):
+        try:
+            words = run.step(s)
+        except Exception as exc:
+            kinds = [t["kind"] for t in steps[:i + 1]]
+            raise AssertionError(f"seed {seed}, step {i} ({s['kind']}) after "
+                                 f"{' '.join(kinds[:-1]) or 'nothing'}: {exc}\nstep: {s}") from exc
+        if first is None and s["kind"] in S.EVALUATING and S.is_sorted(s):
+            first = (s, words)
+    return run, steps, first
+
+
+@pytest.mark.parametrize("seed", _seeds())
+def test_sequence_is_bit_exact(oracle_mod, seed):
+    out = _run_sequence(oracle_mod, seed)
+    if seed == 0:
+        _seed0["run"] = out
+
+
+def test_replay_after_everything(oracle_mod):
+    """The first sorted call of the seed-0 sequence once more at the sequence's end, on the same
+    context and on a new one: the same words as the first time, from both."""
+    if "run" not in _seed0:
+        _seed0["run"] = _run_sequence(oracle_mod, 0)
+    run, steps, (s, words) = _seed0["run"]
+    fresh = Run(oracle_mod, steps.start)
+    fresh.rasters = run.rasters   # (device tensors: any context of the device reads them)
+    fresh.ref.rasters = run.ref.rasters
+    for r in (run, fresh):
+        r.ref.geometry(steps.start)   # the step's map and parameters again
+        r.geometry(steps.start)
+        again = r.check(s, r.call(s, r.guarded(s)))
+        assert again.keys() == words.keys()
+        for k in words:
+            np.testing.assert_array_equal(again[k], words[k], err_msg=k)
+
+
+# ---- two streams ------------------------------------------------------------------------------
+_stream_case = {}
+
+
+def _stream_setup(oracle_mod):
+    """The context of the two-stream test with the call on stream A and its reference, made
+    once for both parametrisations."""
+    if _stream_case:
+        return _stream_case
+    start = {"nfz": 8, "map_seed": 2,
+             "params": {"N": 80, "opts": {"length_smooth": False, "penalty_smooth": True,
+                                          "obstacle_smooth": True, "maxratio_smooth": False},
+                        "enl": 0.1, "maxratio": 1.25, "maxalpha": 0.015, "wscale": 1.0}}
+    run = Run(oracle_mod, start)
+    run.k1({"kind": "k1", "raster": 0, "geo": (640, 512, 0.0, 20.0, 60.0 / 640, 60.0 / 512),
+            "thr": 0.0, "k1_rows": 4, "dem_seed": 1})
+    run.k1({"kind": "k1", "raster": 1, "geo": (300, 420, 8.0, 12.0, 0.11, 0.09),
+            "thr": 0.0, "k1_rows": 1, "dem_seed": 3})
+    a = {"kind": "raster_sorted", "raster": 0, "Q": 20000, "D": 5, "N": 80, "pair_seed": 71,
+         "group": 21, "chunk": 0, "terrain": 1, "tbits": 0, "curve": 1, "sim": 1, "cells": True}
+    want = run.ref.expect(a, "K2h+pack", 21)
+    _stream_case.update(run=run, a=a, want_a=want)
+    return _stream_case
+
+
+STREAM_B = {
+    # K2h on the second raster with cells: the low-priority side stream and the fork / join
+    # events A's call uses; groups of 2 make 1.2M items against A's 400k
+    "k2h": {"kind": "raster_sorted", "raster": 1, "Q": 6000, "D": 5, "N": 80, "pair_seed": 72,
+            "group": 2, "chunk": 7, "terrain": 0, "tbits": 5, "curve": 0, "sim": 1,
+            "cells": True},
+    # K4h on a volume: groups of 1 make 1.6M items
+    "k4h": {"kind": "volume", "raster": 1, "nz": 16, "Q": 4000, "D": 5, "N": 80,
+            "pair_seed": 73, "group": 1, "chunk": 8, "terrain": 0, "tbits": 3, "curve": 0,
+            "form": "sorted", "exact": False},
+}
+
+
+@pytest.mark.parametrize("form", ["k2h", "k4h"])
+def test_sorted_forms_on_two_streams(oracle_mod, form):
+    """One context, two streams, no host synchronisation of the test's own between the calls:
+    on stream A some tens of milliseconds of unrelated work and then a K2h call (20 000 pairs
+    x 5, N = 80, with cells); on stream B at once a sorted call that needs a scratch several
+    times A's (so the scratch is reallocated while A's event is pending) under another
+    k2g_curve and tile-bits setting (so the tile-key table A reads is rewritten); then A again
+    under its first setting.  All three equal the oracle bit for bit.
+
+    The test cannot prove that the launches overlapped, nor that the reallocation happened: it
+    sees only the results.  What orders the calls is the library's own event on the scratch;
+    the calls themselves wait on the host where the library does (the table's upload)."""
+    c = _stream_setup(oracle_mod)
+    run, a, b = c["run"], c["a"], STREAM_B[form]
+    e = run.e
+    if form == "k4h":
+        run.volume(b)
+    want_b = run.ref.expect(b, *run.ref.forced(b))
+    dev = lambda x: e.tensor(x, torch.float64)
+    in_a, in_b = (dev(S.pairs_of(a)), dev(S.utab_of(a))), (dev(S.pairs_of(b)), dev(S.utab_of(b)))
+    outs = [run.guarded(a), run.guarded(b), run.guarded(a)]
+    busy = torch.zeros(1 << 28, dtype=torch.float32, device=e.torch_device)
+    torch.cuda.synchronize()
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+
+    def launch(s, inputs, outputs, stream):
+        run.options(s)
+        with torch.cuda.stream(stream):
+            if s["kind"] == "volume":
+                e.eval_generated3d(*inputs, run.vol[1], outputs=outputs)
+            else:
+                e.eval_generated(*inputs, raster=run.rasters[s["raster"]], want_cells=True,
+                                 outputs=outputs)
+        return e.last_kernel(), e.last_group()
+
+    with torch.cuda.stream(sa):
+        for _ in range(40):   # 2 GiB of traffic a pass
+            busy.mul_(1.0001).add_(1.0)
+    ran = [launch(a, in_a, outs[0], sa), launch(b, in_b, outs[1], sb),
+           launch(a, in_a, outs[2], sa)]
+    torch.cuda.synchronize()
+    assert ran == [("K2h+pack", 21), run.ref.forced(b), ("K2h+pack", 21)]
+    for s, (o, _), want in ((a, outs[0], c["want_a"]), (b, outs[1], want_b),
+                            (a, outs[2], c["want_a"])):
+        P, Q, W = s["Q"] * s["D"], s["Q"], s["N"] + 2
+        for key, w in want.items():
+            n = Q if key in S.BEST_KEYS else P * W if key == "cells" else P
+            raw = _raw(o[key]).reshape(-1)
+            mark = np.uint64(MARK_F64) if raw.dtype == np.uint64 else np.int32(MARK_I32)
+            assert not (raw[:n] == mark).any(), f"{s['kind']} {key}: never written"
+            assert (raw[-GUARD:] == mark).all(), f"{s['kind']} {key}: written past the batch"
+            np.testing.assert_array_equal(o[key].cpu().numpy().reshape(-1)[:n].reshape(w.shape),
+                                          w, err_msg=f"{s['kind']} {key}")
+    e.synchronize()
+
+
+# ---- two contexts -----------------------------------------------------------------------------
+def test_two_contexts_interleaved(oracle_mod):
+    """Two contexts alive at once, with different maps and parameters, taking turns at
+    dem_polygons, a sorted raster call and an analytic call for three rounds: each result equals
+    its own oracle (the K8 arenas are reached through thread-local pointers to "the calling
+    context's", the "attributes raised" flags are per context)."""
+    opts = {"length_smooth": False, "penalty_smooth": True, "obstacle_smooth": True,
+            "maxratio_smooth": False}
+    starts = [{"nfz": 8, "map_seed": 5,
+               "params": {"N": 40, "opts": dict(opts), "enl": 0.1, "maxratio": 1.25,
+                          "maxalpha": 0.3, "wscale": 1.0}},
+              {"nfz": 32, "map_seed": 9,
+               "params": {"N": 7, "opts": dict(opts, length_smooth=True, obstacle_smooth=False),
+                          "enl": 0.35, "maxratio": 2.0, "maxalpha": 0.05, "wscale": 3.7}}]
+    k1 = [{"kind": "k1", "raster": 0, "geo": (310, 200, 2.0, 18.0, 0.18, 0.21), "thr": 0.0,
+           "k1_rows": 8, "dem_seed": 2},
+          {"kind": "k1", "raster": 0, "geo": (150, 260, 10.0, 15.0, 0.25, 0.2), "thr": 100.0,
+           "k1_rows": 2, "dem_seed": 4}]
+    rounds = [[{"kind": "polygons", "mask": "noise59", "divided": True},
+               {"kind": "raster_sorted", "raster": 0, "Q": 700, "D": 5, "N": 40, "pair_seed": 81,
+                "group": 9, "chunk": 0, "terrain": 1, "tbits": 0, "curve": 1, "sim": 1,
+                "cells": True},
+               {"kind": "analytic", "Q": 300, "D": 5, "N": 40, "pair_seed": 82,
+                "k3b_segment": 8, "pair_order": 1}],
+              [{"kind": "polygons", "mask": "spiral", "divided": False},
+               {"kind": "raster_sorted", "raster": 0, "Q": 1900, "D": 2, "N": 7, "pair_seed": 83,
+                "group": 4, "chunk": 11, "terrain": 0, "tbits": 5, "curve": 0, "sim": 1,
+                "cells": False},
+               {"kind": "analytic", "Q": 450, "D": 2, "N": 7, "pair_seed": 84,
+                "k3b_segment": 0, "pair_order": 0}]]
+    runs = [Run(oracle_mod, st) for st in starts]
+    for r, s in zip(runs, k1):
+        r.k1(s)
+    first = {}
+    for rnd in range(3):
+        for j in range(3):
+            for i, r in enumerate(runs):
+                words = r.step(rounds[i][j])
+                if words is not None:   # the same call, the same words every round
+                    for k, w in first.setdefault((i, j), words).items():
+                        np.testing.assert_array_equal(words[k], w, err_msg=f"{i} {j} {k}")

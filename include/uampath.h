@@ -575,7 +575,8 @@ int uam_kernel_time(uam_ctx* ctx, double* ms_total, int64_t* launches);
  * (lane per path), "K2w" (wave per path), "K2d" (D > 16), "K3b", "K3", "K3d", "K4", "K4w";
  * "K4e" / "K4ew" (uam_eval_waypoints3d lane / wave per path), "K4p"
  * (uam_eval_generated3d_profiles), "K4e+v" / "K4ew+v" / "K4p+v" (their _v forms with the
- * vertical terms); "K9" (uam_route_field) / "K9t" (uam_route_paths); "" before the first call.
+ * vertical terms); "K9" (uam_route_field) / "K9t" (uam_route_paths) / "K9b"
+ * (uam_route_free_bits) / "K9s" (uam_route_paths_smooth); "" before the first call.
  * The string is static (never freed).  For benchmarks and tests:
  * which kernel a number belongs to. */
 const char* uam_last_kernel(const uam_ctx* ctx);
@@ -1003,6 +1004,74 @@ int uam_route_paths_host(const uam_raster_desc* desc, const void* rec,
                          const double* goals, int32_t n_goals, const double* starts,
                          const int32_t* goal_idx, int64_t n_queries, int32_t N, double* wp,
                          int32_t* status, int32_t* steps);
+
+/* Route seeds, smoothing (K9b / K9s): any-angle shortcuts on the traced path.  An 8-connected
+ * route turns by 45 degrees per kink; these calls keep of the traced cell chain only the cells
+ * from which the next one kept is no longer in straight sight, and resample that polyline.
+ *
+ * Definition (normative; independent statement: tests/route_smooth_ref.py).  The trace is
+ * uam_route_paths': the status rules, steps and the cell chain c_0 = s, c_1, .., c_{n-1} = g
+ * along next (n = steps) are unchanged.  Smoothing chooses a subsequence of the interior cells;
+ * the vertices and the resampling are uam_route_paths' own rules applied to that subsequence.
+ *   touched    for cells A = (ax, ay), B = (bx, by), d = (bx - ax, by - ay): T(A, B) is the set
+ *              of cells (x, y) in the integer bounding box of A and B with
+ *              2*|dx*(y - ay) - dy*(x - ax)| <= |dx| + |dy|: the closed supercover of the
+ *              segment between the two cell centres (a segment through a cell corner touches
+ *              all four cells around it).  Integers only; |dx|, |dy| <= span <= 1024.
+ *   visible    LOS(A, B) holds iff every cell of T(A, B) is free (not blocked, inflation
+ *              included).  Adjacent chain cells are always visible: a diagonal step's T is the
+ *              2 x 2 square, free by the corner rule.
+ *   anchors    none for n <= 2.  Otherwise a_0 = 1; a_{k+1} = the largest j <= min(a_k + span,
+ *              n - 2) such that LOS(c_{a_k}, c_i) holds for every i in (a_k, j] ("advance while
+ *              visible", not "the farthest visible"; never less than a_k + 1); stop at a_k =
+ *              n - 2.  c_1 and c_{n-2} are always kept: the start and goal points are no cell
+ *              centres, so the first and last segments stay the ones uam_route_paths flies.
+ *   vertices   V_0 = the start point, the centres of c_{a_0}, c_{a_1}, .., V_m = the goal
+ *              point.  S_i, the waypoints p_j, the straight line of a nonzero status and the
+ *              status values: uam_route_paths' text, word for word.  vertices[q] = m + 1 (2 +
+ *              the number of anchors); 0 for a nonzero status.
+ *   guarantee  every point of a segment lies in a closed cell of its T, all free: every
+ *              waypoint of a status-0 path lies in a free cell.
+ *   bridge     span = 1 keeps every interior cell: wp, status and steps are uam_route_paths'
+ *              bits.
+ * The shortcut test is geometric: it does not weigh phi along the segment; span bounds how far
+ * a shortcut may leave the field's route.
+ *
+ * uam_route_free_bits: the free cells of (desc, rec_dev, params) as one bit per cell, set =
+ * free, row-major, bit ix & 31 of word iy * ((nx + 31) / 32) + ix / 32 (rows padded to uint32
+ * words, the padding 0), uam_route_free_bits_bytes(desc) bytes (-1 for a bad descriptor),
+ * 4-B aligned.  uam_last_kernel: "K9b".  Failures as uam_route_field's for ctx / desc / params /
+ * a NULL buffer.
+ * uam_route_paths_smooth: uam_route_paths with shortcuts of at most span chain cells, 1 <= span
+ * <= UAM_ROUTE_SPAN_MAX, against bits_dev and next_dev of the same desc, rec and params (the
+ * start's blocking is read from the bits); steps_dev and vertices_dev may be NULL.  One wave
+ * per query; a query with more than UAM_ROUTE_SMOOTH_LIST anchors is smoothed twice (no output
+ * depends on that).  Asynchronous.  uam_last_kernel: "K9s".  UAM_E_INVALID before any launch
+ * for ctx / desc / a buffer NULL, a bad descriptor, span outside the range, n_goals < 1 or too
+ * many cells, nx*ny > 2^31 - 1 - UAM_ROUTE_SPAN_MAX (chain indices are int32), n_queries < 0 or
+ * too large; UAM_E_STATE without uam_set_params.
+ * The _host calls run the same inline functions without a GPU.  uam_route_visible_host: the
+ * library's LOS on n pairs of cell indices (iy * nx + ix; UAM_E_INVALID for one off the
+ * raster) into out_u8 (1 = visible). */
+#define UAM_ROUTE_SPAN_MAX 1024
+#define UAM_ROUTE_SMOOTH_LIST 256
+int64_t uam_route_free_bits_bytes(const uam_raster_desc* desc);
+int uam_route_free_bits(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec_dev,
+                        const uam_route_params* params, uint32_t* bits_dev, uam_stream stream);
+int uam_route_paths_smooth(uam_ctx* ctx, const uam_raster_desc* desc, const uint32_t* bits_dev,
+                           const uint8_t* next_dev, const double* goals_dev, int32_t n_goals,
+                           const double* starts_dev, const int32_t* goal_idx_dev,
+                           int64_t n_queries, int32_t span, double* wp_dev, int32_t* status_dev,
+                           int32_t* steps_dev, int32_t* vertices_dev, uam_stream stream);
+int uam_route_free_bits_host(const uam_raster_desc* desc, const void* rec,
+                             const uam_route_params* params, uint32_t* bits);
+int uam_route_paths_smooth_host(const uam_raster_desc* desc, const uint32_t* bits,
+                                const uint8_t* next, const double* goals, int32_t n_goals,
+                                const double* starts, const int32_t* goal_idx,
+                                int64_t n_queries, int32_t N, int32_t span, double* wp,
+                                int32_t* status, int32_t* steps, int32_t* vertices);
+int uam_route_visible_host(const uam_raster_desc* desc, const uint32_t* bits, int64_t n,
+                           const int32_t* a_cells, const int32_t* b_cells, uint8_t* out_u8);
 
 /* Workspace bytes uam_refine needs for n_paths (after uam_set_geometry/uam_set_params). */
 int64_t uam_refine_workspace_bytes(uam_ctx* ctx, int64_t n_paths,

@@ -4,9 +4,10 @@ goals drawn from a small set of vertiports so that one cost-to-go field serves m
 Refines the 5 arc candidates of every pair, and separately the route seed
 (Engine.route_field -> route_paths), and prints the share of pairs whose best candidate reaches
 sum g^2 <= 1e-3 with the arcs alone and with the arcs plus the seed, for n_restart 0 and 1,
-plus the seed's own share.
+plus the seed's own share.  --smooth SPAN .. repeats the seed's rows per span of
+route_paths(..., smooth=SPAN) (0: the unsmoothed trace), with the mean vertices per path.
 usage: python tools/route_seed_feasibility.py [--pairs Q] [--ports V] [--N N] [--R R]
-       [--lam L] [--inflate I] [--seed S]"""
+       [--lam L] [--inflate I] [--seed S] [--smooth SPAN ..]"""
 import argparse
 import json
 import os
@@ -27,6 +28,8 @@ def main():
     ap.add_argument("--inflate", type=int, default=1)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--threshold", type=float, default=1e-3)
+    ap.add_argument("--smooth", type=int, nargs="*", default=[0],
+                    help="spans of route_paths' smooth (0: none), one set of seed rows each")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -63,7 +66,8 @@ def main():
     field = eng.route_field(raster, ports, lam=a.lam, inflate=a.inflate)
     torch.cuda.synchronize()
     t_field = time.perf_counter() - t0
-    seed = eng.route_paths(field, starts, gi)
+    seeds = {span: eng.route_paths(field, starts, gi, smooth=span) for span in a.smooth}
+    seed = seeds[a.smooth[0]]
     status = seed["status"].cpu().numpy()
     arcs = eng.gen_paths(torch.tensor(pairs, device="cuda"), arc_table(a.N, displacements(5)))
     seed_hits = eng.eval_waypoints(seed["wp"], raster=raster)["nfz_hits"].cpu().numpy()
@@ -74,19 +78,30 @@ def main():
            "seed_status_counts": {int(k): int((status == k).sum()) for k in np.unique(status)},
            "seed_unrefined_share_nfz_free": float((seed_hits[status == 0] == 0).mean()),
            "pairs_share_with_an_nfz_free_arc": float((arc_hits == 0).any(axis=1).mean())}
+    ok = status == 0
+    for span, sd in seeds.items():
+        if span:
+            hits = eng.eval_waypoints(sd["wp"], raster=raster)["nfz_hits"].cpu().numpy()
+            out[f"smooth_{span}"] = {
+                "vertices_mean": float(sd["vertices"].cpu().numpy()[ok].mean()),
+                "steps_mean": float(sd["steps"].cpu().numpy()[ok].mean()),
+                "seed_unrefined_share_nfz_free": float((hits[ok] == 0).mean())}
     for n_restart in (0, 1):
         rp = {"n_restart": n_restart}
         ia = eng.refine(arcs, rp)["infeas"].cpu().numpy().reshape(Q, 5).min(axis=1)
-        isd = eng.refine(seed["wp"], rp)["infeas"].cpu().numpy()
-        isd = np.where(status == 0, isd, np.inf)   # a failed seed is the straight line: no seed
-        out[f"n_restart_{n_restart}"] = {
-            "pairs_share_arcs": float((ia <= a.threshold).mean()),
-            "pairs_share_arcs_plus_seed": float((np.minimum(ia, isd) <= a.threshold).mean()),
-            "seed_share": float((isd <= a.threshold).mean()),
-            "seed_rescues": int(((isd <= a.threshold) & (ia > a.threshold)).sum()),
-            "seed_median_infeas": float(np.median(isd[np.isfinite(isd)])) if
-            np.isfinite(isd).any() else None,
-            "arcs_median_best_infeas": float(np.median(ia))}
+        for span, sd in seeds.items():
+            isd = eng.refine(sd["wp"], rp)["infeas"].cpu().numpy()
+            isd = np.where(ok, isd, np.inf)   # a failed seed is the straight line: no seed
+            key = f"n_restart_{n_restart}" + (f"_smooth_{span}" if span else "")
+            out[key] = {
+                "pairs_share_arcs": float((ia <= a.threshold).mean()),
+                "pairs_share_arcs_plus_seed": float((np.minimum(ia, isd) <= a.threshold).mean()),
+                "seed_share": float((isd <= a.threshold).mean()),
+                "seed_rescues": int(((isd <= a.threshold) & (ia > a.threshold)).sum()),
+                "seed_median_infeas": float(np.median(isd[np.isfinite(isd)])) if
+                np.isfinite(isd).any() else None,
+                "arcs_median_best_infeas": float(np.median(ia))}
+            print(json.dumps({key: out[key]}), flush=True)
     print(json.dumps(out))
 
 

@@ -1,8 +1,11 @@
 """Time the route seeds (K9) on the cfg3 raster: uam_route_field per UAM_OPT_K9_TILE x
 UAM_OPT_K9_INNER (host wall ms of the whole call, rounds, tile visits, visits per tile) for a
 goal near the centre and one in a corner, checking that every setting gives the same bits, then
-uam_route_paths at --queries starts.  One JSON line per measurement.
-usage: python tools/time_route.py [--R R] [--queries Q] [--lam L] [--inflate I]"""
+uam_route_paths at --queries starts, uam_route_free_bits, and uam_route_paths_smooth per
+--smooth SPAN (its bits at span 1 checked against uam_route_paths').  One JSON line per
+measurement.
+usage: python tools/time_route.py [--R R] [--queries Q] [--lam L] [--inflate I]
+       [--smooth SPAN ..] [--no-sweep]"""
 import argparse
 import json
 import os
@@ -21,6 +24,10 @@ def main():
     ap.add_argument("--queries", type=int, default=100000)
     ap.add_argument("--lam", type=float, default=1.0)
     ap.add_argument("--inflate", type=int, default=0)
+    ap.add_argument("--smooth", type=int, nargs="*", default=[],
+                    help="spans to time uam_route_paths_smooth at")
+    ap.add_argument("--no-sweep", action="store_true",
+                    help="skip the tile x inner sweep of uam_route_field")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -49,7 +56,7 @@ def main():
     goals = {"centre": free_near(30.0, -10.0), "corner": free_near(0.4, 19.6)}
     print(json.dumps({"goals": {k: v.tolist() for k, v in goals.items()}}), flush=True)
     first = {}
-    for tile, inner in COMBOS:
+    for tile, inner in ([] if a.no_sweep else COMBOS):
         for name, g in goals.items():
             eng.set_option("k9_tile", tile)
             eng.set_option("k9_inner", inner)
@@ -85,7 +92,49 @@ def main():
     print(json.dumps({"route_paths_queries": a.queries, "ms": round(e0.elapsed_time(e1), 3),
                       "status_counts": {int(k): int((st == k).sum()) for k in np.unique(st)},
                       "steps_mean": float(steps[st == 0].mean()) if (st == 0).any() else None,
-                      "steps_max": int(steps.max())}))
+                      "steps_max": int(steps.max())}), flush=True)
+    if not a.smooth:
+        return
+
+    def timed(fn, reps=3):
+        """ms of each of reps calls (events around the call), after one untimed call."""
+        out = fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(reps):
+            e0.record()
+            out = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(round(e0.elapsed_time(e1), 3))
+        return out, ms
+
+    _, ms = timed(lambda: eng.route_paths(f, s, gi))
+    print(json.dumps({"route_paths_queries": a.queries, "ms_each": ms}), flush=True)
+
+    def build_bits():
+        f.free_bits = None
+        return eng.route_free_bits(f)
+
+    bits, ms = timed(build_bits)
+    print(json.dumps({"route_free_bits": True, "ms_each": ms, "bytes": bits.numel() * 4}),
+          flush=True)
+    one = eng.route_paths(f, s, gi, smooth=1)
+    print(json.dumps({"span_1_equals_route_paths": bool(
+        torch.equal(one["wp"].view(torch.int64), o["wp"].view(torch.int64))
+        and torch.equal(one["status"], o["status"]) and torch.equal(one["steps"], o["steps"]))}),
+        flush=True)
+    ok = torch.as_tensor(st == 0, device=o["status"].device)
+    for span in a.smooth:
+        sm, ms = timed(lambda: eng.route_paths(f, s, gi, smooth=span))
+        v = sm["vertices"][ok].double()
+        print(json.dumps({"route_paths_smooth_span": span, "queries": a.queries, "ms_each": ms,
+                          "vertices_mean": float(v.mean()) if v.numel() else None,
+                          "vertices_max": int(v.max()) if v.numel() else None,
+                          "same_status_and_steps": bool(torch.equal(sm["status"], o["status"])
+                                                        and torch.equal(sm["steps"],
+                                                                        o["steps"]))}),
+              flush=True)
 
 
 if __name__ == "__main__":

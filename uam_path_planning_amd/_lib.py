@@ -28,6 +28,8 @@ OPTIONS = {"group": 1, "sorted_min_paths": 2, "k2s_segments": 3, "wave_max_paths
            "test_sort_fault": 22, "exact_sum": 23, "exact_sum_volume": 24}
 # the route seeds' options (K9; UAM_OPT_K9_TILE / UAM_OPT_K9_INNER), which no output depends on
 ROUTE_OPTIONS = {"k9_tile": 27, "k9_inner": 28}
+# uam_route_paths_smooth: the largest span, and the anchors K9s keeps for its resampling pass
+ROUTE_SPAN_MAX, ROUTE_SMOOTH_LIST = 1024, 256
 INEQ_HALFPLANE, INEQ_ELLIPSE, INEQ_AXIS = 0, 1, 2
 MODE_ANALYTIC, MODE_RASTER, MODE_VOLUME = 0, 1, 2
 FLAG_NFZ, FLAG_MASK, FLAG_NODATA = 1, 2, 4
@@ -233,6 +235,20 @@ SIGNATURES = {
                                             ctypes.POINTER(RouteParams), _vp, _vp, ctypes.c_int32,
                                             _vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp,
                                             _vp]),
+    "uam_route_free_bits_bytes": (ctypes.c_int64, [ctypes.POINTER(RasterDesc)]),
+    "uam_route_free_bits": (ctypes.c_int, [_vp, ctypes.POINTER(RasterDesc), _vp,
+                                           ctypes.POINTER(RouteParams), _vp, _vp]),
+    "uam_route_paths_smooth": (ctypes.c_int, [_vp, ctypes.POINTER(RasterDesc), _vp, _vp, _vp,
+                                              ctypes.c_int32, _vp, _vp, ctypes.c_int64,
+                                              ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "uam_route_free_bits_host": (ctypes.c_int, [ctypes.POINTER(RasterDesc), _vp,
+                                                ctypes.POINTER(RouteParams), _vp]),
+    "uam_route_paths_smooth_host": (ctypes.c_int, [ctypes.POINTER(RasterDesc), _vp, _vp, _vp,
+                                                   ctypes.c_int32, _vp, _vp, ctypes.c_int64,
+                                                   ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
+                                                   _vp]),
+    "uam_route_visible_host": (ctypes.c_int, [ctypes.POINTER(RasterDesc), _vp, ctypes.c_int64,
+                                              _vp, _vp, _vp]),
     "uam_refine_workspace_bytes": (ctypes.c_int64, [_vp, ctypes.c_int64,
                                                     ctypes.POINTER(RefineParams)]),
     "uam_refine": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.POINTER(RefineParams), _vp,

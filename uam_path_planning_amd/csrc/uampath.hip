@@ -6276,6 +6276,8 @@ __global__ __launch_bounds__(1024) void k_g_final(KParams p, KGrp kg, KOut out,
 
 // K9: route seeds, k_route_cost, k_route_init, k_route_relax, k_route_next, k_route_trace
 #include "k9_route.inc"
+// K9b / K9s: any-angle shortcuts on the traced route, k_route_free_bits, k_route_smooth
+#include "k9_smooth.inc"
 
 // closes the anonymous namespace opened above the device-side tables
 }  // namespace
@@ -9440,6 +9442,144 @@ int uam_route_paths_host(const uam_raster_desc* desc, const void* rec,
     for (int64_t q = 0; q < n_queries; ++q)
         r9_trace(g, (const uint4*)rec, next, goals, n_goals, starts, goal_idx, q, N, wp, status,
                  steps);
+    return UAM_OK;
+}
+
+// ---- K9b / K9s: shortcuts on the traced route (k9_smooth.inc) ---------------------------------
+// the grid alone (the smoothing calls take no uam_route_params: blocking comes from the bits)
+static int route_grid(const uam_raster_desc* desc, KRoute* g) {
+    KRaster kr{};
+    const int st = make_kraster(desc, &kr);
+    if (st) return st;
+    g->nx = kr.nx, g->ny = kr.ny;
+    g->x0 = kr.x0, g->y_top = kr.y_top, g->dx = kr.dx, g->dy = kr.dy;
+    g->inv_dx = kr.inv_dx, g->inv_dy = kr.inv_dy;
+    r9_set_lengths(g);
+    return UAM_OK;
+}
+
+static int route_smooth_ok(const KRoute& g, int32_t n_goals, int64_t n_queries, int32_t span) {
+    const int st = route_goals_ok(g, n_goals);
+    if (st) return st;
+    if (n_queries < 0) return fail(UAM_E_INVALID, "route n_queries < 0");
+    if (span < 1 || span > UAM_ROUTE_SPAN_MAX)
+        return fail(UAM_E_INVALID, "route span %d outside [1, %d]", span, UAM_ROUTE_SPAN_MAX);
+    // chain indices are int32 and the kernel forms a + span
+    if ((int64_t)g.nx * g.ny > (int64_t)INT32_MAX - UAM_ROUTE_SPAN_MAX)
+        return fail(UAM_E_INVALID, "route smoothing needs nx*ny <= 2^31 - 1 - %d",
+                    UAM_ROUTE_SPAN_MAX);
+    return UAM_OK;
+}
+
+int64_t uam_route_free_bits_bytes(const uam_raster_desc* desc) {
+    KRoute g{};
+    if (route_grid(desc, &g)) return -1;
+    return (int64_t)g.ny * r9s_wpr(g.nx) * 4;
+}
+
+int uam_route_free_bits(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
+                        const uam_route_params* params, uint32_t* bits, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    KRoute g{};
+    const int st = route_setup(desc, params, &g);
+    if (st) return st;
+    if (!rec || !bits) return fail(UAM_E_INVALID, "uam_route_free_bits: rec / bits is NULL");
+    if ((uintptr_t)bits & 3) return fail(UAM_E_INVALID, "route free bits not 4-B aligned");
+    DeviceGuard dg(ctx->device);
+    const int64_t chunks = (((int64_t)g.nx + 63) >> 6) * g.ny;
+    hipLaunchKernelGGL(k_route_free_bits, dim3(grid_for(chunks * 64, R9_THREADS, 1 << 16)),
+                       dim3(R9_THREADS), 0, (hipStream_t)stream, (const uint4*)rec, g, bits);
+    HIP_TRY(hipGetLastError());
+    ctx->last_kernel = "K9b";
+    return UAM_OK;
+}
+
+int uam_route_paths_smooth(uam_ctx* ctx, const uam_raster_desc* desc, const uint32_t* bits,
+                           const uint8_t* next, const double* goals, int32_t n_goals,
+                           const double* starts, const int32_t* goal_idx, int64_t n_queries,
+                           int32_t span, double* wp, int32_t* status, int32_t* steps,
+                           int32_t* vertices, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
+    KRoute g{};
+    int st = route_grid(desc, &g);
+    if (st) return st;
+    if ((st = route_smooth_ok(g, n_goals, n_queries, span))) return st;
+    if (n_queries == 0) return UAM_OK;
+    if (!bits || !next || !goals || !starts || !goal_idx || !wp || !status)
+        return fail(UAM_E_INVALID, "uam_route_paths_smooth: a buffer is NULL");
+    if (n_queries >= ((int64_t)1 << 31) * R9S_WAVES)
+        return fail(UAM_E_INVALID, "route n_queries too large");
+    DeviceGuard dg(ctx->device);
+    const int64_t blocks = (n_queries + R9S_WAVES - 1) / R9S_WAVES;
+    hipLaunchKernelGGL(k_route_smooth, dim3((unsigned)blocks), dim3(R9S_WAVES * 64), 0,
+                       (hipStream_t)stream, g, bits, next, goals, n_goals, starts, goal_idx,
+                       n_queries, ctx->kp.N, span, wp, status, steps, vertices);
+    HIP_TRY(hipGetLastError());
+    ctx->last_kernel = "K9s";
+    return UAM_OK;
+}
+
+int uam_route_free_bits_host(const uam_raster_desc* desc, const void* rec,
+                             const uam_route_params* params, uint32_t* bits) {
+    KRoute g{};
+    const int st = route_setup(desc, params, &g);
+    if (st) return st;
+    if (!rec || !bits) return fail(UAM_E_INVALID, "uam_route_free_bits_host: rec / bits is NULL");
+    const int wpr = r9s_wpr(g.nx);
+    for (int iy = 0; iy < g.ny; ++iy)
+        for (int w = 0; w < wpr; ++w) {
+            uint32_t m = 0u;
+            for (int b = 0; b < 32 && (int64_t)w * 32 + b < g.nx; ++b)
+                if (r9_cost(g, (const uint4*)rec, w * 32 + b, iy) < r9_inf()) m |= 1u << b;
+            bits[(int64_t)iy * wpr + w] = m;
+        }
+    return UAM_OK;
+}
+
+int uam_route_paths_smooth_host(const uam_raster_desc* desc, const uint32_t* bits,
+                                const uint8_t* next, const double* goals, int32_t n_goals,
+                                const double* starts, const int32_t* goal_idx,
+                                int64_t n_queries, int32_t N, int32_t span, double* wp,
+                                int32_t* status, int32_t* steps, int32_t* vertices) {
+    KRoute g{};
+    int st = route_grid(desc, &g);
+    if (st) return st;
+    if ((st = route_smooth_ok(g, n_goals, n_queries, span))) return st;
+    if (N < 0) return fail(UAM_E_INVALID, "route N < 0");
+    if (n_queries == 0) return UAM_OK;
+    if (!bits || !next || !goals || !starts || !goal_idx || !wp || !status)
+        return fail(UAM_E_INVALID, "uam_route_paths_smooth_host: a buffer is NULL");
+    std::vector<int32_t> cells, anchors;
+    for (int64_t q = 0; q < n_queries; ++q)
+        r9s_smooth_host(g, bits, next, goals, n_goals, starts, goal_idx, q, N, span, wp, status,
+                        steps, vertices, cells, anchors);
+    return UAM_OK;
+}
+
+int uam_route_visible_host(const uam_raster_desc* desc, const uint32_t* bits, int64_t n,
+                           const int32_t* a_cells, const int32_t* b_cells, uint8_t* out) {
+    KRoute g{};
+    const int st = route_grid(desc, &g);
+    if (st) return st;
+    if (n < 0) return fail(UAM_E_INVALID, "uam_route_visible_host: n < 0");
+    if (n == 0) return UAM_OK;
+    if (!bits || !a_cells || !b_cells || !out)
+        return fail(UAM_E_INVALID, "uam_route_visible_host: a buffer is NULL");
+    const int64_t cells = (int64_t)g.nx * g.ny;
+    for (int64_t i = 0; i < n; ++i)
+        if (a_cells[i] < 0 || a_cells[i] >= cells || b_cells[i] < 0 || b_cells[i] >= cells)
+            return fail(UAM_E_INVALID, "uam_route_visible_host: pair %lld is off the raster",
+                        (long long)i);
+    const int wpr = r9s_wpr(g.nx);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t ax = a_cells[i] % g.nx, ay = a_cells[i] / g.nx;
+        const int64_t bx = b_cells[i] % g.nx, by = b_cells[i] / g.nx;
+        const int64_t far = std::max(std::llabs(bx - ax), std::llabs(by - ay));
+        // the kernel's 32-bit walk wherever a span can reach, 64-bit beyond
+        out[i] = far <= UAM_ROUTE_SPAN_MAX ? r9s_visible(bits, g.nx, a_cells[i], b_cells[i])
+                                           : r9s_los<int64_t>(bits, wpr, ax, ay, bx, by);
+    }
     return UAM_OK;
 }
 

@@ -157,7 +157,9 @@ class RouteField:
     255 = no route), goals [G, 2], rounds = relaxation rounds of all goals together, visits =
     tiles those rounds visited.  rec and the parameters are kept for route_paths (the start's
     blocking is read from rec).  Device tensors from route_field, numpy arrays from
-    route_field_host.  A derived, untracked product of rec: rebuild it when rec changes."""
+    route_field_host.  A derived, untracked product of rec: rebuild it when rec changes.
+    free_bits: the free cells as one bit per cell ([ny, (nx + 31) // 32] 32-bit words;
+    Engine.route_free_bits), built and kept here by the first route_paths(..., smooth >= 1)."""
     geo: RasterGeo
     goals: object = field(repr=False)
     dist: object = field(repr=False)
@@ -168,6 +170,7 @@ class RouteField:
     lam: float = 1.0
     block_flags: int = _lib.FLAG_NFZ
     inflate: int = 0
+    free_bits: object = field(default=None, repr=False)
 
     def params(self, max_rounds=0):
         return _route_params(self.lam, self.block_flags, self.inflate, max_rounds)
@@ -869,12 +872,31 @@ class Engine:
                           int(self.lib.uam_route_visits(self._ctx)), raster.rec, float(lam),
                           int(block_flags), int(inflate))
 
-    def route_paths(self, field, starts, goal_idx):
+    def route_free_bits(self, field):
+        """The free cells of a RouteField's raster and parameters as one bit per cell
+        (uam_route_free_bits, K9b): [ny, (nx + 31) // 32] int32 words, bit ix & 31 of word
+        ix // 32 set = free.  Computed once and kept on the field."""
+        if field.free_bits is None:
+            torch = _torch()
+            geo = field.geo
+            bits = self.empty((geo.ny, (geo.nx + 31) // 32), torch.int32)
+            rp = field.params()
+            _lib.check(self.lib.uam_route_free_bits(
+                self._ctx, ctypes.byref(geo.as_struct()), _ptr(field.rec), ctypes.byref(rp),
+                _ptr(bits), self.stream), "uam_route_free_bits")
+            field.free_bits = bits
+        return field.free_bits
+
+    def route_paths(self, field, starts, goal_idx, smooth=0):
         """Seed paths through a RouteField (uam_route_paths): starts [Q, 2], goal_idx [Q] into
         field.goals.  Returns {"wp" [Q, N+2, 2], "status" [Q], "steps" [Q]} (device tensors);
         status 0 ok, 1 start off the raster or blocked, 2 goal unreachable, 3 walk too long,
         4 bad goal -- a nonzero status leaves the straight line in wp.  wp is what
-        eval_waypoints and refine take."""
+        eval_waypoints and refine take.
+        smooth >= 1 (uam_route_paths_smooth, K9s): any-angle shortcuts over at most smooth
+        chain cells (1..1024) wherever the cells between lie in straight sight; adds "vertices"
+        [Q] (the polyline's vertices, end points included; 0 for a nonzero status).  smooth = 1
+        keeps every cell: the bits of smooth = 0."""
         torch = _torch()
         s = self.tensor(starts, torch.float64).reshape(-1, 2)
         gi = self.tensor(goal_idx, torch.int32).reshape(-1)
@@ -884,6 +906,15 @@ class Engine:
         N = self.params.N
         out = {"wp": self.empty((Q, N + 2, 2), torch.float64),
                "status": self.empty((Q,), torch.int32), "steps": self.empty((Q,), torch.int32)}
+        if smooth:
+            out["vertices"] = self.empty((Q,), torch.int32)
+            bits = self.route_free_bits(field)
+            _lib.check(self.lib.uam_route_paths_smooth(
+                self._ctx, ctypes.byref(field.geo.as_struct()), _ptr(bits), _ptr(field.next),
+                _ptr(field.goals), field.goals.shape[0], _ptr(s), _ptr(gi), Q, int(smooth),
+                _ptr(out["wp"]), _ptr(out["status"]), _ptr(out["steps"]),
+                _ptr(out["vertices"]), self.stream), "uam_route_paths_smooth")
+            return out
         rp = field.params()
         _lib.check(self.lib.uam_route_paths(
             self._ctx, ctypes.byref(field.geo.as_struct()), _ptr(field.rec), ctypes.byref(rp),
@@ -909,9 +940,24 @@ class Engine:
         return RouteField(geo, g, dist, nxt, 0, 0, r, float(lam), int(block_flags), int(inflate))
 
     @staticmethod
-    def route_paths_host(field, starts, goal_idx, N):
+    def route_free_bits_host(field):
+        """route_free_bits on the host (uam_route_free_bits_host) for a RouteField of numpy
+        arrays: [ny, (nx + 31) // 32] uint32, kept on the field."""
+        if field.free_bits is None:
+            geo = field.geo
+            bits = np.empty((geo.ny, (geo.nx + 31) // 32), dtype=np.uint32)
+            rp = field.params()
+            _lib.check(_lib.load().uam_route_free_bits_host(
+                ctypes.byref(geo.as_struct()), _host_rec(field.rec, geo).ctypes.data,
+                ctypes.byref(rp), bits.ctypes.data), "uam_route_free_bits_host")
+            field.free_bits = bits
+        return field.free_bits
+
+    @staticmethod
+    def route_paths_host(field, starts, goal_idx, N, smooth=0):
         """route_paths on the host (uam_route_paths_host; needs no GPU) for a RouteField of
-        numpy arrays; N interior waypoints.  Returns {"wp", "status", "steps"} numpy arrays."""
+        numpy arrays; N interior waypoints.  Returns {"wp", "status", "steps"} numpy arrays,
+        and "vertices" for smooth >= 1 (uam_route_paths_smooth_host)."""
         s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 2)
         gi = np.ascontiguousarray(goal_idx, dtype=np.int32).reshape(-1)
         Q = s.shape[0]
@@ -923,6 +969,16 @@ class Engine:
         rp = field.params()
         nxt = np.ascontiguousarray(field.next, dtype=np.uint8)
         goals = np.ascontiguousarray(field.goals, dtype=np.float64)
+        if smooth:
+            out["vertices"] = np.empty((Q,), dtype=np.int32)
+            bits = Engine.route_free_bits_host(field)
+            _lib.check(_lib.load().uam_route_paths_smooth_host(
+                ctypes.byref(field.geo.as_struct()), bits.ctypes.data, nxt.ctypes.data,
+                goals.ctypes.data, goals.shape[0], s.ctypes.data, gi.ctypes.data, Q, N,
+                int(smooth), out["wp"].ctypes.data, out["status"].ctypes.data,
+                out["steps"].ctypes.data, out["vertices"].ctypes.data),
+                "uam_route_paths_smooth_host")
+            return out
         _lib.check(_lib.load().uam_route_paths_host(
             ctypes.byref(field.geo.as_struct()), _host_rec(field.rec, field.geo).ctypes.data,
             ctypes.byref(rp), nxt.ctypes.data, goals.ctypes.data, goals.shape[0], s.ctypes.data,

@@ -1,9 +1,16 @@
 // k4h.inc -- K4h, the packed volume in the similarity form: VSlot / VSlotX, KVol4, the pack
-// kernels (k_volume_pack_planes, k_volume_pack_t4, k_volume_codes), v_path_seed, k_v_hist,
-// k_v_eval (k_v_eval_x: its exact form), k_v_final / k_v_final_x.
+// kernels (k_volume_pack_planes, k_volume_pack_t4, k_volume_codes), KProf, v_path_seed,
+// k_v_hist_f (k_v_hist / k_vp_hist), k_v_eval (k_v_eval_x: its exact form; k_vp_eval /
+// k_vp_eval_x: its instances with the profile table), k_v_final / k_v_final_x.
 // Included in the anonymous namespace of uampath.hip; relies on its text above (the device tables,
 // arc_point, pk_bound_decode, pk_terms_k, xcd_chunk, K2g's KGrp, UGeo, G_* limits, put_*) and on
 // k2h.inc (X128, x_add, x_term, x_result).
+//
+// The seed, the histogram and the evaluation serve two forms of the altitude: K4h's straight
+// climb and K4hp's profile table (k4hp.inc), which they take as a trailing parameter pack of
+// zero or one KProf -- K4h's instances keep their argument list.  PROF, the pack's presence,
+// guards every statement that is per form: the path split (the profile rides inside the path
+// index), the table staged in LDS after the arc rows, and where z comes from.
 
 // ---- K4h: the volume (config 5) in K2h's form -------------------------------------------------
 // The packed volume (uam_volume_pack; layout: VpkDims).  Planes in K2h's 4 x 8-column blocks,
@@ -175,19 +182,67 @@ __device__ __forceinline__ bool vol_voxel(const KVol4& vs, double x0, double x1,
     return in;
 }
 
-// K4h: a path's clearance seed (k_v_eval's E and Ub): the exact clearance z - T (T the column's
+// K4hp (uam_eval_generated3d_profiles_h): the altitude of waypoint j from the profile table
+// instead of the straight climb.  The profile rides inside the path index, p = (q D + d) A + a,
+// so KGrp describes P = Q D A paths with kg.D the lateral candidates (the unit-arc rows and
+// k_g_scatter's UGeo rows are per d) and every shared launch (the scan, k_g_scatter) runs
+// unchanged.  KGrp itself stays as it is -- it is a kernel argument of K2g / K2h / K4h -- and
+// what the profile form adds travels in KProf.
+struct KProf {
+    const double* __restrict__ ztab;  // [A][W][3]
+    int32_t A;
+    int32_t sh_a;
+    uint64_t m_a;  // div_magic's multiplier and shift for / A
+};
+
+constexpr int VPK_ZTAB_LDS = 40 * 1024;  // the profile rows in LDS up to this
+
+// A kernel's optional trailing KProf argument (a parameter pack of zero or one), as vert_of
+__device__ __forceinline__ KProf prof_of() { return KProf{}; }
+__device__ __forceinline__ const KProf& prof_of(const KProf& f) { return f; }
+
+// the table rule: two products, their sum, then the sum with the third coefficient (row: the
+// profile's 3 W coefficients)
+__device__ __forceinline__ double vp_z(const double* row, int j, double za, double zb) {
+    const double* c = row + 3 * j;
+    return (za * c[0] + zb * c[1]) + c[2];
+}
+
+// a path = (lateral path, profile); the lateral path = (pair, displacement)
+__device__ __forceinline__ void vp_split(const KGrp& kg, const KProf& kf, int32_t path,
+                                         int32_t& q, int32_t& d, int32_t& a) {
+    const int32_t lat = (int32_t)div_magic((uint32_t)path, kf.m_a, kf.sh_a);
+    a = path - lat * kf.A;
+    q = (int32_t)div_magic((uint32_t)lat, kg.m_d, kg.sh_d);
+    d = lat - q * kg.D;
+}
+
+// A path's clearance seed (k_v_eval's E and Ub): the exact clearance z - T (T the column's
 // terrain, t4) of the in-volume sampled waypoint with the smallest z - lb, over j = 0, s, 2s,
 // ... (s = kg.lb_stride) and j = W - 1, at their own voxels and altitudes by the evaluation's
 // operations (+inf: none).  It is an exact clearance of the path, so at least the path's
 // minimum M.  hdr / u: the packed header and the unit-arc table (LDS copies when staged).
+// PROF: z by the table rule on the profile's row in global memory, formed with the sample's
+// loads.
+template <class... F>
 __device__ __forceinline__ double v_path_seed(const KParams& p, const KVol4& vs, const KGrp& kg,
                                              int32_t path, const uint32_t* __restrict__ hdr,
-                                             const double2* __restrict__ utab) {
-    const int32_t q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d), d = path - q * kg.D;
+                                             const double2* __restrict__ utab, const F&... f) {
+    constexpr bool PROF = sizeof...(F) != 0;
+    [[maybe_unused]] const KProf kf = prof_of(f...);
+    int32_t q, d;
+    [[maybe_unused]] int32_t a = 0;
+    if constexpr (PROF) {
+        vp_split(kg, kf, path, q, d, a);
+    } else {
+        q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d), d = path - q * kg.D;
+    }
     const double* pr = kg.pairs + (int64_t)q * 6;
     const double ax = pr[0], ay = pr[1], za = pr[2], bx = pr[3], by = pr[4], zb = pr[5];
     const double2* u = utab + d * p.N - 1;
     const int W = kg.W;
+    [[maybe_unused]] const double* zrow = nullptr;
+    if constexpr (PROF) zrow = kf.ztab + (int64_t)a * W * 3;
     constexpr uint32_t NONE = 0xffffffffu;
     double Ub = INFINITY, zbest = 0.0;
     uint32_t best = NONE;  // the t4 index of the sample holding Ub
@@ -206,32 +261,45 @@ __device__ __forceinline__ double v_path_seed(const KParams& p, const KVol4& vs,
         zbest = dn ? z : zbest;
         best = dn ? vt4_index(vs, ix, iy) : best;
     };
-    take(ax, ay, vz_at(za, zb, 0.0 / (double)(W - 1)));
-    take(bx, by, vz_at(za, zb, (double)(W - 1) / (double)(W - 1)));
+    if constexpr (PROF) {
+        take(ax, ay, vp_z(zrow, 0, za, zb));
+        take(bx, by, vp_z(zrow, W - 1, za, zb));
+    } else {
+        take(ax, ay, vz_at(za, zb, 0.0 / (double)(W - 1)));
+        take(bx, by, vz_at(za, zb, (double)(W - 1) / (double)(W - 1)));
+    }
     // four samples at a time, every load of the four issued together (a sample past the last
     // interior waypoint repeats it)
     constexpr int K = 4;
     for (int j0 = kg.lb_stride; j0 < W - 1; j0 += K * kg.lb_stride) {
         double2 uu[K];
         int jj[K];
+        [[maybe_unused]] double zz[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             jj[k] = min(j0 + k * kg.lb_stride, W - 2);
             uu[k] = u[jj[k]];
+            if constexpr (PROF) zz[k] = vp_z(zrow, jj[k], za, zb);
         }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             double x0, x1;
             arc_point(ax, ay, bx, by, uu[k].x, uu[k].y, x0, x1);
-            take(x0, x1, vz_at(za, zb, (double)jj[k] / (double)(W - 1)));
+            if constexpr (PROF) take(x0, x1, zz[k]);
+            else take(x0, x1, vz_at(za, zb, (double)jj[k] / (double)(W - 1)));
         }
     }
     return best == NONE ? INFINITY
                         : zbest - (double)reinterpret_cast<const float*>(vs.pk + vs.ot4)[best];
 }
 
-// sort, launch 1 (K4h): keys on (altitude band, tile) of each item's middle waypoint
-__global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
+// sort, launch 1 (K4h, K4hp): keys on (altitude band, tile) of each item's middle waypoint.
+// PROF: at the profile's own z (its three coefficients loaded with the batch), so the profiles
+// of a lateral candidate that fly at different heights fall into different bands.
+template <class... F>
+__global__ __launch_bounds__(1024) void k_v_hist_f(KParams p, KVol4 vs, KGrp kg, F... f) {
+    constexpr bool PROF = sizeof...(F) != 0;
+    [[maybe_unused]] const KProf kf = prof_of(f...);
     __shared__ __attribute__((aligned(16))) int32_t h[G_BINS_MAX];
     __shared__ uint16_t tk[1 << (2 * G_TBITS_MAX)];
     // with kg.seed_lds: the packed header and the unit-arc table staged for the seeds
@@ -256,11 +324,12 @@ __global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
     const int64_t hi = ((int64_t)kg.P * (b + 1) / G_NBK) * kg.nseg;
     const int N = p.N, W = kg.W;
     const int tiles = 1 << (2 * kg.tbits);
-    const double inv_w1 = 1.0 / (double)(W - 1);
+    [[maybe_unused]] const double inv_w1 = 1.0 / (double)(W - 1);
     // U items per thread with all their loads issued first (k_g_hist's batching)
     constexpr int U = 4;
     for (int64_t i0 = lo + t; i0 < hi; i0 += 1024 * U) {
         double pr[U][6];
+        [[maybe_unused]] double zc[U][3];
         double2 u[U];
         int jm[U], sg[U];
 #pragma unroll
@@ -268,8 +337,14 @@ __global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
             const int32_t i = (int32_t)min(i0 + k * 1024, hi - 1);
             const int32_t path = (int32_t)div_magic((uint32_t)i, kg.m_nseg, kg.sh_nseg);
             sg[k] = (int)(i - (int64_t)path * kg.nseg);
-            const int32_t q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d);
-            const int32_t d = path - q * kg.D;
+            int32_t q, d;
+            [[maybe_unused]] int32_t ap = 0;  // the profile
+            if constexpr (PROF) {
+                vp_split(kg, kf, path, q, d, ap);
+            } else {
+                q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d);
+                d = path - q * kg.D;
+            }
             const int j0 = sg[k] * kg.G, j1 = min(j0 + kg.G, W);
             jm[k] = (j0 + j1 - 1) >> 1;
             const double2* pp = reinterpret_cast<const double2*>(kg.pairs + (int64_t)q * 6);
@@ -277,6 +352,10 @@ __global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
             pr[k][0] = a.x, pr[k][1] = a.y, pr[k][2] = b2.x, pr[k][3] = b2.y, pr[k][4] = c.x,
             pr[k][5] = c.y;
             u[k] = reinterpret_cast<const double2*>(kg.utab)[d * N + min(max(jm[k] - 1, 0), N - 1)];
+            if constexpr (PROF) {
+                const double* zr = kf.ztab + ((int64_t)ap * W + jm[k]) * 3;
+                zc[k][0] = zr[0], zc[k][1] = zr[1], zc[k][2] = zr[2];
+            }
         }
 #pragma unroll
         for (int k = 0; k < U; ++k) {
@@ -291,7 +370,9 @@ __global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
                 arc_point(pr[k][0], pr[k][1], pr[k][3], pr[k][4], u[k].x, u[k].y, x0, x1);
             }
             // (the key only orders the items: j / (W-1) by a reciprocal is exact enough)
-            const double z = vz_at(pr[k][2], pr[k][5], (double)jm[k] * inv_w1);
+            double z;
+            if constexpr (PROF) z = (pr[k][2] * zc[k][0] + pr[k][5] * zc[k][1]) + zc[k][2];
+            else z = vz_at(pr[k][2], pr[k][5], (double)jm[k] * inv_w1);
             const double tx = (x0 - vs.x0) * vs.inv_dx, ty = (vs.y_top - x1) * vs.inv_dy;
             const double tz = (z - vs.z0) * vs.inv_dz;
             uint32_t key = kg.bins - 1;
@@ -300,8 +381,10 @@ __global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
                 const uint32_t cx = (uint32_t)tx >> kg.tshift, cy = (uint32_t)ty >> kg.tshift;
                 key = ((uint32_t)tz >> vs.zshift) * tiles + tk[(cy << kg.tbits) | cx];
                 // (kg.last_bin is 0, one bin per tile and band, as K2h's: k_v_eval masks the
-                // slots past a lane's group and pads s_u / s_jw by G + 16 slots)
-                if (sg[k] == kg.nseg - 1) key += kg.last_bin;
+                // slots past a lane's group and pads s_u / s_jw by G + 16 slots; the profile
+                // form never had the statement)
+                if constexpr (!PROF)
+                    if (sg[k] == kg.nseg - 1) key += kg.last_bin;
             }
             kg.key[i] = (uint16_t)key;
             atomicAdd(&h[key], 1);
@@ -310,11 +393,13 @@ __global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
     if (kg.ubp) {  // the partition's paths' clearance seeds, one thread per path
         const int64_t plo = (int64_t)kg.P * b / G_NBK, phi = (int64_t)kg.P * (b + 1) / G_NBK;
         for (int64_t pth = plo + t; pth < phi; pth += 1024)
-            kg.ubp[pth] = v_path_seed(p, vs, kg, (int32_t)pth, s_hdr, s_ut);
+            kg.ubp[pth] = v_path_seed(p, vs, kg, (int32_t)pth, s_hdr, s_ut, f...);
     }
     __syncthreads();
     for (int k = t; k < kg.bins; k += 1024) kg.cnt[(int64_t)k * G_NBK + b] = h[k];
 }
+constexpr auto k_v_hist = k_v_hist_f<>;
+constexpr auto k_vp_hist = k_v_hist_f<KProf>;
 
 // every (path, group) item in sorted order (h_item's phases): the CH waypoints' voxels (x, y by
 // the arc formula or the pair's end points, z on the linear climb), the header reads, then per
@@ -340,18 +425,31 @@ __global__ __launch_bounds__(1024) void k_v_hist(KParams p, KVol4 vs, KGrp kg) {
 // ones as side flags.  One body for both forms, in the kernel itself: moved into an inlined
 // function, the EX = false instantiations no longer allocated the registers they had (DESIGN
 // §10), so the exact form is this kernel's third template flag and vs.xscale its scale.
-// k_vp_eval (k4hp.inc) is a copy of this body with the altitude from the profile table (a body
-// of its own for the same reason): a fix to the phases here belongs there too.
-template <int CH, bool TE, bool EX = false>  // TE: the terrain in the entry (UAM_OPT_K4H_TERRAIN 1)
+// PROF (a trailing KProf: k_vp_eval, K4hp): the profile rows staged in LDS beside the arc rows
+// (24 A W bytes + padding, in place of the j / (W-1) table): a lane's row is s_jw + 3 a W, and
+// waypoint j's altitude is the table rule on it (vp_z), formed once in phase 1 and kept in
+// registers for the consume loop (the straight climb forms vz_at a second time there from one LDS
+// word; three words per slot read again cost 24 VGPRs at CH = 7 and spilled at CH = 6, 8 and 16
+// -- DESIGN §10.1).  A slot past the group's end reads the next row or the padding (zeros): its
+// voxel is masked, and whatever its z, vol_voxel gives indices inside the volume.  The per-form
+// statements stand under `if constexpr (PROF)` in this body, not in a shared inlined function,
+// for the reason above.
+template <int CH, bool TE, bool EX = false, class... F>  // TE: the terrain in the entry
+                                                         // (UAM_OPT_K4H_TERRAIN 1)
 __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(KParams p, KVol4 vs,
-                                                                              KGrp kg) {
+                                                                              KGrp kg, F... f) {
     PK_CODES_CHECK(CH);
-    // unit-arc rows + padding, then j / (W-1) (+ padding), then the header
+    constexpr bool PROF = sizeof...(F) != 0;
+    static_assert(sizeof...(F) <= 1, "at most one KProf");
+    [[maybe_unused]] const KProf kf = prof_of(f...);
+    // unit-arc rows + padding, then j / (W-1) or the profile rows (+ padding), then the header
     extern __shared__ __attribute__((aligned(16))) double2 s_u[];
     const int N = p.N, W = kg.W;
     const int nu = kg.D * N, npad = kg.G + 16;  // a lane's slots reach j <= W + G + CH - 3
     double* s_jw = reinterpret_cast<double*>(s_u + nu + npad);
-    const int njw = W + npad;
+    int njw;
+    if constexpr (PROF) njw = (kf.A * W + npad) * 3;
+    else njw = W + npad;
     uint32_t* s_hdr = reinterpret_cast<uint32_t*>(s_jw + ((njw + 1) & ~1));
     // the item's order entry, pair and path bound before the staging (their round trips
     // overlap it)
@@ -360,7 +458,13 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
     const int32_t item = live ? kg.order[pos] : 0;
     const int32_t path = (int32_t)div_magic((uint32_t)item, kg.m_nseg, kg.sh_nseg);
     const int s = item - path * kg.nseg;
-    const int32_t q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d), d = path - q * kg.D;
+    int32_t q, d;
+    [[maybe_unused]] int32_t a = 0;  // PROF: the path's profile
+    if constexpr (PROF) {
+        vp_split(kg, kf, path, q, d, a);
+    } else {
+        q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d), d = path - q * kg.D;
+    }
     const double* prp = kg.pairs + (int64_t)q * 6;
     const double2 pa = *reinterpret_cast<const double2*>(prp);
     const double2 pb = *reinterpret_cast<const double2*>(prp + 2);
@@ -369,8 +473,13 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
     double Ub = seed;
     for (int i = threadIdx.x; i < nu + npad; i += 256)
         s_u[i] = i < nu ? reinterpret_cast<const double2*>(kg.utab)[i] : make_double2(0.0, 0.0);
-    for (int j = threadIdx.x; j < njw; j += 256)
-        s_jw[j] = j < W ? (double)j / (double)(W - 1) : 0.0;
+    if constexpr (PROF) {
+        const int nz3 = kf.A * W * 3;
+        for (int i = threadIdx.x; i < njw; i += 256) s_jw[i] = i < nz3 ? kf.ztab[i] : 0.0;
+    } else {
+        for (int j = threadIdx.x; j < njw; j += 256)
+            s_jw[j] = j < W ? (double)j / (double)(W - 1) : 0.0;
+    }
     {
         const uint4* src = reinterpret_cast<const uint4*>(vs.hdr);
         uint4* dst = reinterpret_cast<uint4*>(s_hdr);
@@ -380,6 +489,8 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
     __syncthreads();
     const double ax = pa.x, ay = pa.y, za = pb.x, bx = pb.y, by = pc.x, zb = pc.y;
     const double2* urow = s_u + d * N - 1;  // waypoint j's unit vector: urow[j]
+    // PROF: waypoint j's coefficients, zrow[3 j ..]
+    [[maybe_unused]] const double* zrow = s_jw + a * W * 3;
     const int j0 = s * kg.G, j1 = live ? min(j0 + kg.G, W) : j0;
     int nch = (j1 - j0 + CH - 1) / CH;  // the wave's most: a wave-uniform loop
 #pragma unroll
@@ -387,16 +498,18 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
     const double vx = ax - bx, vy = ay - by;
     const double cx = (bx + ax) * 0.5, cy = (by + ay) * 0.5;
     const double dN = (double)N, yN = kg.inv_n;
-    auto over_n = [&](double a) {  // (K4h: N <= 4096)
-        const double q0 = a * yN;
-        const double q1 = fma(fma(-q0, dN, a), yN, q0);
-        return __builtin_isinf(a) ? q0 : q1;
+    auto over_n = [&](double v) {  // (K4h: N <= 4096)
+        const double q0 = v * yN;
+        const double q1 = fma(fma(-q0, dN, v), yN, q0);
+        return __builtin_isinf(v) ? q0 : q1;
     };
     // the layer centre of layer iz (the below-terrain test)
     auto zc_of = [&](int32_t iz) { return vs.z0 + ((double)iz + 0.5) * vs.dz; };
     // the end points' voxels, formed once
     int32_t ixF, iyF, izF, ixL, iyL, izL;
-    const double zF = vz_at(za, zb, s_jw[0]), zL = vz_at(za, zb, s_jw[W - 1]);
+    double zF, zL;
+    if constexpr (PROF) zF = vp_z(zrow, 0, za, zb), zL = vp_z(zrow, W - 1, za, zb);
+    else zF = vz_at(za, zb, s_jw[0]), zL = vz_at(za, zb, s_jw[W - 1]);
     const bool inF = vol_voxel(vs, ax, ay, zF, ixF, iyF, izF);
     const bool inL = vol_voxel(vs, bx, by, zL, ixL, iyL, izL);
     const uint16_t* const bnd = reinterpret_cast<const uint16_t*>(s_hdr + vs.bnd_off);
@@ -433,15 +546,16 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
     uint32_t kcA[CH], vinA = 0, tkA = 0, bvA = 0;
     int nvA = 0, jcA = 0;
     constexpr bool ahead = false;  // (h_item's)
+    static_assert(!PROF || !ahead, "the kept zB is the chunk the same iteration consumes");
     for (int c = ahead ? -1 : 0; c < nch; ++c) {  // (nch wave-uniform)
         const int ci = ahead ? c + 1 : c;  // the chunk issued by this iteration
         uint4 rB[CH];
         float tvB[CH];
         uint32_t kcB[CH], vinB = 0, tkB = 0, bvB = 0;
         int nvB = 0;
+        double zB[CH];  // the slots' altitudes (PROF: kept for the consume loop)
         const int jc = j0 + ci * CH;
         if (ci < nch) {
-            double zB[CH];
             int32_t izB[CH];
             const double2* uc = urow + jc;
             // phase 1: the voxels
@@ -450,7 +564,9 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
             for (int t = 0; t < CH; ++t) {
                 const int j = jc + t;
                 const double2 u = uc[t];
-                const double z = vz_at(za, zb, s_jw[j]);
+                double z;
+                if constexpr (PROF) z = vp_z(zrow, j, za, zb);
+                else z = vz_at(za, zb, s_jw[j]);
                 int32_t x, y, zz;
                 bool in = vol_voxel(vs, cx + 0.5 * (vx * u.x - vy * u.y),
                                     cy + 0.5 * (vy * u.x + vx * u.y), z, x, y, zz);
@@ -549,7 +665,9 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
                         gc = gc + over_n((double)__uint_as_float(risk));
                         gn = gn + (rec ? (double)__uint_as_float(r.y) : 0.0);
                     }
-                    const double z = vz_at(za, zb, s_jw[jcA + t]);
+                    double z;
+                    if constexpr (PROF) z = zB[t];
+                    else z = vz_at(za, zb, s_jw[jcA + t]);
                     bel += (in && zc_of((int32_t)(kcA[t] >> 8)) < (double)ter) ? 1u : 0u;
                     E = in ? fmin(E, z - (double)ter) : E;
                     continue;
@@ -570,7 +688,9 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
                 // the exact terrain, where taken: v16's (code 3) or the fetched one
                 const bool ex = in & (c3 | ((tkA >> t) & 1u));
                 const float ter = c3 ? rter : tvA[t];
-                const double z = vz_at(za, zb, s_jw[jcA + t]);
+                double z;
+                if constexpr (PROF) z = zB[t];
+                else z = vz_at(za, zb, s_jw[jcA + t]);
                 const uint32_t below =
                     ex ? (zc_of((int32_t)(kcA[t] >> 8)) < (double)ter ? 1u : 0u) : ((bvA >> t) & 1u);
                 bel += in ? below : 0u;
@@ -604,6 +724,11 @@ __global__ __launch_bounds__(256, CH >= 11 ? 2 : CH >= 7 ? 3 : 4) void k_v_eval(
 // the exact form (UAM_OPT_EXACT_SUM_VOLUME), k_v_eval's sibling: the same body with EX set
 template <int CH, bool TE>
 constexpr auto k_v_eval_x = k_v_eval<CH, TE, true>;
+// K4hp's instances (the host tables' names)
+template <int CH, bool TE, bool EX = false>
+constexpr auto k_vp_eval = k_v_eval<CH, TE, EX, KProf>;
+template <int CH, bool TE>
+constexpr auto k_vp_eval_x = k_v_eval<CH, TE, true, KProf>;
 
 // outputs of every path (block = 64 pairs x D): the similarity-form geometry (oracle sim_geo on
 // the pair's x/y), cost = (N+1) L + the risk / N partials in group order, min clearance, the

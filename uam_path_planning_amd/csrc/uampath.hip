@@ -34,9 +34,10 @@
 //                      arithmetic (X128) host and device share
 //   sum_scale.inc      k_sum_scale_init k_sum_scale
 //   k4h.inc            K4h: k_volume_pack_planes k_volume_pack_t4 k_volume_codes k_v_hist
-//                      k_v_eval (k_v_eval_x) k_v_final k_v_final_x
-//   k4hp.inc           K4hp: k_vp_hist k_vp_eval (k_vp_eval_x) k_vp_final k_vp_final_x
-//                      k_vp_sel_check; K4hp+v: k_vp_final_v k_vp_final_xv
+//                      k_v_eval (k_v_eval_x) k_v_final k_v_final_x; with a trailing KProf,
+//                      K4hp's k_vp_hist k_vp_eval (k_vp_eval_x)
+//   k4hp.inc           K4hp: k_vp_final k_vp_final_x k_vp_sel_check; K4hp+v: k_vp_final_v
+//                      k_vp_final_xv
 //   struct uam_ctx and its helpers; then the C ABI (include/uampath.h) with the launches'
 //   static helpers between its entry points: context, geometry, params, K1; K2w launch; the
 //   option table; pair-order scratch and K2s launch; the grouped plan (K2g / K2h / K4h / K4hp);
@@ -6268,10 +6269,11 @@ __global__ __launch_bounds__(1024) void k_g_final(KParams p, KGrp kg, KOut out,
 // sum scales of the exact forms: k_sum_scale_init, k_sum_scale
 #include "sum_scale.inc"
 
-// K4h: packed volume, k_volume_pack_planes / _t4, k_volume_codes, k_v_hist, k_v_eval, k_v_final*
+// K4h: packed volume, k_volume_pack_planes / _t4, k_volume_codes, k_v_hist, k_v_eval, k_v_final*;
+// K4hp's k_vp_hist and k_vp_eval are the same kernels with a trailing KProf
 #include "k4h.inc"
 
-// K4hp: the altitude profiles on the packed, sorted volume, k_vp_hist, k_vp_eval, k_vp_final*
+// K4hp: the altitude profiles on the packed, sorted volume: the output launches k_vp_final*
 #include "k4hp.inc"
 
 // K9: route seeds, k_route_cost, k_route_init, k_route_relax, k_route_next, k_route_trace
@@ -7514,9 +7516,11 @@ using GFinalFn = void (*)(KParams, KGrp, KOut, int32_t*, int32_t*);
 using HEvalXFn = void (*)(KParams, KRaster, KGrp, const int32_t*);
 using HFinalXFn = void (*)(KParams, KGrp, KOut, int32_t*, int32_t*, const int32_t*);
 using VEvalFn = void (*)(KParams, KVol4, KGrp);
+using VPEvalFn = void (*)(KParams, KVol4, KGrp, KProf);
 struct GPlan {
     KGrp kg;
-    bool vol;                 // K4h (the packed volume); the packed raster otherwise
+    KProf kf;                 // vol: the profiles (ztab null, A = 1: the straight climb, K4h)
+    bool vol;                 // K4h / K4hp (the packed volume); the packed raster otherwise
     bool sim;                 // K2h / K4h (the similarity form); K2g otherwise
     bool exact;               // the exact form (UAM_OPT_EXACT_SUM: hevx / finx, 40-B slots;
                               // UAM_OPT_EXACT_SUM_VOLUME: vev / finx, 48-B slots)
@@ -7534,6 +7538,7 @@ struct GPlan {
     GEvalFn ev;
     HEvalFn hev;
     VEvalFn vev;
+    VPEvalFn pev;             // K4hp (kf.ztab set): vev's instance with the profile table
     GFinalFn fin;
 };
 
@@ -7747,7 +7752,7 @@ static void grouped_carve(GPlan* pl, char* w) {
 }
 
 // A family's histogram launch (G_NBK workgroups of 1024, lds bytes of dynamic LDS) over its
-// grid: the raster's KRaster (k_g_hist) or the volume's KVol4 (k_v_hist)
+// grid: the raster's KRaster (k_g_hist) or the volume's VGrid (k_v_hist / k_vp_hist)
 using GHistFn = void (*)(uam_ctx*, const KGrp&, const void* grid, size_t lds, hipStream_t);
 
 static void raster_hist(uam_ctx* ctx, const KGrp& kg, const void* kr, size_t lds, hipStream_t s) {
@@ -7755,8 +7760,17 @@ static void raster_hist(uam_ctx* ctx, const KGrp& kg, const void* kr, size_t lds
                        kg);
 }
 
-static void volume_hist(uam_ctx* ctx, const KGrp& kg, const void* kv, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL(k_v_hist, dim3(G_NBK), dim3(1024), lds, s, ctx->kp, *(const KVol4*)kv, kg);
+struct VGrid {  // the volume's view and the profiles (a null table: K4h's own instance)
+    KVol4 kv;
+    KProf kf;
+};
+
+static void volume_hist(uam_ctx* ctx, const KGrp& kg, const void* g, size_t lds, hipStream_t s) {
+    const VGrid* vg = (const VGrid*)g;
+    if (vg->kf.ztab)
+        hipLaunchKernelGGL(k_vp_hist, dim3(G_NBK), dim3(1024), lds, s, ctx->kp, vg->kv, kg, vg->kf);
+    else
+        hipLaunchKernelGGL(k_v_hist, dim3(G_NBK), dim3(1024), lds, s, ctx->kp, vg->kv, kg);
 }
 
 // the counting sort; the histogram launch is the only part that differs
@@ -7784,11 +7798,14 @@ static void grouped_eval(uam_ctx* ctx, const GPlan& pl, const KRaster& kr, const
                            (const uint4*)rec);
 }
 
-// K4h's: the exact form reads its scale through the volume's view
+// K4h's and K4hp's: the exact form reads its scale through the volume's view
 static void grouped_eval(uam_ctx* ctx, const GPlan& pl, KVol4 kv, hipStream_t s) {
     const dim3 grid((unsigned)((pl.kg.n_items + pl.bs - 1) / pl.bs));
     if (pl.exact) kv.xscale = pl.scale;
-    hipLaunchKernelGGL(pl.vev, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kv, pl.kg);
+    if (pl.pev)
+        hipLaunchKernelGGL(pl.pev, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kv, pl.kg, pl.kf);
+    else
+        hipLaunchKernelGGL(pl.vev, grid, dim3(pl.bs), pl.lds, s, ctx->kp, kv, pl.kg);
 }
 
 static void grouped_final(uam_ctx* ctx, const GPlan& pl, const KOut& ko, int32_t* best_f,
@@ -7806,11 +7823,12 @@ static void grouped_final(uam_ctx* ctx, const GPlan& pl, const KOut& ko, int32_t
 // K4hp's and K4hp+v's: one thread per path (vert: the sequential 3-D geometry, k_vp_final_v /
 // k_vp_final_xv), then uam_argmin's rule over the pair's C = D * A candidates, as K4p, and the
 // sort check's mark on the selections
-static void profile_final(uam_ctx* ctx, const GPlan& pl, const KProf& kf, const KVert* vert,
-                          const KOut& ko, int32_t* best_f, int32_t* best_l, int32_t C,
-                          hipStream_t s) {
+static void profile_final(uam_ctx* ctx, const GPlan& pl, const KVert* vert, const KOut& ko,
+                          int32_t* best_f, int32_t* best_l, hipStream_t s) {
     const KGrp& kg = pl.kg;
+    const KProf& kf = pl.kf;
     const int64_t n_pairs = kg.n_pairs;
+    const int32_t C = kg.D * kf.A;
     const dim3 gfin((unsigned)(((int64_t)kg.P + 255) / 256));
     if (vert && pl.exact)
         hipLaunchKernelGGL(k_vp_final_xv, gfin, dim3(256), 0, s, ctx->kp, kg, kf, *vert, ko,
@@ -7926,10 +7944,13 @@ static const char* volume_refusal(const uam_ctx* ctx, const KVol4& kv, const KOu
     return nullptr;
 }
 
-// the sequence a volume batch takes (K4h): as grouped_plan
+// the sequence a volume batch takes (K4h; K4hp with a profile table ztab [A][W][3], the profile
+// inside the path index): as grouped_plan.  must: a call with a sum order of its own
+// (uam_eval_generated3d_profiles_h / _hv), so every batch it does not take is an error -- 1 or
+// < 0, never 0.  The two forms' refusals keep each its own order and texts.
 static int grouped_plan3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
-                          const double* utab, int32_t D, const KOut& ko, GPlan* pl,
-                          bool must = false, bool vert = false) {
+                          const double* utab, int32_t D, const double* ztab, int32_t A,
+                          const KOut& ko, GPlan* pl, bool must, bool vert) {
     const int G = ctx->k2g_group;
     const bool exact = ctx->exact_sum_vol != 0;
     *pl = GPlan{};
@@ -7937,28 +7958,39 @@ static int grouped_plan3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, i
     pl->exact = exact;
     pl->must = must;
     pl->needs = vert   ? "uam_eval_generated3d_profiles_hv needs K4hpv"
+                : ztab ? "uam_eval_generated3d_profiles_h needs K4hp"
                 : must ? "uam_eval_generated3d_profiles_h needs K4h"
                        : "UAM_OPT_EXACT_SUM_VOLUME needs K4h";
     pl->scale = exact ? ctx->vol_sum_scale : nullptr;
+    pl->kf.ztab = ztab;
+    pl->kf.A = A;
+    magic_div((uint32_t)A, &pl->kf.m_a, &pl->kf.sh_a);
     auto no = [&](const char* why) { return grouped_no(*pl, why); };
     if (const char* why = volume_refusal(ctx, kv, ko, D, vert)) return no(why);
-    if (!exact && !must && n_pairs * D < ctx->k2s_min) return 0;
-    if (n_pairs > INT32_MAX / D) return no("more than 2^31 paths");
+    if (!ztab) {
+        if (!exact && !must && n_pairs * D < ctx->k2s_min) return 0;
+        if (n_pairs > INT32_MAX / D) return no("more than 2^31 paths");
+    }
+    const int64_t W = ctx->kp.N + 2, npad = G + 16;  // k_v_eval's padding slots
     const size_t ubytes = (size_t)D * ctx->kp.N * 16;
     if (ubytes > (size_t)G_UTAB_LDS) return no("the unit-arc table exceeds its LDS share");
+    if (ztab && (size_t)A * W * 24 > (size_t)VPK_ZTAB_LDS)
+        return no("the profile table exceeds its LDS share");
     if ((size_t)kv.hwords * 4 > (size_t)VPK_HDR_LDS)
         return no("the packed header exceeds its LDS share");
     int st = grouped_sizes(ctx, pl, pairs6, n_pairs, utab, D, kv.nx, kv.ny, kv.nbands,
-                           volume_tiles, exact ? sizeof(VSlotX) : sizeof(VSlot), 8);
+                           volume_tiles, exact ? sizeof(VSlotX) : sizeof(VSlot), 8, A);
     if (st <= 0) return st;
     // workgroups per CU: 3 by default through an LDS floor of 40 000 B (UAM_OPT_K2G_LDS_FLOOR
     // sets another): fewer items resident per XCD, so fewer of their lines miss L2 -- round 5's
     // bound form, cfg5: 0.394 ms at 3 with 7 in flight, 0.397 at 5 (28 000 B), 0.428 at 2
     // (60 000 B), 0.448 at 2 with 11 (profiles/r05/k4h2, cc)
-    const int64_t W = pl->kg.W, npad = G + 16;  // k_v_eval's padding slots
-    pl->lds = std::max((size_t)(D * ctx->kp.N + npad) * 16 + (size_t)((W + npad + 1) & ~1) * 8 +
+    const int64_t njw = ztab ? (A * W + npad) * 3 : W + npad;  // k_v_eval's table after the arcs
+    pl->lds = std::max((size_t)(D * ctx->kp.N + npad) * 16 + (size_t)((njw + 1) & ~(int64_t)1) * 8 +
                            (size_t)(ctx->k4h_te ? kv.bnd_off : kv.hwords) * 4,
                        (size_t)std::min(ctx->k2g_lds ? ctx->k2g_lds : 40000, 160 * 1024));
+    if (ztab && pl->lds > 160 * 1024)
+        return no("the arc rows, profile rows and header exceed the LDS");
     pl->bs = 256;
     pl->seeds = ctx->k2h_lbs > 0 && !ctx->k4h_te;
     pl->hist_dyn = (size_t)kv.hwords * 4 + ubytes;
@@ -7966,21 +7998,19 @@ static int grouped_plan3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, i
     // are built for 3 / 2 waves per SIMD)
     const int chl = ctx->k2g_chunk ? ctx->k2g_chunk : 7;
     // (21 runs as 16: a chunk's per-slot codes take 4 bits each of 64)
-    static const VEvalFn vevals[10] = {k_v_eval<6, false>, k_v_eval<7, false>,
-                                       k_v_eval<8, false>,  k_v_eval<11, false>,
-                                       k_v_eval<16, false>, k_v_eval<6, true>,
-                                       k_v_eval<7, true>,   k_v_eval<8, true>,
-                                       k_v_eval<11, true>,  k_v_eval<16, true>};
-    static const VEvalFn vevalsx[10] = {k_v_eval_x<6, false>, k_v_eval_x<7, false>,
-                                         k_v_eval_x<8, false>,  k_v_eval_x<11, false>,
-                                         k_v_eval_x<16, false>, k_v_eval_x<6, true>,
-                                         k_v_eval_x<7, true>,   k_v_eval_x<8, true>,
-                                         k_v_eval_x<11, true>,  k_v_eval_x<16, true>};
+#define UAM_V_EVALS(K) {K<6, false>, K<7, false>, K<8, false>, K<11, false>, K<16, false>, \
+                        K<6, true>,  K<7, true>,  K<8, true>,  K<11, true>,  K<16, true>}
+    static const VEvalFn vevals[10] = UAM_V_EVALS(k_v_eval), vevalsx[10] = UAM_V_EVALS(k_v_eval_x);
+    static const VPEvalFn pevals[10] = UAM_V_EVALS(k_vp_eval),
+                          pevalsx[10] = UAM_V_EVALS(k_vp_eval_x);
+#undef UAM_V_EVALS
     const int vi = (chl <= 6 ? 0 : chl == 7 ? 1 : chl <= 8 ? 2 : chl == 11 ? 3 : 4) +
                    (ctx->k4h_te ? 5 : 0);
-    pl->vev = exact ? vevalsx[vi] : vevals[vi];
-    if (pl->lds > 64 * 1024) {
-        st = raise_lds(&ctx->k4h_attrs, 160 * 1024, vevals, vevalsx);
+    if (ztab) pl->pev = exact ? pevalsx[vi] : pevals[vi];
+    else pl->vev = exact ? vevalsx[vi] : vevals[vi];
+    if (pl->lds > 64 * 1024) {  // (the two forms' instances are distinct functions)
+        st = ztab ? raise_lds(&ctx->k4hp_attrs, 160 * 1024, pevals, pevalsx)
+                  : raise_lds(&ctx->k4h_attrs, 160 * 1024, vevals, vevalsx);
         if (st) return st;
     }
     pl->fin = k_v_final;
@@ -7988,19 +8018,22 @@ static int grouped_plan3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, i
     return 1;  // (the error word: launch_grouped3d, after the carve as before)
 }
 
-// K4h launch (the packed volume in K2h's form); returns 1 if launched, 0 if the batch is not
-// one it takes (the caller runs K4).  Scratch: the pair-order scratch (order_scratch).
+// K4h / K4hp launch (the packed volume in K2h's form); returns 1 if launched, 0 if the batch is
+// not one it takes (the caller runs K4).  Scratch: the pair-order scratch (order_scratch).
 // UAM_OPT_EXACT_SUM_VOLUME: the exact form (k_v_eval_x / k_v_final_x, 48-B slots) at every batch
 // size; it never stands aside for another sum order, so a batch K4h does not take is an error
 // with its reason, raised before any launch.
-// vert (uam_eval_generated3d_profiles_hv with no table): the sort and k_v_eval as they are, then
-// K4hp+v's output launch on the straight climb in place of k_v_final.
+// ztab (uam_eval_generated3d_profiles_h with a table): K4hp, the sort and the evaluation at the
+// table's z and one output thread per path.
+// vert (uam_eval_generated3d_profiles_hv): the sort and the evaluation as they are, then
+// K4hp+v's output launch (with no table on the straight climb, in place of k_v_final).
 static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
-                            const double* utab, int32_t D, const KOut& ko, int32_t* best_f,
-                            int32_t* best_l, hipStream_t s, bool must = false,
-                            const KVert* vert = nullptr) {
+                            const double* utab, int32_t D, const double* ztab, int32_t A,
+                            const KOut& ko, int32_t* best_f, int32_t* best_l, hipStream_t s,
+                            bool must = false, const KVert* vert = nullptr) {
     GPlan pl;
-    int st = grouped_plan3d(ctx, kv, pairs6, n_pairs, utab, D, ko, &pl, must, vert != nullptr);
+    int st = grouped_plan3d(ctx, kv, pairs6, n_pairs, utab, D, ztab, A, ko, &pl, must,
+                            vert != nullptr);
     if (st <= 0) return st;
     if (pl.exact && !pl.scale)
         return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM_VOLUME is on and no volume sum scale is set "
@@ -8018,143 +8051,25 @@ static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6,
     if (st) return st;
     if (pl.kg.seed_lds) {
         static const VEvalFn hist[1] = {k_v_hist};
-        st = raise_lds(&ctx->k4h_hist_attr, G_HIST_DYN_MAX, hist);
+        static const VPEvalFn phist[1] = {k_vp_hist};
+        st = ztab ? raise_lds(&ctx->k4hp_hist_attr, G_HIST_DYN_MAX, phist)
+                  : raise_lds(&ctx->k4h_hist_attr, G_HIST_DYN_MAX, hist);
         if (st) return st;
     }
-    grouped_sort(ctx, pl, volume_hist, &kv, s);
+    const VGrid vg{kv, pl.kf};
+    grouped_sort(ctx, pl, volume_hist, &vg, s);
     grouped_eval(ctx, pl, kv, s);
-    if (vert) {
-        KProf kf{};  // no table: one profile, the straight climb
-        kf.A = 1;
-        magic_div(1u, &kf.m_a, &kf.sh_a);
-        profile_final(ctx, pl, kf, vert, ko, best_f, best_l, D, s);
-    } else {
-        grouped_final(ctx, pl, ko, best_f, best_l, s);
-    }
-    if (hipGetLastError() != hipSuccess) return fail(UAM_E_HIP, "grouped volume evaluation launch");
+    if (ztab || vert) profile_final(ctx, pl, vert, ko, best_f, best_l, s);
+    else grouped_final(ctx, pl, ko, best_f, best_l, s);
+    if (hipGetLastError() != hipSuccess)
+        return fail(UAM_E_HIP, ztab ? "grouped volume profile evaluation launch"
+                                    : "grouped volume evaluation launch");
     st = ktime_end(ctx, s);
     if (st) return st;
     ctx->last_group = pl.kg.G;
-    ctx->last_kernel = vert ? (pl.exact ? "K4hpxv+pack" : "K4hpv+pack")
-                            : pl.exact ? "K4hx+pack" : "K4h+pack";
-    st = order_done(ctx, s);
-    return st ? st : 1;
-}
-
-// K4hp (uam_eval_generated3d_profiles_h): K4h's plan with the profile inside the path index.
-// The call has a sum order of its own, so every batch it does not take is an error (pl->must):
-// returns 1 or < 0, never 0.
-using VPEvalFn = void (*)(KParams, KVol4, KGrp, KProf);
-struct VPGrid {  // the histogram launch's grid: the volume's view and the profiles
-    KVol4 kv;
-    KProf kf;
-};
-
-static void volume_profile_hist(uam_ctx* ctx, const KGrp& kg, const void* g, size_t lds,
-                                hipStream_t s) {
-    const VPGrid* vg = (const VPGrid*)g;
-    hipLaunchKernelGGL(k_vp_hist, dim3(G_NBK), dim3(1024), lds, s, ctx->kp, vg->kv, kg, vg->kf);
-}
-
-static int grouped_plan3dp(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
-                           const double* utab, int32_t D, int32_t A, const KOut& ko, GPlan* pl,
-                           VPEvalFn* vpev, bool vert = false) {
-    const int G = ctx->k2g_group;
-    const bool exact = ctx->exact_sum_vol != 0;
-    *pl = GPlan{};
-    pl->vol = pl->sim = true;
-    pl->exact = exact;
-    pl->must = true;
-    pl->needs = vert ? "uam_eval_generated3d_profiles_hv needs K4hpv"
-                     : "uam_eval_generated3d_profiles_h needs K4hp";
-    pl->scale = exact ? ctx->vol_sum_scale : nullptr;
-    auto no = [&](const char* why) { return grouped_no(*pl, why); };
-    if (const char* why = volume_refusal(ctx, kv, ko, D, vert)) return no(why);
-    const int64_t W = ctx->kp.N + 2, npad = G + 16;  // k_vp_eval's padding slots
-    const size_t ubytes = (size_t)D * ctx->kp.N * 16;
-    if (ubytes > (size_t)G_UTAB_LDS) return no("the unit-arc table exceeds its LDS share");
-    if ((size_t)A * W * 24 > (size_t)VPK_ZTAB_LDS)
-        return no("the profile table exceeds its LDS share");
-    if ((size_t)kv.hwords * 4 > (size_t)VPK_HDR_LDS)
-        return no("the packed header exceeds its LDS share");
-    int st = grouped_sizes(ctx, pl, pairs6, n_pairs, utab, D, kv.nx, kv.ny, kv.nbands,
-                           volume_tiles, exact ? sizeof(VSlotX) : sizeof(VSlot), 8, A);
-    if (st <= 0) return st;
-    // K4h's shape: 3 workgroups per CU through the LDS floor, 7 gathers in flight
-    pl->lds = std::max((size_t)(D * ctx->kp.N + npad) * 16 +
-                           (size_t)(((A * W + npad) * 3 + 1) & ~(int64_t)1) * 8 +
-                           (size_t)(ctx->k4h_te ? kv.bnd_off : kv.hwords) * 4,
-                       (size_t)std::min(ctx->k2g_lds ? ctx->k2g_lds : 40000, 160 * 1024));
-    if (pl->lds > 160 * 1024) return no("the arc rows, profile rows and header exceed the LDS");
-    pl->bs = 256;
-    pl->seeds = ctx->k2h_lbs > 0 && !ctx->k4h_te;
-    pl->hist_dyn = (size_t)kv.hwords * 4 + ubytes;
-    const int chl = ctx->k2g_chunk ? ctx->k2g_chunk : 7;
-    static const VPEvalFn vevals[10] = {k_vp_eval<6, false>, k_vp_eval<7, false>,
-                                        k_vp_eval<8, false>,  k_vp_eval<11, false>,
-                                        k_vp_eval<16, false>, k_vp_eval<6, true>,
-                                        k_vp_eval<7, true>,   k_vp_eval<8, true>,
-                                        k_vp_eval<11, true>,  k_vp_eval<16, true>};
-    static const VPEvalFn vevalsx[10] = {k_vp_eval_x<6, false>, k_vp_eval_x<7, false>,
-                                         k_vp_eval_x<8, false>,  k_vp_eval_x<11, false>,
-                                         k_vp_eval_x<16, false>, k_vp_eval_x<6, true>,
-                                         k_vp_eval_x<7, true>,   k_vp_eval_x<8, true>,
-                                         k_vp_eval_x<11, true>,  k_vp_eval_x<16, true>};
-    const int vi = (chl <= 6 ? 0 : chl == 7 ? 1 : chl <= 8 ? 2 : chl == 11 ? 3 : 4) +
-                   (ctx->k4h_te ? 5 : 0);
-    *vpev = exact ? vevalsx[vi] : vevals[vi];
-    if (pl->lds > 64 * 1024) {
-        st = raise_lds(&ctx->k4hp_attrs, 160 * 1024, vevals, vevalsx);
-        if (st) return st;
-    }
-    return 1;
-}
-
-static int launch_grouped3dp(uam_ctx* ctx, const KVol4& kv, const double* pairs6, int64_t n_pairs,
-                             const double* utab, int32_t D, const double* ztab, int32_t A,
-                             const KOut& ko, int32_t* best_f, int32_t* best_l, hipStream_t s,
-                             const KVert* vert = nullptr) {
-    GPlan pl;
-    VPEvalFn vpev = nullptr;
-    int st = grouped_plan3dp(ctx, kv, pairs6, n_pairs, utab, D, A, ko, &pl, &vpev,
-                             vert != nullptr);
-    if (st <= 0) return st;
-    if (pl.exact && !pl.scale)
-        return fail(UAM_E_STATE, "UAM_OPT_EXACT_SUM_VOLUME is on and no volume sum scale is set "
-                                 "(uam_volume_sum_scale, uam_set_volume_sum_scale)");
-    char* w = nullptr;
-    st = order_scratch(ctx, pl.bytes, s, &w);
-    if (st) return st;
-    st = tile_keys(ctx, pl.kg.tbits, ctx->k2g_curve, s);
-    if (st) return st;
-    pl.kg.tkey = ctx->d_tkey;
-    grouped_carve(&pl, w);
-    st = err_word(ctx, &pl.kg);
-    if (st) return st;
-    st = ktime_begin(ctx, s);
-    if (st) return st;
-    if (pl.kg.seed_lds) {
-        static const VPEvalFn hist[1] = {k_vp_hist};
-        st = raise_lds(&ctx->k4hp_hist_attr, G_HIST_DYN_MAX, hist);
-        if (st) return st;
-    }
-    VPGrid vg{kv, KProf{}};
-    vg.kf.ztab = ztab;
-    vg.kf.A = A;
-    magic_div((uint32_t)A, &vg.kf.m_a, &vg.kf.sh_a);
-    if (pl.exact) vg.kv.xscale = pl.scale;
-    const KGrp& kg = pl.kg;
-    grouped_sort(ctx, pl, volume_profile_hist, &vg, s);
-    hipLaunchKernelGGL(vpev, dim3((unsigned)((kg.n_items + pl.bs - 1) / pl.bs)), dim3(pl.bs),
-                       pl.lds, s, ctx->kp, vg.kv, kg, vg.kf);
-    profile_final(ctx, pl, vg.kf, vert, ko, best_f, best_l, D * A, s);
-    if (hipGetLastError() != hipSuccess)
-        return fail(UAM_E_HIP, "grouped volume profile evaluation launch");
-    st = ktime_end(ctx, s);
-    if (st) return st;
-    ctx->last_group = kg.G;
-    ctx->last_kernel = vert ? (pl.exact ? "K4hpxv+pack" : "K4hpv+pack")
-                            : pl.exact ? "K4hpx+pack" : "K4hp+pack";
+    ctx->last_kernel = vert   ? (pl.exact ? "K4hpxv+pack" : "K4hpv+pack")
+                       : ztab ? (pl.exact ? "K4hpx+pack" : "K4hp+pack")
+                              : pl.exact ? "K4hx+pack" : "K4h+pack";
     st = order_done(ctx, s);
     return st ? st : 1;
 }
@@ -8881,7 +8796,7 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
         KVol4 k4{};
         packed_view(ctx, vd, packed, &k4);
         if (exact || !want_wave(ctx, n_pairs * D)) {
-            st = launch_grouped3d(ctx, k4, pairs6, n_pairs, utab, D, ko, best_f, best_l,
+            st = launch_grouped3d(ctx, k4, pairs6, n_pairs, utab, D, nullptr, 1, ko, best_f, best_l,
                                   (hipStream_t)stream);
             if (st < 0) return st;
             if (st == 1) return UAM_OK;  // last_kernel: "K4h+pack" / "K4hx+pack"
@@ -9189,7 +9104,7 @@ int uam_eval_generated3d_profiles_v(uam_ctx* ctx, const uam_volume_desc* vd, con
 // order of its own: sorted at every batch size or an error, never K4p / K4 / K4w.  Failures, in
 // order: an earlier call's device check; the context; the dimensions (profile_dims; n_pairs ==
 // 0 then returns UAM_OK); the descriptor; pairs6 / utab NULL; a selection without its output;
-// no packed_dev; misaligned buffers; the plan's refusals (grouped_plan3dp / grouped_plan3d);
+// no packed_dev; misaligned buffers; the plan's refusals (grouped_plan3d);
 // UAM_E_STATE without a scale in the exact form.  All before any launch or allocation.
 // with_vert: uam_eval_generated3d_profiles_hv (K4hp+v), the same sorted sums with the geometry
 // per path under the vertical terms; vert is checked after the context, as K4p+v's, and the
@@ -9236,13 +9151,10 @@ static int eval_profiles_h(uam_ctx* ctx, const uam_volume_desc* vd, const void* 
     DeviceGuard dg(ctx->device);
     KVol4 k4{};
     packed_view(ctx, vd, packed, &k4);
-    if (!ztab)  // the straight climb: K4h's own kernels and bits (last_kernel "K4h+pack");
-                // with_vert: K4h's sort and evaluation, K4hp+v's output launch
-        st = launch_grouped3d(ctx, k4, pairs6, n_pairs, utab, D, ko, best_f, best_l,
-                              (hipStream_t)stream, true, kvp);
-    else
-        st = launch_grouped3dp(ctx, k4, pairs6, n_pairs, utab, D, ztab, A, ko, best_f, best_l,
-                               (hipStream_t)stream, kvp);
+    // (no table, the straight climb: K4h's own kernels and bits, last_kernel "K4h+pack";
+    // with_vert: K4h's sort and evaluation, K4hp+v's output launch)
+    st = launch_grouped3d(ctx, k4, pairs6, n_pairs, utab, D, ztab, A, ko, best_f, best_l,
+                          (hipStream_t)stream, true, kvp);
     if (st < 0) return st;
     if (st != 1) return fail(UAM_E_INVALID, "uam_eval_generated3d_profiles_h: not taken");
     return UAM_OK;

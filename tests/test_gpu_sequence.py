@@ -4,10 +4,10 @@ oracle, bit for bit (ulp-level for the CRS reprojection), whatever the context r
 A context carries state from call to call -- the shared grow-only scratch that every sorted form
 and pair order carves its own way and nobody clears, the cached tile-key table, the grow-only
 K7 tables, the tables set_params / set_geometry rebuild, the K8 arenas behind thread-local
-pointers, the side streams with their one fork / join event pair, the per-context "attributes
-raised" flags and the borrowed sum scales -- while every other parity test starts from a new
-context and makes one kind of call on it.  A launch that reads a word the current call did not
-write sees zeros there and the previous call's data here.
+pointers, the side streams with their one fork / join event pair, the per-context list of
+kernels with a raised LDS limit and the borrowed sum scales -- while every other parity test
+starts from a new context and makes one kind of call on it.  A launch that reads a word the
+current call did not write sees zeros there and the previous call's data here.
 
   * test_sequence_is_bit_exact: the drawn sequences of sequence_cases.py (13-14 calls: large
     then small on the scratch, raster -> volume -> analytic -> raster, a tile-key rewrite, N and
@@ -370,7 +370,7 @@ def test_two_contexts_interleaved(oracle_mod):
     """Two contexts alive at once, with different maps and parameters, taking turns at
     dem_polygons, a sorted raster call and an analytic call for three rounds: each result equals
     its own oracle (the K8 arenas are reached through thread-local pointers to "the calling
-    context's", the "attributes raised" flags are per context)."""
+    context's", the raised LDS limits are remembered per context)."""
     opts = {"length_smooth": False, "penalty_smooth": True, "obstacle_smooth": True,
             "maxratio_smooth": False}
     starts = [{"nfz": 8, "map_seed": 5,

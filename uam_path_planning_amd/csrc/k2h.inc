@@ -561,24 +561,8 @@ __device__ __forceinline__ void h_final_wg(KParams p, KGrp kg, KOut out,
             for (int s = 0; s < NR; ++s) g[s] = slot[(int64_t)min(s, kg.nseg - 1) * kg.P + gp];
         }
         const double4 pr = reinterpret_cast<const double4*>(kg.pairs)[q0 + qi];
-        const UGeo u = kg.ugeo[di];
-        // sim_geo (oracle): h = |v| / 2, h^2 = |v|^2 / 4
-        const double vx = pr.x - pr.z, vy = pr.y - pr.w;
-        const double sv = vx * vx + vy * vy;
-        const double h = sqrt(sv) * 0.5, h2 = sv * 0.25;
-        const bool ls = p.length_smooth != 0;
-        double L;
-        if (p.quirk_length) {
-            const double ax = p.anchor_mode ? p.anchor_x : pr.x;
-            const double ay = p.anchor_mode ? p.anchor_y : pr.y;
-            const double dx = pr.x - ax, dy = pr.y - ay;
-            const double n = sqrt(dx * dx + dy * dy);
-            L = (ls ? n * n : n) + (ls ? h2 * u.s2n : h * u.s1n);
-        } else {
-            L = ls ? h2 * u.s2a : h * u.s1a;
-        }
-        const double len = h * u.s1a;
-        const double ksum = (h > 0.0 && h < INFINITY) ? h * u.e12 + u.e3 : 0.0;
+        double L, len, ksum;
+        sim_geo(p, kg.ugeo[di], pr.x, pr.y, pr.z, pr.w, L, len, ksum);
         double nsum = 0.0, hmax = -INFINITY;
         int32_t nh = 0, off = 0;
         double cost = (double)(p.N + 1) * L;

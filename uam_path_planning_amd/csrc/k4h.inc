@@ -1,9 +1,10 @@
 // k4h.inc -- K4h, the packed volume in the similarity form: VSlot / VSlotX, KVol4, the pack
 // kernels (k_volume_pack_planes, k_volume_pack_t4, k_volume_codes), KProf, v_path_seed,
-// k_v_hist_f (k_v_hist / k_vp_hist), k_v_eval (k_v_eval_x: its exact form; k_vp_eval /
-// k_vp_eval_x: its instances with the profile table), k_v_final / k_v_final_x.
+// k_v_eval (k_v_eval_x: its exact form; k_vp_eval / k_vp_eval_x: its instances with the profile
+// table), v_path_slots, k_v_final / k_v_final_x.  The histogram launch (k_v_hist / k_vp_hist) is
+// gsort.inc's k_sort_hist.
 // Included in the anonymous namespace of uampath.hip; relies on its text above (the device tables,
-// arc_point, pk_bound_decode, pk_terms_k, xcd_chunk, K2g's KGrp, UGeo, G_* limits, put_*) and on
+// arc_point, pk_bound_decode, pk_terms_k, xcd_chunk, K2g's KGrp, UGeo, sim_geo, put_*) and on
 // k2h.inc (X128, x_add, x_term, x_result).
 //
 // The seed, the histogram and the evaluation serve two forms of the altitude: K4h's straight
@@ -292,114 +293,6 @@ __device__ __forceinline__ double v_path_seed(const KParams& p, const KVol4& vs,
     return best == NONE ? INFINITY
                         : zbest - (double)reinterpret_cast<const float*>(vs.pk + vs.ot4)[best];
 }
-
-// sort, launch 1 (K4h, K4hp): keys on (altitude band, tile) of each item's middle waypoint.
-// PROF: at the profile's own z (its three coefficients loaded with the batch), so the profiles
-// of a lateral candidate that fly at different heights fall into different bands.
-template <class... F>
-__global__ __launch_bounds__(1024) void k_v_hist_f(KParams p, KVol4 vs, KGrp kg, F... f) {
-    constexpr bool PROF = sizeof...(F) != 0;
-    [[maybe_unused]] const KProf kf = prof_of(f...);
-    __shared__ __attribute__((aligned(16))) int32_t h[G_BINS_MAX];
-    __shared__ uint16_t tk[1 << (2 * G_TBITS_MAX)];
-    // with kg.seed_lds: the packed header and the unit-arc table staged for the seeds
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_vhist_dyn[];
-    const int t = threadIdx.x, b = blockIdx.x;
-    if (b == 0 && t == 0) *kg.err = 0;
-    for (int k = t; k < kg.bins; k += 1024) h[k] = 0;
-    for (int k = t; k < (1 << (2 * kg.tbits)); k += 1024) tk[k] = kg.tkey[k];
-    const uint32_t* s_hdr = vs.hdr;
-    const double2* s_ut = reinterpret_cast<const double2*>(kg.utab);
-    if (kg.ubp && kg.seed_lds) {
-        uint4* dh = reinterpret_cast<uint4*>(s_vhist_dyn);
-        const uint4* gh = reinterpret_cast<const uint4*>(vs.hdr);
-        for (int k = t; k < (vs.hwords >> 2); k += 1024) dh[k] = gh[k];
-        double2* du = reinterpret_cast<double2*>(s_vhist_dyn + vs.hwords);
-        for (int k = t; k < kg.D * p.N; k += 1024) du[k] = s_ut[k];
-        s_hdr = s_vhist_dyn;
-        s_ut = du;
-    }
-    __syncthreads();
-    const int64_t lo = ((int64_t)kg.P * b / G_NBK) * kg.nseg;
-    const int64_t hi = ((int64_t)kg.P * (b + 1) / G_NBK) * kg.nseg;
-    const int N = p.N, W = kg.W;
-    const int tiles = 1 << (2 * kg.tbits);
-    [[maybe_unused]] const double inv_w1 = 1.0 / (double)(W - 1);
-    // U items per thread with all their loads issued first (k_g_hist's batching)
-    constexpr int U = 4;
-    for (int64_t i0 = lo + t; i0 < hi; i0 += 1024 * U) {
-        double pr[U][6];
-        [[maybe_unused]] double zc[U][3];
-        double2 u[U];
-        int jm[U], sg[U];
-#pragma unroll
-        for (int k = 0; k < U; ++k) {
-            const int32_t i = (int32_t)min(i0 + k * 1024, hi - 1);
-            const int32_t path = (int32_t)div_magic((uint32_t)i, kg.m_nseg, kg.sh_nseg);
-            sg[k] = (int)(i - (int64_t)path * kg.nseg);
-            int32_t q, d;
-            [[maybe_unused]] int32_t ap = 0;  // the profile
-            if constexpr (PROF) {
-                vp_split(kg, kf, path, q, d, ap);
-            } else {
-                q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d);
-                d = path - q * kg.D;
-            }
-            const int j0 = sg[k] * kg.G, j1 = min(j0 + kg.G, W);
-            jm[k] = (j0 + j1 - 1) >> 1;
-            const double2* pp = reinterpret_cast<const double2*>(kg.pairs + (int64_t)q * 6);
-            const double2 a = pp[0], b2 = pp[1], c = pp[2];
-            pr[k][0] = a.x, pr[k][1] = a.y, pr[k][2] = b2.x, pr[k][3] = b2.y, pr[k][4] = c.x,
-            pr[k][5] = c.y;
-            u[k] = reinterpret_cast<const double2*>(kg.utab)[d * N + min(max(jm[k] - 1, 0), N - 1)];
-            if constexpr (PROF) {
-                const double* zr = kf.ztab + ((int64_t)ap * W + jm[k]) * 3;
-                zc[k][0] = zr[0], zc[k][1] = zr[1], zc[k][2] = zr[2];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < U; ++k) {
-            const int64_t i = i0 + k * 1024;
-            if (i >= hi) break;
-            double x0, x1;
-            if (jm[k] == 0) {
-                x0 = pr[k][0], x1 = pr[k][1];
-            } else if (jm[k] == W - 1) {
-                x0 = pr[k][3], x1 = pr[k][4];
-            } else {
-                arc_point(pr[k][0], pr[k][1], pr[k][3], pr[k][4], u[k].x, u[k].y, x0, x1);
-            }
-            // (the key only orders the items: j / (W-1) by a reciprocal is exact enough)
-            double z;
-            if constexpr (PROF) z = (pr[k][2] * zc[k][0] + pr[k][5] * zc[k][1]) + zc[k][2];
-            else z = vz_at(pr[k][2], pr[k][5], (double)jm[k] * inv_w1);
-            const double tx = (x0 - vs.x0) * vs.inv_dx, ty = (vs.y_top - x1) * vs.inv_dy;
-            const double tz = (z - vs.z0) * vs.inv_dz;
-            uint32_t key = kg.bins - 1;
-            if ((tx >= 0.0) && (tx < (double)vs.nx) && (ty >= 0.0) && (ty < (double)vs.ny) &&
-                (tz >= 0.0) && (tz < (double)vs.nz)) {
-                const uint32_t cx = (uint32_t)tx >> kg.tshift, cy = (uint32_t)ty >> kg.tshift;
-                key = ((uint32_t)tz >> vs.zshift) * tiles + tk[(cy << kg.tbits) | cx];
-                // (kg.last_bin is 0, one bin per tile and band, as K2h's: k_v_eval masks the
-                // slots past a lane's group and pads s_u / s_jw by G + 16 slots; the profile
-                // form never had the statement)
-                if constexpr (!PROF)
-                    if (sg[k] == kg.nseg - 1) key += kg.last_bin;
-            }
-            kg.key[i] = (uint16_t)key;
-            atomicAdd(&h[key], 1);
-        }
-    }
-    if (kg.ubp) {  // the partition's paths' clearance seeds, one thread per path
-        const int64_t plo = (int64_t)kg.P * b / G_NBK, phi = (int64_t)kg.P * (b + 1) / G_NBK;
-        for (int64_t pth = plo + t; pth < phi; pth += 1024)
-            kg.ubp[pth] = v_path_seed(p, vs, kg, (int32_t)pth, s_hdr, s_ut, f...);
-    }
-    __syncthreads();
-    for (int k = t; k < kg.bins; k += 1024) kg.cnt[(int64_t)k * G_NBK + b] = h[k];
-}
-constexpr auto k_v_hist = k_v_hist_f<>;
-constexpr auto k_vp_hist = k_v_hist_f<KProf>;
 
 // every (path, group) item in sorted order (h_item's phases): the CH waypoints' voxels (x, y by
 // the arc formula or the pair's end points, z on the linear climb), the header reads, then per
@@ -730,17 +623,51 @@ constexpr auto k_vp_eval = k_v_eval<CH, TE, EX, KProf>;
 template <int CH, bool TE>
 constexpr auto k_vp_eval_x = k_v_eval<CH, TE, true, KProf>;
 
-// outputs of every path (block = 64 pairs x D): the similarity-form geometry (oracle sim_geo on
-// the pair's x/y), cost = (N+1) L + the risk / N partials in group order, min clearance, the
-// counts, and the main.py:175-180 selection
-// EX (UAM_OPT_EXACT_SUM_VOLUME): a path's VSlotX sums added as integers and their flags ORed,
-// each field rounded once (x_result), cost = (N+1) L + fl(S_risk) / N, nfz_sum = fl(S_psi)
+// path gp's slots in group order (the K4h, K4hp and K4hp+v output launches): the risk / N
+// partials onto cost (the caller's (N+1) L), nfz_sum, the minimum clearance and the three counts
+// EX (UAM_OPT_EXACT_SUM_VOLUME): the VSlotX sums added as integers and their flags ORed, each
+// field rounded once (x_result, a true division): cost = (N+1) L + fl(S_risk) / N, nfz_sum =
+// fl(S_psi)
+template <bool EX>
+__device__ __forceinline__ void v_path_slots(const KGrp& kg, int64_t gp, int N, int32_t e_risk,
+                                             int32_t e_psi, double& cost, double& nsum,
+                                             double& cm, int32_t& nh, int32_t& off,
+                                             int32_t& bel) {
+    using Slot = std::conditional_t<EX, VSlotX, VSlot>;
+    const Slot* slot = reinterpret_cast<const Slot*>(kg.slot);
+    nsum = 0.0, cm = INFINITY;
+    nh = off = bel = 0;
+    X128 xc = {0, 0}, xn = {0, 0};
+    uint32_t xfl = 0;
+    for (int s = 0; s < kg.nseg; ++s) {
+        const Slot g = slot[(int64_t)s * kg.P + gp];
+        if constexpr (EX) {
+            xc = x_add(xc, X128{g.c_lo, g.c_hi});
+            xn = x_add(xn, X128{g.n_lo, g.n_hi});
+            xfl |= g.cnt >> 24;
+        } else {
+            cost = cost + g.cost;
+            nsum = nsum + g.psi;
+        }
+        cm = fmin(cm, g.cm);
+        nh += (int32_t)(g.cnt & 255u);
+        off += (int32_t)((g.cnt >> 8) & 255u);
+        bel += (int32_t)((g.cnt >> 16) & 255u);
+    }
+    if constexpr (EX) {
+        cost = cost + x_result(xc, xfl & 7u, e_risk) / (double)N;
+        nsum = x_result(xn, (xfl >> 3) & 7u, e_psi);
+    }
+}
+
+// outputs of every path (block = 64 pairs x D): the similarity-form geometry (sim_geo on the
+// pair's x/y), cost = (N+1) L + the slots' partials (v_path_slots), min clearance, the counts,
+// and the main.py:175-180 selection
 template <bool EX>
 __device__ __forceinline__ void v_final_wg(KParams p, KGrp kg, KOut out,
                                            int32_t* __restrict__ best_f,
                                            int32_t* __restrict__ best_l, int32_t e_risk,
                                            int32_t e_psi) {
-    using Slot = std::conditional_t<EX, VSlotX, VSlot>;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int D = kg.D, t = threadIdx.x;
     double* s_cost = smem;
@@ -748,51 +675,14 @@ __device__ __forceinline__ void v_final_wg(KParams p, KGrp kg, KOut out,
     const int64_t q0 = (int64_t)blockIdx.x * 64;
     const int qi = t / D, di = t - qi * D;
     const bool bad = *kg.err != 0;  // an inconsistent sort (k_g_scatter / k_v_hist)
-    const Slot* slot = reinterpret_cast<const Slot*>(kg.slot);
     if (q0 + qi < kg.n_pairs) {
         const int64_t gp = (q0 + qi) * D + di;
         const double* pr = kg.pairs + (q0 + qi) * 6;
-        const double x0 = pr[0], y0 = pr[1], xf = pr[3], yf = pr[4];
-        const UGeo u = kg.ugeo[di];
-        const double vx = x0 - xf, vy = y0 - yf;
-        const double sv = vx * vx + vy * vy;
-        const double h = sqrt(sv) * 0.5, h2 = sv * 0.25;
-        const bool ls = p.length_smooth != 0;
-        double L;
-        if (p.quirk_length) {
-            const double axx = p.anchor_mode ? p.anchor_x : x0;
-            const double ayy = p.anchor_mode ? p.anchor_y : y0;
-            const double dx = x0 - axx, dy = y0 - ayy;
-            const double n = sqrt(dx * dx + dy * dy);
-            L = (ls ? n * n : n) + (ls ? h2 * u.s2n : h * u.s1n);
-        } else {
-            L = ls ? h2 * u.s2a : h * u.s1a;
-        }
-        const double len = h * u.s1a;
-        const double ksum = (h > 0.0 && h < INFINITY) ? h * u.e12 + u.e3 : 0.0;
-        double cost = (double)(p.N + 1) * L, nsum = 0.0, cm = INFINITY;
-        int32_t nh = 0, off = 0, bel = 0;
-        X128 xc = {0, 0}, xn = {0, 0};
-        uint32_t xfl = 0;
-        for (int s = 0; s < kg.nseg; ++s) {
-            const Slot g = slot[(int64_t)s * kg.P + gp];
-            if constexpr (EX) {
-                xc = x_add(xc, X128{g.c_lo, g.c_hi});
-                xn = x_add(xn, X128{g.n_lo, g.n_hi});
-                xfl |= g.cnt >> 24;
-            } else {
-                cost = cost + g.cost;
-                nsum = nsum + g.psi;
-            }
-            cm = fmin(cm, g.cm);
-            nh += (int32_t)(g.cnt & 255u);
-            off += (int32_t)((g.cnt >> 8) & 255u);
-            bel += (int32_t)((g.cnt >> 16) & 255u);
-        }
-        if constexpr (EX) {  // one rounding per field, a true division
-            cost = cost + x_result(xc, xfl & 7u, e_risk) / (double)p.N;
-            nsum = x_result(xn, (xfl >> 3) & 7u, e_psi);
-        }
+        double L, len, ksum;
+        sim_geo(p, kg.ugeo[di], pr[0], pr[1], pr[3], pr[4], L, len, ksum);
+        double cost = (double)(p.N + 1) * L, nsum, cm;
+        int32_t nh, off, bel;
+        v_path_slots<EX>(kg, gp, p.N, e_risk, e_psi, cost, nsum, cm, nh, off, bel);
         put_outputs(out, gp, bad, cost, L, len, ksum, nsum, cm, nh, off, bel);
         s_cost[di * 64 + qi] = cost;
         s_len[di * 64 + qi] = len;

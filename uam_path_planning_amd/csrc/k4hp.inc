@@ -3,43 +3,8 @@
 // terms) and k_vp_sel_check.  The sort and the evaluation are k4h.inc's kernels with a trailing
 // KProf (k_vp_hist, k_vp_eval / k_vp_eval_x); KProf, vp_z and vp_split stand there.
 // Included in the anonymous namespace of uampath.hip after k4h.inc; relies on its text (VSlot /
-// VSlotX, KProf) and on what k4h.inc relies on; K4hp+v also on KVert, VertAcc, vert_begin and
+// VSlotX, KProf, v_path_slots) and on what k4h.inc relies on; K4hp+v also on KVert, VertAcc, vert_begin and
 // vert_segment (uampath.hip, K4e+v / K4p+v).  Definition: include/uampath.h.
-
-// path gp's slots in group order, as v_final_wg's loop: the risk / N partials onto cost (the
-// caller's (N+1) L), nfz_sum, the minimum clearance and the three counts (EX: the slots' sums
-// added as integers and each field rounded once, a true division)
-template <bool EX>
-__device__ __forceinline__ void vp_path_slots(const KGrp& kg, int64_t gp, int N, int32_t e_risk,
-                                              int32_t e_psi, double& cost, double& nsum,
-                                              double& cm, int32_t& nh, int32_t& off,
-                                              int32_t& bel) {
-    using Slot = std::conditional_t<EX, VSlotX, VSlot>;
-    const Slot* slot = reinterpret_cast<const Slot*>(kg.slot);
-    nsum = 0.0, cm = INFINITY;
-    nh = off = bel = 0;
-    X128 xc = {0, 0}, xn = {0, 0};
-    uint32_t xfl = 0;
-    for (int s = 0; s < kg.nseg; ++s) {
-        const Slot g = slot[(int64_t)s * kg.P + gp];
-        if constexpr (EX) {
-            xc = x_add(xc, X128{g.c_lo, g.c_hi});
-            xn = x_add(xn, X128{g.n_lo, g.n_hi});
-            xfl |= g.cnt >> 24;
-        } else {
-            cost = cost + g.cost;
-            nsum = nsum + g.psi;
-        }
-        cm = fmin(cm, g.cm);
-        nh += (int32_t)(g.cnt & 255u);
-        off += (int32_t)((g.cnt >> 8) & 255u);
-        bel += (int32_t)((g.cnt >> 16) & 255u);
-    }
-    if constexpr (EX) {
-        cost = cost + x_result(xc, xfl & 7u, e_risk) / (double)N;
-        nsum = x_result(xn, (xfl >> 3) & 7u, e_psi);
-    }
-}
 
 // outputs of every path, one thread per path (v_final_wg's 64 x D block does not reach D A =
 // 128): the similarity-form geometry of the path's (q, d) -- the same for its A profiles -- and
@@ -54,27 +19,11 @@ __device__ __forceinline__ void vp_final_path(const KParams& p, const KGrp& kg, 
     int32_t q, di, a;
     vp_split(kg, kf, (int32_t)gp, q, di, a);
     const double* pr = kg.pairs + (int64_t)q * 6;
-    const double x0 = pr[0], y0 = pr[1], xf = pr[3], yf = pr[4];
-    const UGeo u = kg.ugeo[di];
-    const double vx = x0 - xf, vy = y0 - yf;
-    const double sv = vx * vx + vy * vy;
-    const double h = sqrt(sv) * 0.5, h2 = sv * 0.25;
-    const bool ls = p.length_smooth != 0;
-    double L;
-    if (p.quirk_length) {
-        const double axx = p.anchor_mode ? p.anchor_x : x0;
-        const double ayy = p.anchor_mode ? p.anchor_y : y0;
-        const double dx = x0 - axx, dy = y0 - ayy;
-        const double n = sqrt(dx * dx + dy * dy);
-        L = (ls ? n * n : n) + (ls ? h2 * u.s2n : h * u.s1n);
-    } else {
-        L = ls ? h2 * u.s2a : h * u.s1a;
-    }
-    const double len = h * u.s1a;
-    const double ksum = (h > 0.0 && h < INFINITY) ? h * u.e12 + u.e3 : 0.0;
+    double L, len, ksum;
+    sim_geo(p, kg.ugeo[di], pr[0], pr[1], pr[3], pr[4], L, len, ksum);
     double cost = (double)(p.N + 1) * L, nsum, cm;
     int32_t nh, off, bel;
-    vp_path_slots<EX>(kg, gp, p.N, e_risk, e_psi, cost, nsum, cm, nh, off, bel);
+    v_path_slots<EX>(kg, gp, p.N, e_risk, e_psi, cost, nsum, cm, nh, off, bel);
     put_outputs(out, gp, bad, cost, L, len, ksum, nsum, cm, nh, off, bel);
 }
 __global__ __launch_bounds__(256) void k_vp_final(KParams p, KGrp kg, KProf kf, KOut out) {
@@ -140,7 +89,7 @@ __device__ __forceinline__ void vp_final_v_path(const KParams& p, const KGrp& kg
     }
     double cost = (double)(N + 1) * g.L, nsum, cm;
     int32_t nh, off, bel;
-    vp_path_slots<EX>(kg, gp, N, e_risk, e_psi, cost, nsum, cm, nh, off, bel);
+    v_path_slots<EX>(kg, gp, N, e_risk, e_psi, cost, nsum, cm, nh, off, bel);
     put_outputs(out, gp, bad, cost, g.L, g.len, g.ksum, nsum, cm, nh, off, bel);
     if (v.climb) v.climb[gp] = bad ? __builtin_nan("") : g.csum;
 }

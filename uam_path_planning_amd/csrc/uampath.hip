@@ -29,15 +29,18 @@
 //   Pair order         k_pair_bounds k_pair_keys k_pair_scan k_pair_scatter (K3)
 //                      k_rorder_hist k_rorder_scatter (K2)
 //   (K2s)              k_seg_hist k_seg_scatter k_seg_eval k_seg_final
-//   (K2g)              k_g_hist k_g_scatter k_g_eval k_g_final
+//   (K2g)              k_g_eval k_g_final; the similarity-form geometry (sim_geo) of the K2h /
+//                      K4h / K4hp output launches
 //   k2h.inc            K2h: k_h_eval k_h_eval_x k_cells k_h_final k_h_final_x; the exact-sum
 //                      arithmetic (X128) host and device share
 //   sum_scale.inc      k_sum_scale_init k_sum_scale
-//   k4h.inc            K4h: k_volume_pack_planes k_volume_pack_t4 k_volume_codes k_v_hist
-//                      k_v_eval (k_v_eval_x) k_v_final k_v_final_x; with a trailing KProf,
-//                      K4hp's k_vp_hist k_vp_eval (k_vp_eval_x)
+//   k4h.inc            K4h: k_volume_pack_planes k_volume_pack_t4 k_volume_codes k_v_eval
+//                      (k_v_eval_x) k_v_final k_v_final_x; with a trailing KProf, K4hp's
+//                      k_vp_eval (k_vp_eval_x)
 //   k4hp.inc           K4hp: k_vp_final k_vp_final_x k_vp_sel_check; K4hp+v: k_vp_final_v
 //                      k_vp_final_xv
+//   gsort.inc          the grouped forms' counting sort: k_sort_hist (one body: k_g_hist,
+//                      k_v_hist, k_vp_hist) k_g_scatter
 //   struct uam_ctx and its helpers; then the C ABI (include/uampath.h) with the launches'
 //   static helpers between its entry points: context, geometry, params, K1; K2w launch; the
 //   option table; pair-order scratch and K2s launch; the grouped plan (K2g / K2h / K4h / K4hp);
@@ -5492,14 +5495,7 @@ __global__ __launch_bounds__(1024) void k_seg_final(KParams p, KSeg ks, KOut out
 // the evaluation cost ~90 us of its 130-150).  Against the sequential reference the grouped
 // sums differ by rounding only (<= 1e-12 relative, tests/test_oracle_golden.py); against the
 // grouped oracle they are bit-exact.
-constexpr int G_TBITS_MAX = 6;                          // up to 64 x 64 tiles over the raster
-// tile bins twice over (K2g: a ragged last group's items have their own; K2h / K4h sort on one
-// bin per tile and use half of them) + one for off-raster / NaN
-constexpr int G_BINS_MAX = (2 << (2 * G_TBITS_MAX)) + 1;
-constexpr int G_NBK = UAM_G_NBK;                        // partitions of the counting sort
-constexpr int G_HIST_DYN_MAX = 119 * 1024;  // k_g_hist's dynamic LDS (K2h seeds) beside its 40 KiB
-constexpr int G_MAXLEN = 64;                            // longest group
-constexpr int G_UTAB_LDS = 48 * 1024;                   // K2g: unit-arc table (in LDS) up to this
+// (The sort's limits G_* and its launches k_g_hist and k_g_scatter: gsort.inc.)
 
 struct alignas(16) GSlot {  // 48 B per (path, group), written by one lane
     double cost;     // partial sums from +0.0 in waypoint order: Phi/N,
@@ -5545,6 +5541,29 @@ __device__ void unit_geo_row(const KParams& p, const double2* __restrict__ u, UG
         qx = cx, qy = cy, pdx = dx, pdy = dy, pb = b;
     }
     out->s1n = s1n, out->s2n = s2n, out->s1a = s1a, out->s2a = s2a, out->e12 = e12, out->e3 = e3;
+}
+
+// the similarity-form geometry of a path (oracle sim_geo) in the K2h / K4h / K4hp output
+// launches: get_cost's length term L, the true length and the kinematic rows from the pair's
+// scale h = |v| / 2 (h^2 = |v|^2 / 4) and its displacement row's unit sums
+__device__ __forceinline__ void sim_geo(const KParams& p, const UGeo& u, double x0, double y0,
+                                        double xf, double yf, double& L, double& len,
+                                        double& ksum) {
+    const double vx = x0 - xf, vy = y0 - yf;
+    const double sv = vx * vx + vy * vy;
+    const double h = sqrt(sv) * 0.5, h2 = sv * 0.25;
+    const bool ls = p.length_smooth != 0;
+    if (p.quirk_length) {
+        const double ax = p.anchor_mode ? p.anchor_x : x0;
+        const double ay = p.anchor_mode ? p.anchor_y : y0;
+        const double dx = x0 - ax, dy = y0 - ay;
+        const double n = sqrt(dx * dx + dy * dy);
+        L = (ls ? n * n : n) + (ls ? h2 * u.s2n : h * u.s1n);
+    } else {
+        L = ls ? h2 * u.s2a : h * u.s1a;
+    }
+    len = h * u.s1a;
+    ksum = (h > 0.0 && h < INFINITY) ? h * u.e12 + u.e3 : 0.0;
 }
 
 struct KGrp {
@@ -5776,164 +5795,6 @@ __device__ __forceinline__ float h_path_seed(const KParams& p, const KRaster& rs
         for (int k = 0; k < K; ++k) take(in[k], ix[k], iy[k], e[k], sb[k]);
     }
     return best == NONE ? -INFINITY : best == OFF ? 0.0f : rs.t4[best];
-}
-
-// counting sort, launch 1: partition b = paths [P b / NBK, P (b+1) / NBK); keys of all their
-// groups (the tile under the group's middle waypoint) and the partition's histogram, stored
-// bin-major so the scan yields each (bin, partition)'s offset
-__global__ __launch_bounds__(1024) void k_g_hist(KParams p, KRaster rs, KGrp kg) {
-    __shared__ __attribute__((aligned(16))) int32_t h[G_BINS_MAX];
-    __shared__ uint16_t tk[1 << (2 * G_TBITS_MAX)];  // the tile-key table (curve order)
-    // K2h with kg.seed_lds: the packed header and the unit-arc table staged for the seeds
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_hist_dyn[];
-    const int t = threadIdx.x, b = blockIdx.x;
-    if (b == 0 && t == 0) *kg.err = 0;
-    for (int k = t; k < kg.bins; k += 1024) h[k] = 0;
-    for (int k = t; k < (1 << (2 * kg.tbits)); k += 1024) tk[k] = kg.tkey[k];
-    const uint32_t* s_hdr = rs.pmap;
-    const double2* s_ut = reinterpret_cast<const double2*>(kg.utab);
-    if (kg.lbp && kg.seed_lds) {
-        uint4* dh = reinterpret_cast<uint4*>(s_hist_dyn);
-        const uint4* gh = reinterpret_cast<const uint4*>(rs.pmap);
-        for (int k = t; k < (rs.hwords >> 2); k += 1024) dh[k] = gh[k];
-        double2* du = reinterpret_cast<double2*>(s_hist_dyn + rs.hwords);
-        for (int k = t; k < kg.D * p.N; k += 1024) du[k] = s_ut[k];
-        s_hdr = s_hist_dyn;
-        s_ut = du;
-    }
-    __syncthreads();
-    // thread = item (consecutive threads: the groups of one path, then the next path's), so
-    // the key stores are coalesced and a path's pair is one broadcast load; U items per thread
-    // with all their loads issued first (indices clamped into the partition)
-    const int64_t lo = ((int64_t)kg.P * b / G_NBK) * kg.nseg;
-    const int64_t hi = ((int64_t)kg.P * (b + 1) / G_NBK) * kg.nseg;
-    const int N = p.N, W = kg.W;
-    constexpr int U = 4;
-    for (int64_t i0 = lo + t; i0 < hi; i0 += 1024 * U) {
-        double4 pr[U];
-        double2 u[U];
-        int jm[U], sg[U];
-#pragma unroll
-        for (int k = 0; k < U; ++k) {
-            const int32_t i = (int32_t)min(i0 + k * 1024, hi - 1);
-            const int32_t path = (int32_t)div_magic((uint32_t)i, kg.m_nseg, kg.sh_nseg);
-            sg[k] = i - path * kg.nseg;
-            const int32_t q = (int32_t)div_magic((uint32_t)path, kg.m_d, kg.sh_d);
-            const int32_t d = path - q * kg.D;
-            const int j0 = sg[k] * kg.G, j1 = min(j0 + kg.G, W);
-            jm[k] = (j0 + j1 - 1) >> 1;  // the group's middle waypoint
-            pr[k] = reinterpret_cast<const double4*>(kg.pairs)[q];
-            u[k] = reinterpret_cast<const double2*>(kg.utab)[d * N + min(max(jm[k] - 1, 0), N - 1)];
-        }
-#pragma unroll
-        for (int k = 0; k < U; ++k) {
-            const int64_t i = i0 + k * 1024;
-            if (i >= hi) break;
-            double x0, x1;  // PathSrc::at's point
-            if (jm[k] == 0) {
-                x0 = pr[k].x, x1 = pr[k].y;
-            } else if (jm[k] == W - 1) {
-                x0 = pr[k].z, x1 = pr[k].w;
-            } else {
-                arc_point(pr[k].x, pr[k].y, pr[k].z, pr[k].w, u[k].x, u[k].y, x0, x1);
-            }
-            // the key: the position of the point's tile of the 2^tbits x 2^tbits grid on the
-            // tile curve (Hilbert by default: consecutive tiles always adjacent), bins - 1 off
-            // the raster or NaN
-            const double fx = floor((x0 - rs.x0) * rs.inv_dx);
-            const double fy = floor((rs.y_top - x1) * rs.inv_dy);
-            uint32_t key = kg.bins - 1;
-            if ((fx >= 0.0) && (fx < (double)rs.nx) && (fy >= 0.0) && (fy < (double)rs.ny)) {
-                const uint32_t tx = (uint32_t)fx >> kg.tshift, ty = (uint32_t)fy >> kg.tshift;
-                key = tk[(ty << kg.tbits) | tx];
-                // K2g (kg.last_bin > 0): a ragged last group's items in their own bins; the
-                // waves then rarely mix group lengths, so k_g_eval's straight-line chunks stay
-                // wave-uniform.  K2h adds nothing (kg.last_bin == 0, one bin per tile): h_item's
-                // chunk loop runs the wave's most chunks and masks every slot past a lane's own
-                // group (vjb, vinB, nvB), and its LDS rows are padded by G + CH slots, which
-                // covers a last group of one waypoint in a wave of full ones -- so a wave may
-                // mix group lengths freely, and the last groups' items stay among their tile's
-                // other items instead of forming a sparse second pass over all the tiles
-                if (sg[k] == kg.nseg - 1) key += kg.last_bin;
-            }
-            kg.key[i] = (uint16_t)key;
-            atomicAdd(&h[key], 1);
-        }
-    }
-    if (kg.lbp) {  // K2h: the partition's paths' terrain seeds, one thread per path
-        const int64_t plo = (int64_t)kg.P * b / G_NBK, phi = (int64_t)kg.P * (b + 1) / G_NBK;
-        for (int64_t pth = plo + t; pth < phi; pth += 1024)
-            kg.lbp[pth] = h_path_seed(p, rs, kg, (int32_t)pth, s_hdr, s_ut);
-    }
-    __syncthreads();
-    // the partition's count per bin, bin-major ([bin][partition]): k_scan_local's exclusive
-    // scan of it is each (bin, partition)'s place, up to its scan block's total
-    for (int k = t; k < kg.bins; k += 1024) kg.cnt[(int64_t)k * G_NBK + b] = h[k];
-}
-
-// launch 3 (after k_scan_local over cnt; the scan blocks' totals are scanned here, or by
-// k_scan_totals beyond 1024 of them): LDS cursors, items scattered; U keys per thread loaded
-// before the first cursor update.  The order of the items inside a (bin, partition) run follows
-// the LDS atomics: it only decides which lane evaluates an item, never what the item computes.
-// (A two-launch form -- device-scope
-// atomics on the bin totals in the histogram launch, their scan in this one -- ran the
-// histogram 11 -> 34 us at cfg3: 256 partitions' atomics on each bin address serialise
-// across the XCDs; profiles/r04/prof1.)
-__global__ __launch_bounds__(1024) void k_g_scatter(KParams p, KGrp kg) {
-    __shared__ __attribute__((aligned(16))) int32_t cur[G_BINS_MAX];
-    __shared__ int32_t stot[1024];
-    __shared__ int32_t wsum[16];
-    const int t = threadIdx.x;
-    // K2h / K4h: block 0 forms the unit rows through its LDS (dispatched first, so hidden under
-    // the scatter); the partitions are the other blocks
-    if (kg.ugeo && blockIdx.x == 0) {
-        unit_geo_block(p, kg, reinterpret_cast<double2*>(cur), (int)sizeof(cur));
-        return;
-    }
-    const int b = blockIdx.x - (kg.ugeo ? 1 : 0);
-    if (kg.test_fault && b == 0 && t == 0) atomicOr(kg.err, 1);  // (UAM_OPT_TEST_SORT_FAULT)
-    const int nsb = kg.nsb_raw;
-    if (nsb > 0) {  // the scan's block totals, scanned here (replaces k_scan_totals' launch)
-        const int32_t v = t < nsb ? kg.tot[t] : 0;
-        const int lane = t & 63, wv = t >> 6;
-        int32_t x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wsum[wv] = x;
-        __syncthreads();
-        int32_t woff = 0;
-        for (int k = 0; k < wv; ++k) woff += wsum[k];
-        stot[t] = woff + x - v;
-        __syncthreads();
-    }
-    for (int k = t; k < kg.bins; k += 1024) {
-        const int64_t c = (int64_t)k * G_NBK + b;
-        const int sb = (int)(c / (256 * SCAN_ITEMS));
-        cur[k] = kg.cnt[c] + (nsb > 0 ? stot[sb] : kg.tot[sb]);
-    }
-    __syncthreads();
-    const int64_t lo = ((int64_t)kg.P * b / G_NBK) * kg.nseg;
-    const int64_t hi = ((int64_t)kg.P * (b + 1) / G_NBK) * kg.nseg;
-    constexpr int U = 8;
-    for (int64_t i0 = lo + t; i0 < hi; i0 += 1024 * U) {
-        uint16_t kk[U];
-#pragma unroll
-        for (int k = 0; k < U; ++k) kk[k] = kg.key[min(i0 + k * 1024, hi - 1)];
-#pragma unroll
-        for (int k = 0; k < U; ++k) {
-            const int64_t i = i0 + k * 1024;
-            if (i < hi) {
-                const int32_t at = atomicAdd(&cur[kk[k]], 1);
-                if ((uint32_t)at < (uint32_t)kg.n_items)
-                    kg.order[at] = (int32_t)i;
-                else
-                    atomicOr(kg.err, 1);  // never in a consistent sort: poisons the outputs
-            }
-        }
-    }
 }
 
 // sqrt(x) for x in [2^-767, 2^1000]: the gfx9 lowering of sqrt(double) (rsq, then two
@@ -6276,6 +6137,9 @@ __global__ __launch_bounds__(1024) void k_g_final(KParams p, KGrp kg, KOut out,
 // K4hp: the altitude profiles on the packed, sorted volume: the output launches k_vp_final*
 #include "k4hp.inc"
 
+// the grouped forms' counting sort: k_sort_hist (k_g_hist, k_v_hist, k_vp_hist), k_g_scatter
+#include "gsort.inc"
+
 // K9: route seeds, k_route_cost, k_route_init, k_route_relax, k_route_next, k_route_trace
 #include "k9_route.inc"
 // K9b / K9s: any-angle shortcuts on the traced route, k_route_free_bits, k_route_smooth
@@ -6328,17 +6192,12 @@ struct uam_ctx {
                                 // 2/4/6/8/16, 0 = the lane-per-path K3)
     int k3b_cpl = 1;            // K3b points per lane in the evaluation phase
                                 // (UAM_OPT_K3B_POINTS_PER_LANE: 1, 2)
-    bool k3b_attrs = false;     // K3b dynamic-LDS attributes raised on this context's device
     int64_t wave_max = 16384;   // K2w / K4w for batches of up to this many paths
                                 // (UAM_OPT_WAVE_MAX_PATHS; tools/probe_wave.py crossover)
     int k2s_segs = 2;           // K2s segments per path (UAM_OPT_K2S_SEGMENTS: 2..8)
     int64_t k2s_min = 65536;    // K2g / K2s: smallest batch in paths (UAM_OPT_SORTED_MIN_PATHS)
-    bool k2s_attrs = false;     // K2s dynamic-LDS attributes raised on this context's device
-    bool k2h_attrs = false;     // K2h's dynamic-LDS attributes raised on this context's device
-    bool k2h_hist_attr = false, k4h_hist_attr = false;  // k_g_hist's and k_v_hist's, likewise
-    bool k2g_attrs = false;     // K2g dynamic-LDS attributes raised on this context's device
-    bool k4h_attrs = false;     // the same for K4h
-    bool k4hp_attrs = false, k4hp_hist_attr = false;  // and for K4hp (k_vp_eval, k_vp_hist)
+    std::vector<const void*> lds_raised;  // kernels whose dynamic-LDS limit this context has
+                                          // raised on its device (raise_lds), sorted
     void* d_ord = nullptr;      // pair_order scratch (grow-only)
     uint16_t* d_tkey = nullptr; // K2g: sort key of each tile (curve order), for tkey_bits/curve
     int tkey_bits = -1, tkey_curve = -1;
@@ -6388,7 +6247,6 @@ struct uam_ctx {
     int k9_inner = 16;          // K9 sweeps inside a tile per round (UAM_OPT_K9_INNER: 1..256;
                                 // cfg3 4096^2 at tile 32, centre / corner goal: 4 87 / 64 ms,
                                 // 16 65 / 40, 32 69 / 42, 64 76 / 48)
-    bool k9_attrs = false;      // k_route_relax<64>'s dynamic-LDS attribute raised
     int32_t* h_route = nullptr; // page-locked words the active-tile counts are copied to
     int64_t route_visits = 0;   // uam_route_visits: tiles the last uam_route_field visited
 
@@ -6460,22 +6318,18 @@ int err_word(uam_ctx* ctx, KGrp* kg) {
     return UAM_OK;
 }
 
-// The dynamic-LDS limit of every kernel in the tables raised to `limit` bytes, once per context
-// = per device (the caller's DeviceGuard is active): *done is the context's flag of the tables.
-template <class Tab>
-int raise_lds_table(const Tab& fns, int limit) {
-    for (auto f : fns)
-        HIP_TRY(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    limit));
+// Kernel fn's dynamic-LDS limit raised to `limit` bytes before a launch that asks for more than
+// the default 64 KiB: once per context = per device (the caller's DeviceGuard is active), on the
+// kernel's first such use.  A failed call is not remembered.
+template <class Fn>
+int raise_lds(uam_ctx* ctx, Fn fn, int limit) {
+    const void* f = (const void*)fn;
+    std::vector<const void*>& v = ctx->lds_raised;
+    const auto it = std::lower_bound(v.begin(), v.end(), f, std::less<const void*>());
+    if (it != v.end() && *it == f) return UAM_OK;
+    HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, limit));
+    v.insert(it, f);
     return UAM_OK;
-}
-template <class... Tab>
-int raise_lds(bool* done, int limit, const Tab&... tabs) {
-    if (*done) return UAM_OK;
-    int st = UAM_OK;
-    ((st = st ? st : raise_lds_table(tabs, limit)), ...);
-    *done = !st;
-    return st;
 }
 
 int device_status(uam_ctx* ctx) {
@@ -6484,6 +6338,16 @@ int device_status(uam_ctx* ctx) {
     return fail(UAM_E_DEVICE,
                 "a sorted evaluation (K2h / K2g / K4h) found its counting sort inconsistent on "
                 "the device; that call wrote NaN / -1 to every output of its batch");
+}
+
+// an evaluation entry point's first checks, in the order a caller sees them: an earlier call's
+// failed device check, reported once (uam_device_status), then the context
+int eval_prologue(uam_ctx* ctx) {
+    if (ctx) {
+        const int st = device_status(ctx);
+        if (st) return st;
+    }
+    return check_ctx(ctx, true);
 }
 
 int make_kraster(const uam_raster_desc* d, KRaster* k) {
@@ -6518,6 +6382,16 @@ KOut make_kout(const uam_path_outputs* o) {
     k.g_rows = o->g_rows;
     k.below_terrain = o->below_terrain;
     return k;
+}
+
+// the selections a call asks for; needs (or null: the caller decides later): the refusal's text
+// for a selection without its output -- best_fval_idx reads cost, best_length_idx length
+int selections(const uam_path_outputs* o, const char* needs, int32_t** best_f, int32_t** best_l) {
+    *best_f = o ? o->best_fval_idx : nullptr;
+    *best_l = o ? o->best_length_idx : nullptr;
+    if (needs && ((*best_f && !o->cost) || (*best_l && !o->length)))
+        return fail(UAM_E_INVALID, "%s", needs);
+    return UAM_OK;
 }
 
 }  // namespace
@@ -7013,6 +6887,15 @@ int uam_gen_paths(uam_ctx* ctx, const double* pairs, int64_t n_pairs, const doub
     return UAM_OK;
 }
 
+// uam_argmin's rule over each pair's C candidates: best_f on the costs, best_l on the lengths
+// (either may be null).  The caller reads hipGetLastError.
+static void launch_argmin(const KOut& ko, int64_t n_pairs, int32_t C, int32_t* best_f,
+                          int32_t* best_l, hipStream_t s) {
+    const dim3 g2(grid_for(n_pairs, 256, INT32_MAX));
+    if (best_f) hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.cost, n_pairs, C, 1, best_f);
+    if (best_l) hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.length, n_pairs, C, 0, best_l);
+}
+
 // K2w launch (raster / volume, explicit or generated); returns 1 if launched, 0 if the
 // shape does not fit (caller falls back to the lane-per-path kernels), <0 on error.
 static int launch_wave(uam_ctx* ctx, int mode, bool gen, const KRaster& kr, const KVolume& kv,
@@ -7043,11 +6926,7 @@ static int launch_wave(uam_ctx* ctx, int mode, bool gen, const KRaster& kr, cons
     st = ktime_end(ctx, s);
     if (st) return st;
     if (gen && (best_f || best_l)) {
-        const int64_t n_pairs = n_paths / D;
-        const dim3 g2(grid_for(n_pairs, 256, INT32_MAX));
-        if (best_f) hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.cost, n_pairs, D, 1, best_f);
-        if (best_l)
-            hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.length, n_pairs, D, 0, best_l);
+        launch_argmin(ko, n_paths / D, D, best_f, best_l, s);
         if (hipGetLastError() != hipSuccess) return fail(UAM_E_HIP, "k_argmin launch failed");
     }
     return 1;
@@ -7328,6 +7207,16 @@ static int raster_pair_order(uam_ctx* ctx, const KRaster& kr, const double* pair
     return UAM_OK;
 }
 
+// the raster pair order over a volume's x/y extent (K4, K4p: results do not depend on it)
+static int volume_pair_order(uam_ctx* ctx, const KVolume& kv, const uam_volume_desc* vd,
+                             const double* pairs6, int64_t n, hipStream_t s,
+                             const int32_t** order) {
+    KRaster kxy{};
+    kxy.nx = kv.nx, kxy.ny = kv.ny, kxy.x0 = kv.x0, kxy.y_top = kv.y_top;
+    kxy.dx = vd->dx, kxy.dy = vd->dy;
+    return raster_pair_order(ctx, kxy, pairs6, n, s, order, 1);
+}
+
 // K2s launch (segment-sorted raster evaluation, the reference's sequential sums); returns 1 if
 // launched, 0 if the batch is not one it takes (the caller runs K2).  Scratch: the pair-order
 // scratch (order_scratch), so two streams sharing the context serialise on it.
@@ -7378,18 +7267,15 @@ static int launch_segmented(uam_ctx* ctx, const KRaster& kr, const void* rec, co
     const size_t lds_min = kr.pmap ? (size_t)kr.pwords * 4 : kr.sum ? (size_t)kr.swords * 4 : 0;
     const size_t lds = std::max(lds_min, (size_t)(kr.pmap ? 40 : 80) * 1024);
     const size_t lds0 = lds_min;
-    if (!ctx->k2s_attrs) {  // per context = per device (the caller's DeviceGuard is active)
-        const void* fns[] = {(const void*)k_seg_eval<true, false>,
-                             (const void*)k_seg_eval<false, false>,
-                             (const void*)k_seg_eval<true, true>,
-                             (const void*)k_seg_eval<false, true>,
-                             (const void*)k_seg_eval<false, true, true>,
-                             (const void*)k_seg_eval<false, false, true>};
-        for (const void* f : fns)
-            HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-        ctx->k2s_attrs = true;
-    }
+    // segment 0's instance (FIRST) and the later segments'
+    const auto ev0 = kr.pmap  ? k_seg_eval<false, true, true>
+                     : kr.sum ? k_seg_eval<true, true, false>
+                              : k_seg_eval<false, true, false>;
+    const auto ev = kr.pmap  ? k_seg_eval<false, false, true>
+                    : kr.sum ? k_seg_eval<true, false, false>
+                             : k_seg_eval<false, false, false>;
+    if (lds0 > 64 * 1024 && (st = raise_lds(ctx, ev0, 160 * 1024))) return st;
+    if (lds > 64 * 1024 && (st = raise_lds(ctx, ev, 160 * 1024))) return st;
     st = side_stream(ctx);
     if (st) return st;
     // kernel timing brackets the whole sequence (sorts included)
@@ -7421,20 +7307,8 @@ static int launch_segmented(uam_ctx* ctx, const KRaster& kr, const void* rec, co
         const int64_t base = (int64_t)k * P;
         if (k == 1) HIP_TRY(hipStreamWaitEvent(s, ctx->ev_join, 0));
         const dim3 ge((unsigned)((P + 255) / 256));
-#define UAM_LAUNCH_SEG(SK_, F_, LDS_, PK_)                                                     \
-    hipLaunchKernelGGL((k_seg_eval<SK_, F_, PK_>), ge, dim3(256), LDS_, s, ctx->kp, kr, ks,    \
-                       (const uint4*)rec, k, base, (int32_t)P)
-        if (kr.pmap) {
-            if (k == 0) UAM_LAUNCH_SEG(false, true, lds0, true);
-            else UAM_LAUNCH_SEG(false, false, lds, true);
-        } else if (k == 0) {
-            if (kr.sum) UAM_LAUNCH_SEG(true, true, lds0, false);
-            else UAM_LAUNCH_SEG(false, true, lds0, false);
-        } else {
-            if (kr.sum) UAM_LAUNCH_SEG(true, false, lds, false);
-            else UAM_LAUNCH_SEG(false, false, lds, false);
-        }
-#undef UAM_LAUNCH_SEG
+        hipLaunchKernelGGL(k == 0 ? ev0 : ev, ge, dim3(256), k == 0 ? lds0 : lds, s, ctx->kp, kr,
+                           ks, (const uint4*)rec, k, base, (int32_t)P);
     }
     const dim3 gf((unsigned)((n_pairs + 63) / 64));
     const size_t lf = (size_t)2 * 64 * D * sizeof(double);
@@ -7702,9 +7576,9 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
         const int floor_lds = ctx->k2g_lds ? ctx->k2g_lds : big ? 54000 : 0;
         pl->lds = std::max(need, (size_t)std::min(floor_lds, 160 * 1024));
         if (pl->lds > 160 * 1024) return no("the packed header and arc rows exceed the LDS");
-        static const HEvalFn hist[1] = {k_g_hist};
-        st = raise_lds(&ctx->k2h_attrs, 160 * 1024, hevals, hevalsx);
-        if (!st) st = raise_lds(&ctx->k2h_hist_attr, G_HIST_DYN_MAX, hist);
+        // (raised at every size: harmless below 64 KiB)
+        st = exact ? raise_lds(ctx, pl->hevx, 160 * 1024) : raise_lds(ctx, pl->hev, 160 * 1024);
+        if (!st) st = raise_lds(ctx, k_g_hist, G_HIST_DYN_MAX);
         if (st) return st;
     } else {  // K2g: 256-item workgroups, the code map in LDS
 #define UAM_G_EVALS(CH) k_g_eval<CH, false, false>, k_g_eval<CH, false, true>, \
@@ -7719,7 +7593,7 @@ static int grouped_plan(uam_ctx* ctx, const KRaster& kr, const double* pairs, in
         const size_t need = (size_t)((kr.pwords + 3) & ~3) * 4 + ubytes + 16;
         pl->lds = std::max(need, (size_t)std::min(ctx->k2g_lds, 160 * 1024));
         if (pl->lds > 64 * 1024) {
-            st = raise_lds(&ctx->k2g_attrs, 160 * 1024, evals);
+            st = raise_lds(ctx, pl->ev, 160 * 1024);
             if (st) return st;
         }
     }
@@ -7840,11 +7714,7 @@ static void profile_final(uam_ctx* ctx, const GPlan& pl, const KVert* vert, cons
     else
         hipLaunchKernelGGL(k_vp_final, gfin, dim3(256), 0, s, ctx->kp, kg, kf, ko);
     if (best_f || best_l) {
-        const dim3 g2(grid_for(n_pairs, 256, INT32_MAX));
-        if (best_f)
-            hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.cost, n_pairs, C, 1, best_f);
-        if (best_l)
-            hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.length, n_pairs, C, 0, best_l);
+        launch_argmin(ko, n_pairs, C, best_f, best_l, s);
         hipLaunchKernelGGL(k_vp_sel_check, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0,
                            s, kg.err, n_pairs, best_f, best_l);
     }
@@ -8008,9 +7878,8 @@ static int grouped_plan3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6, i
                    (ctx->k4h_te ? 5 : 0);
     if (ztab) pl->pev = exact ? pevalsx[vi] : pevals[vi];
     else pl->vev = exact ? vevalsx[vi] : vevals[vi];
-    if (pl->lds > 64 * 1024) {  // (the two forms' instances are distinct functions)
-        st = ztab ? raise_lds(&ctx->k4hp_attrs, 160 * 1024, pevals, pevalsx)
-                  : raise_lds(&ctx->k4h_attrs, 160 * 1024, vevals, vevalsx);
+    if (pl->lds > 64 * 1024) {
+        st = ztab ? raise_lds(ctx, pl->pev, 160 * 1024) : raise_lds(ctx, pl->vev, 160 * 1024);
         if (st) return st;
     }
     pl->fin = k_v_final;
@@ -8050,10 +7919,8 @@ static int launch_grouped3d(uam_ctx* ctx, const KVol4& kv, const double* pairs6,
     st = ktime_begin(ctx, s);
     if (st) return st;
     if (pl.kg.seed_lds) {
-        static const VEvalFn hist[1] = {k_v_hist};
-        static const VPEvalFn phist[1] = {k_vp_hist};
-        st = ztab ? raise_lds(&ctx->k4hp_hist_attr, G_HIST_DYN_MAX, phist)
-                  : raise_lds(&ctx->k4h_hist_attr, G_HIST_DYN_MAX, hist);
+        st = ztab ? raise_lds(ctx, k_vp_hist, G_HIST_DYN_MAX)
+                  : raise_lds(ctx, k_v_hist, G_HIST_DYN_MAX);
         if (st) return st;
     }
     const VGrid vg{kv, pl.kf};
@@ -8206,8 +8073,7 @@ static int eval_generated(uam_ctx* ctx, int32_t mode, const uam_raster_desc* des
                           const double* pairs, int64_t n_pairs, const double* utab, int32_t D,
                           const uam_path_outputs* out, uam_stream stream,
                           const void* packed = nullptr) {
-    int st = check_ctx(ctx, true);
-    if (st) return st;
+    int st;  // (the context: checked by the caller's eval_prologue)
     if (n_pairs < 0 || D < 1) return fail(UAM_E_INVALID, "n_pairs < 0 or D < 1");
     if (n_pairs == 0) return UAM_OK;
     if (!pairs || !utab) return fail(UAM_E_INVALID, "pairs/utab is NULL");
@@ -8219,8 +8085,8 @@ static int eval_generated(uam_ctx* ctx, int32_t mode, const uam_raster_desc* des
         return fail(UAM_E_INVALID, "unknown mode %d", mode);
     }
     const KOut ko = make_kout(out);
-    int32_t* best_f = out ? out->best_fval_idx : nullptr;
-    int32_t* best_l = out ? out->best_length_idx : nullptr;
+    int32_t *best_f, *best_l;
+    (void)selections(out, nullptr, &best_f, &best_l);
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     ctx->last_group = 0;  // sequential sums unless K2g runs
@@ -8274,9 +8140,7 @@ static int eval_generated(uam_ctx* ctx, int32_t mode, const uam_raster_desc* des
         if (best_f || best_l) {  // selection needs the costs/lengths even if not requested
             if ((best_f && !ko.cost) || (best_l && !ko.length))
                 return fail(UAM_E_INVALID, "best_*_idx needs cost/length outputs (D > 16)");
-            const dim3 g2(grid_for(n_pairs, 256, INT32_MAX));
-            if (best_f) hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.cost, n_pairs, D, 1, best_f);
-            if (best_l) hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.length, n_pairs, D, 0, best_l);
+            launch_argmin(ko, n_pairs, D, best_f, best_l, s);
             HIP_TRY(hipGetLastError());
         }
         return UAM_OK;
@@ -8305,37 +8169,19 @@ static int eval_generated(uam_ctx* ctx, int32_t mode, const uam_raster_desc* des
         while (S > 2 && k3b_lds_bytes(D, S) > 160 * 1024) S = S == 6 ? 4 : S / 2;
         const int CPL = ctx->k3b_cpl >= 2 ? 2 : 1;
         const size_t l3 = k3b_lds_bytes(D, S);
-        {
-            const void* fns[] = {(const void*)k_eval_pairs_k3b<2, 1>,
-                                 (const void*)k_eval_pairs_k3b<4, 1>,
-                                 (const void*)k_eval_pairs_k3b<8, 1>,
-                                 (const void*)k_eval_pairs_k3b<16, 1>,
-                                 (const void*)k_eval_pairs_k3b<6, 1>,
-                                 (const void*)k_eval_pairs_k3b<6, 2>,
-                                 (const void*)k_eval_pairs_k3b<2, 2>,
-                                 (const void*)k_eval_pairs_k3b<4, 2>,
-                                 (const void*)k_eval_pairs_k3b<8, 2>,
-                                 (const void*)k_eval_pairs_k3b<16, 2>};
-            st = raise_lds(&ctx->k3b_attrs, 160 * 1024, fns);
-            if (st) return st;
-        }
-#define UAM_LAUNCH_K3B(S_, C_)                                                                 \
-    hipLaunchKernelGGL((k_eval_pairs_k3b<S_, C_>), grid, block, l3, s, ctx->kg, ctx->kp, pairs,   \
-                       n_pairs, utab, D, ko, best_f, best_l, order)
+        // K3b's instances by (S, CPL), S in {2, 4, 6, 8, 16}
+        using K3bFn = void (*)(KGeom, KParams, const double*, int64_t, const double*, int, KOut,
+                               int32_t*, int32_t*, const int32_t*);
+#define UAM_K3B(S_) {k_eval_pairs_k3b<S_, 1>, k_eval_pairs_k3b<S_, 2>}
+        static const K3bFn k3b[5][2] = {UAM_K3B(2), UAM_K3B(4), UAM_K3B(6), UAM_K3B(8),
+                                        UAM_K3B(16)};
+#undef UAM_K3B
+        const K3bFn fn = k3b[S == 2 ? 0 : S == 4 ? 1 : S == 6 ? 2 : S == 8 ? 3 : 4][CPL - 1];
+        st = raise_lds(ctx, fn, 160 * 1024);  // (at every size: harmless below 64 KiB)
+        if (st) return st;
         ctx->last_kernel = "K3b";
-        switch (S * 4 + CPL) {
-            case 16 * 4 + 2: UAM_LAUNCH_K3B(16, 2); break;
-            case 8 * 4 + 2: UAM_LAUNCH_K3B(8, 2); break;
-            case 6 * 4 + 2: UAM_LAUNCH_K3B(6, 2); break;
-            case 6 * 4 + 1: UAM_LAUNCH_K3B(6, 1); break;
-            case 4 * 4 + 2: UAM_LAUNCH_K3B(4, 2); break;
-            case 2 * 4 + 2: UAM_LAUNCH_K3B(2, 2); break;
-            case 16 * 4 + 1: UAM_LAUNCH_K3B(16, 1); break;
-            case 8 * 4 + 1: UAM_LAUNCH_K3B(8, 1); break;
-            case 4 * 4 + 1: UAM_LAUNCH_K3B(4, 1); break;
-            default: UAM_LAUNCH_K3B(2, 1); break;
-        }
-#undef UAM_LAUNCH_K3B
+        hipLaunchKernelGGL(fn, grid, block, l3, s, ctx->kg, ctx->kp, pairs, n_pairs, utab, D, ko,
+                           best_f, best_l, order);
     } else if (mode == UAM_MODE_ANALYTIC) {
         ctx->last_kernel = "K3";
         UAM_LAUNCH_PAIRS(UAM_MODE_ANALYTIC, 1);
@@ -8361,10 +8207,8 @@ int uam_eval_generated(uam_ctx* ctx, int32_t mode, const uam_raster_desc* desc,
                        const void* packed, const double* pairs, int64_t n_pairs,
                        const double* utab, int32_t D, const uam_path_outputs* out,
                        uam_stream stream) {
-    if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
-        const int st = device_status(ctx);
-        if (st) return st;
-    }
+    const int st = eval_prologue(ctx);
+    if (st) return st;
     return eval_generated(ctx, mode, desc, rec, summary, block, pairs, n_pairs, utab, D, out,
                           stream, packed);
 }
@@ -8760,6 +8604,18 @@ static void packed_view(const uam_ctx* ctx, const uam_volume_desc* vd, const voi
     k4->nbands = ((vd->nz - 1) >> zs) + 1;
 }
 
+// vol_dev's sections as the kernels read them; the checks every call on vol_dev makes, in this
+// order
+static int volume_view(const uam_volume_desc* vd, const void* vol, KVolume* kv) {
+    if (!vol) return fail(UAM_E_INVALID, "pointer is NULL");
+    if ((uintptr_t)vol & 255) return fail(UAM_E_INVALID, "volume buffer not 256-B aligned");
+    kv->vox = (const uint2*)vol;
+    kv->col = (const uint2*)((const char*)vol + vol_col_offset(vd));
+    kv->cbits = (const uint32_t*)((const char*)vol + vol_bits_offset(vd));
+    vol_bits_dims(vd, kv);
+    return UAM_OK;
+}
+
 // The failures, in the order a caller sees them: an earlier call's device check; the context
 // (NULL, no geometry, no params); the exact form without packed_dev; n_pairs / D (n_pairs == 0
 // then returns UAM_OK); the volume descriptor; pairs6 / utab NULL; with packed_dev its
@@ -8769,11 +8625,7 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
                          const void* packed, const double* pairs6, int64_t n_pairs,
                          const double* utab, int32_t D, const uam_path_outputs* out,
                          uam_stream stream) {
-    if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
-        const int st = device_status(ctx);
-        if (st) return st;
-    }
-    int st = check_ctx(ctx, true);
+    int st = eval_prologue(ctx);
     if (st) return st;
     // UAM_OPT_EXACT_SUM_VOLUME: K4h's exact form at every batch size or an error (no K4 / K4w,
     // whose ordered sums would make the bits depend on the batch size)
@@ -8788,8 +8640,8 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
     if (st) return st;
     if (!pairs6 || !utab) return fail(UAM_E_INVALID, "pointer is NULL");
     const KOut ko = make_kout(out);
-    int32_t* best_f = out ? out->best_fval_idx : nullptr;
-    int32_t* best_l = out ? out->best_length_idx : nullptr;
+    int32_t *best_f, *best_l;
+    (void)selections(out, nullptr, &best_f, &best_l);
     DeviceGuard dg(ctx->device);
     if (packed) {
         if ((uintptr_t)packed & 255) return fail(UAM_E_INVALID, "packed volume not 256-B aligned");
@@ -8804,12 +8656,8 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
                 return fail(UAM_E_INVALID, "UAM_OPT_EXACT_SUM_VOLUME: the batch did not run K4h");
         }
     }
-    if (!vol) return fail(UAM_E_INVALID, "pointer is NULL");
-    if ((uintptr_t)vol & 255) return fail(UAM_E_INVALID, "volume buffer not 256-B aligned");
-    kv.vox = (const uint2*)vol;
-    kv.col = (const uint2*)((const char*)vol + vol_col_offset(vd));
-    kv.cbits = (const uint32_t*)((const char*)vol + vol_bits_offset(vd));
-    vol_bits_dims(vd, &kv);
+    st = volume_view(vd, vol, &kv);
+    if (st) return st;
     const KRaster kr{};
     ctx->last_kernel = "K4";
     ctx->last_group = 0;
@@ -8827,10 +8675,7 @@ int uam_eval_generated3d(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
     // the raster pair order over the volume's x/y extent (results do not depend on it)
     const int32_t* order = nullptr;
     if (ctx->pair_order && n_pairs >= 4096 && n_pairs < INT32_MAX) {
-        KRaster kxy{};
-        kxy.nx = kv.nx, kxy.ny = kv.ny, kxy.x0 = kv.x0, kxy.y_top = kv.y_top;
-        kxy.dx = vd->dx, kxy.dy = vd->dy;
-        st = raster_pair_order(ctx, kxy, pairs6, n_pairs, (hipStream_t)stream, &order, 1);
+        st = volume_pair_order(ctx, kv, vd, pairs6, n_pairs, (hipStream_t)stream, &order);
         if (st) return st;
     }
     st = ktime_begin(ctx, (hipStream_t)stream);
@@ -8853,17 +8698,6 @@ static int no_exact_volume(const uam_ctx* ctx, const char* call) {
     if (!ctx->exact_sum_vol) return UAM_OK;
     return fail(UAM_E_INVALID,
                 "UAM_OPT_EXACT_SUM_VOLUME: %s forms ordered sums and has no exact form", call);
-}
-
-// vol_dev's sections as the kernels read them (uam_eval_generated3d's checks, in its order)
-static int volume_view(const uam_volume_desc* vd, const void* vol, KVolume* kv) {
-    if (!vol) return fail(UAM_E_INVALID, "pointer is NULL");
-    if ((uintptr_t)vol & 255) return fail(UAM_E_INVALID, "volume buffer not 256-B aligned");
-    kv->vox = (const uint2*)vol;
-    kv->col = (const uint2*)((const char*)vol + vol_col_offset(vd));
-    kv->cbits = (const uint32_t*)((const char*)vol + vol_bits_offset(vd));
-    vol_bits_dims(vd, kv);
-    return UAM_OK;
 }
 
 static int profile_dims(int64_t n_pairs, int32_t D, const double* ztab, int32_t A) {
@@ -8916,11 +8750,7 @@ static int eval_waypoints3d(uam_ctx* ctx, const uam_volume_desc* vd, const void*
                             const double* wp3, int64_t n_paths, const uam_vertical* vert,
                             bool with_vert, const uam_path_outputs* out, double* climb,
                             uam_stream stream) {
-    if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
-        const int st = device_status(ctx);
-        if (st) return st;
-    }
-    int st = check_ctx(ctx, true);
+    int st = eval_prologue(ctx);
     if (st) return st;
     st = no_exact_volume(ctx, with_vert ? "uam_eval_waypoints3d_v" : "uam_eval_waypoints3d");
     if (st) return st;
@@ -8998,11 +8828,7 @@ static int eval_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
                          const double* pairs6, int64_t n_pairs, const double* utab, int32_t D,
                          const double* ztab, int32_t A, const uam_vertical* vert, bool with_vert,
                          const uam_path_outputs* out, double* climb, uam_stream stream) {
-    if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
-        const int st = device_status(ctx);
-        if (st) return st;
-    }
-    int st = check_ctx(ctx, true);
+    int st = eval_prologue(ctx);
     if (st) return st;
     st = no_exact_volume(ctx, with_vert ? "uam_eval_generated3d_profiles_v"
                                         : "uam_eval_generated3d_profiles");
@@ -9020,11 +8846,10 @@ static int eval_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
     if (st) return st;
     if (!pairs6 || !utab) return fail(UAM_E_INVALID, "pointer is NULL");
     const KOut ko = make_kout(out);
-    int32_t* best_f = out ? out->best_fval_idx : nullptr;
-    int32_t* best_l = out ? out->best_length_idx : nullptr;
-    if ((best_f && !ko.cost) || (best_l && !ko.length))
-        return fail(UAM_E_INVALID,
-                    "best_fval_idx needs the cost output, best_length_idx the length output");
+    int32_t *best_f, *best_l;
+    st = selections(out, "best_fval_idx needs the cost output, best_length_idx the length output",
+                    &best_f, &best_l);
+    if (st) return st;
     st = volume_view(vd, vol, &kv);
     if (st) return st;
     DeviceGuard dg(ctx->device);
@@ -9037,10 +8862,7 @@ static int eval_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
     // K4's pair order over the volume's x/y extent (results do not depend on it)
     const int32_t* order = nullptr;
     if (ctx->pair_order && n_pairs >= 4096 && n_pairs < INT32_MAX) {
-        KRaster kxy{};
-        kxy.nx = kv.nx, kxy.ny = kv.ny, kxy.x0 = kv.x0, kxy.y_top = kv.y_top;
-        kxy.dx = vd->dx, kxy.dy = vd->dy;
-        st = raster_pair_order(ctx, kxy, pairs6, n_pairs, s, &order, 1);
+        st = volume_pair_order(ctx, kv, vd, pairs6, n_pairs, s, &order);
         if (st) return st;
     }
     st = ktime_begin(ctx, s);
@@ -9074,11 +8896,7 @@ static int eval_profiles(uam_ctx* ctx, const uam_volume_desc* vd, const void* vo
     }
     // main.py:175-180 over the pair's D * A candidates in index order c = d * A + a (without
     // the vertical terms every profile of a displacement stores the same length)
-    const dim3 g2(grid_for(n_pairs, 256, INT32_MAX));
-    if (best_f)
-        hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.cost, n_pairs, D * A, 1, best_f);
-    if (best_l)
-        hipLaunchKernelGGL(k_argmin, g2, dim3(256), 0, s, ko.length, n_pairs, D * A, 0, best_l);
+    launch_argmin(ko, n_pairs, D * A, best_f, best_l, s);
     HIP_TRY(hipGetLastError());
     return UAM_OK;
 }
@@ -9114,11 +8932,7 @@ static int eval_profiles_h(uam_ctx* ctx, const uam_volume_desc* vd, const void* 
                            const double* utab, int32_t D, const double* ztab, int32_t A,
                            const uam_vertical* vert, bool with_vert, const uam_path_outputs* out,
                            double* climb, uam_stream stream) {
-    if (ctx) {  // an earlier call's failed device check, reported once (uam_device_status)
-        const int st = device_status(ctx);
-        if (st) return st;
-    }
-    int st = check_ctx(ctx, true);
+    int st = eval_prologue(ctx);
     if (st) return st;
     KVert kvert{};
     if (with_vert) {
@@ -9134,11 +8948,10 @@ static int eval_profiles_h(uam_ctx* ctx, const uam_volume_desc* vd, const void* 
     if (st) return st;
     if (!pairs6 || !utab) return fail(UAM_E_INVALID, "pointer is NULL");
     const KOut ko = make_kout(out);
-    int32_t* best_f = out ? out->best_fval_idx : nullptr;
-    int32_t* best_l = out ? out->best_length_idx : nullptr;
-    if ((best_f && !ko.cost) || (best_l && !ko.length))
-        return fail(UAM_E_INVALID,
-                    "best_fval_idx needs the cost output, best_length_idx the length output");
+    int32_t *best_f, *best_l;
+    st = selections(out, "best_fval_idx needs the cost output, best_length_idx the length output",
+                    &best_f, &best_l);
+    if (st) return st;
     if (!packed)
         return fail(UAM_E_INVALID, "%s: no packed_dev",
                     with_vert ? "uam_eval_generated3d_profiles_hv needs K4hpv"
@@ -9239,11 +9052,9 @@ int uam_route_field(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     const int T = ctx->k9_tile, inner = ctx->k9_inner;
-    if (T == 64) {
-        void (*const big[])(const double*, double*, KRoute, int, int, const int32_t*, uint32_t*,
-                            uint32_t*, int32_t*, int32_t*, int, int) = {k_route_relax<64>};
-        if ((st = raise_lds(&ctx->k9_attrs, 2 * 66 * 66 * (int)sizeof(double), big))) return st;
-    }
+    if (T == 64 &&
+        (st = raise_lds(ctx, k_route_relax<64>, 2 * 66 * 66 * (int)sizeof(double))))
+        return st;
     if (!ctx->h_route) HIP_TRY(hipHostMalloc((void**)&ctx->h_route, 64, hipHostMallocDefault));
     char* base = (char*)workspace;
     double* c = (double*)(base + ws.c_off);

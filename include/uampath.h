@@ -576,7 +576,8 @@ int uam_kernel_time(uam_ctx* ctx, double* ms_total, int64_t* launches);
  * "K4e" / "K4ew" (uam_eval_waypoints3d lane / wave per path), "K4p"
  * (uam_eval_generated3d_profiles), "K4e+v" / "K4ew+v" / "K4p+v" (their _v forms with the
  * vertical terms); "K9" (uam_route_field) / "K9t" (uam_route_paths) / "K9b"
- * (uam_route_free_bits) / "K9s" (uam_route_paths_smooth); "" before the first call.
+ * (uam_route_free_bits) / "K9s" (uam_route_paths_smooth); "K9v" (uam_route3d_field) / "K9vt"
+ * (uam_route3d_paths); "" before the first call.
  * The string is static (never freed).  For benchmarks and tests:
  * which kernel a number belongs to. */
 const char* uam_last_kernel(const uam_ctx* ctx);
@@ -688,6 +689,12 @@ enum {
  * round, 1..256 (default 16).  No output depends on either. */
 #define UAM_OPT_K9_TILE 27
 #define UAM_OPT_K9_INNER 28
+/* The volume route seeds' three ("Route seeds in the volume" below): the tile edge in x/y, 8
+ * (default) or 16 voxels, the tile edge in z, 4 (default) or 8 layers, and the sweeps inside a
+ * tile per round, 1..256 (default 64).  No output depends on any of them. */
+#define UAM_OPT_K9V_TILE_XY 29
+#define UAM_OPT_K9V_TILE_Z 30
+#define UAM_OPT_K9V_INNER 31
 int uam_set_option(uam_ctx* ctx, int32_t option, int64_t value);
 int uam_get_option(const uam_ctx* ctx, int32_t option, int64_t* value);
 
@@ -1072,6 +1079,118 @@ int uam_route_paths_smooth_host(const uam_raster_desc* desc, const uint32_t* bit
                                 int32_t* status, int32_t* steps, int32_t* vertices);
 int uam_route_visible_host(const uam_raster_desc* desc, const uint32_t* bits, int64_t n,
                            const int32_t* a_cells, const int32_t* b_cells, uint8_t* out_u8);
+
+/* ---- Route seeds in the volume (K9v): 3-D cost-to-go field and traced 3-D routes --------------
+ * The route seeds above are flat: they know neither the terrain nor the altitude layers.  These
+ * calls are their counterpart over the risk volume's voxels: the cheapest 26-connected route
+ * from any 3-D start to a goal, resampled to the [N+2][3] waypoints uam_eval_waypoints3d and
+ * uam_eval_waypoints3d_v take.  uam_route3d_field is a per-goal SETUP call like uam_route_field
+ * (it synchronises the stream between rounds), uam_route3d_paths is asynchronous.
+ *
+ * Definition (normative; independent statement: tests/route3d_ref.py).  Every float64 operation
+ * is rounded separately, in the order written (no fused multiply-add).
+ *   voxels     a point maps to a voxel by uam_volume_desc's rule in x, y and z; the centre of
+ *              voxel (ix, iy, iz) is (x0 + (ix + 0.5)*dx, y_top - (iy + 0.5)*dy,
+ *              z0 + (iz + 0.5)*dz); its index is (iy*nx + ix)*nz + iz (the cells convention of
+ *              uam_eval_waypoints3d).  Field outputs are laid out [n_goals][ny][nx][nz].
+ *   directions k = 0..25 as (dix, diy, diz): k = 0..7 the route seeds' (dix, diy) table with
+ *              diz = 0, k = 8..15 the same table with diz = +1, k = 16..23 with diz = -1,
+ *              k = 24 (0, 0, +1), k = 25 (0, 0, -1).
+ *   step       hx = dix ? dx : 0, hy = diy ? dy : 0, hz = diz ? (dz * kappa) : 0 (the product
+ *              formed once), L_k = sqrt((hx*hx + hy*hy) + hz*hz).  kappa = z_scale is
+ *              uam_vertical's unit, km of path length per metre of altitude change: the field's
+ *              metric is the one the _v evaluations charge.  kappa is finite and > 0 (a zero
+ *              vertical weight would give zero-weight edges and next-hop cycles).
+ *   voxel cost c_v = 1.0 + lambda * (double)risk_v (the voxel's float32 risk).  A voxel is
+ *              blocked0 when (the column's flags & block_flags) != 0, or c_v is not finite, or
+ *              c_v is not > 0, or z0 + ((double)iz + 0.5)*dz < (double)terrain + agl (the
+ *              column plane's float32 terrain; agl finite and >= 0, metres; with agl = 0 this
+ *              is uam_eval_waypoints3d's below_terrain test).  A voxel is blocked when a
+ *              blocked0 voxel of the same layer lies within Chebyshev distance inflate of it in
+ *              x/y (voxels outside the volume do not count).  Otherwise it is free.
+ *   edges      between voxels u, v that differ by a direction, when every voxel of the
+ *              axis-aligned box the two span (2, 4 or 8 voxels) is free: the route seeds'
+ *              corner rule generalised, so every point of a step's segment lies in a free voxel
+ *              and a one-voxel-thick diagonal sheet is a wall.  w(u,v) = (0.5 * (c_u + c_v)) *
+ *              L_k, symmetric.
+ *   field, next hop, path status, steps
+ *              the route seeds' text with "cell" read as "voxel": dist is the left-fold minimum,
+ *              the one fixed point of d[v] = min(d[v], fl(d[u] + w(u,v))); next is uint8, the
+ *              lowest k whose neighbour attains dist[v], 26 at the goal voxel, 255 where dist is
+ *              +inf; status 4 / 1 / 2 / 3 / 0 tested in that order (4 bad goal index or goal
+ *              outside the volume or blocked, 1 start outside the volume or blocked, 2
+ *              unreachable, 3 the walk visited nx*ny*nz voxels without reaching the goal, 0 ok);
+ *              steps = the voxels the walk visited, s and g included, 0 for a nonzero status.
+ *   vertices   V_0 = the start point (x, y, z) itself, then the centres of the visited voxels
+ *              strictly between s and g, V_m = the goal point itself.  S_0 = 0, S_i = S_{i-1} +
+ *              sqrt((ex*ex + ey*ey) + ez*ez) with (ex, ey) = the x/y differences of V_i and
+ *              V_{i-1} and ez = (z_i - z_{i-1}) * kappa (the difference first, then one product,
+ *              as in uam_vertical).  The choice of segment, the parameter u and the
+ *              interpolation are the route seeds', applied to all three components; a nonzero
+ *              status gives the straight line in all three components with the end points
+ *              copied (a goal index out of range: every waypoint is the start point).
+ *   bridge     nz = 1, a volume built from a raster with layer_w = 1, the layer centre above
+ *              every terrain value, agl = 0: dist equals uam_route_field's bit for bit
+ *              (sqrt(dx*dx) = dx unless the square overflows or underflows), and next agrees
+ *              wherever uam_route_field's value is < 8.
+ *
+ * uam_route3d_params: lambda, block_flags, inflate and max_rounds as uam_route_params' (max_rounds
+ * 0 = nx*ny*nz); agl finite and >= 0; z_scale finite and > 0.
+ * uam_route3d_field: vol_dev is the volume buffer of uam_volume_shape / uam_volume_build (8-B
+ * voxels {float risk, float psi_nfz} [ny][nx][nz], then at col_offset the 8-B columns {float
+ * terrain, uint32 flags} [ny][nx]; 256-B aligned; the column bitmap behind them is not read, so
+ * a test may fill the buffer by hand); goals_dev [n_goals][3]; dist_dev [n_goals][ny][nx][nz]
+ * f64 and next_dev likewise u8; workspace_dev holds uam_route3d_workspace_bytes(desc, params)
+ * bytes, 256-B aligned (the cost plane and the 26-bit admissible-direction masks, shared by the
+ * goals, and the active-tile sets).  Rounds as uam_route_field: one ordinary launch per round
+ * over the active tiles, the host reading one word after each.  rounds_out (host, may be NULL):
+ * the rounds of all goals together; uam_route3d_visits: the tiles those rounds visited.
+ * uam_last_kernel: "K9v".  Failures: UAM_E_INVALID before any launch or allocation for ctx / desc
+ * / params / a buffer NULL, a bad descriptor, lambda NaN, infinite or negative, inflate outside
+ * [0, 8], max_rounds < 0, agl NaN, negative or infinite, z_scale not finite or not > 0, n_goals
+ * < 1 or n_goals * nx * ny * nz >= 2^40, a workspace too small, a misaligned buffer;
+ * UAM_E_VERSION for a wrong abi_version; UAM_E_STATE, the message naming max_rounds, when a field
+ * has not converged -- the outputs are then unspecified and the context stays usable.
+ * uam_route3d_paths: Q queries (starts_dev [Q][3], goal_idx_dev [Q]) against next_dev as
+ * uam_route3d_field wrote it for the same desc, vol_dev, params (the start's blocking is derived
+ * again from vol_dev and params) and goals_dev, into wp3_dev [Q][N+2][3], status_dev [Q] and
+ * steps_dev [Q] (or NULL); N from uam_set_params (UAM_E_STATE without it).  One lane per query,
+ * two sequential walks.  uam_last_kernel: "K9vt".
+ * The _host calls take host pointers and run, without a GPU, the same inline functions as the
+ * kernels (the field's minimum by a heap Dijkstra).
+ * UAM_OPT_K9V_TILE_XY (8 (default), 16), UAM_OPT_K9V_TILE_Z (4 (default), 8) and
+ * UAM_OPT_K9V_INNER (1..256, default 64) choose
+ * the tile and the sweeps inside a tile per round; no output depends on them (rounds and visits
+ * do). */
+typedef struct {
+    uint32_t abi_version; /* UAM_ABI_VERSION */
+    double lambda;        /* weight of the risk in the voxel cost; finite, >= 0 */
+    uint32_t block_flags; /* UAM_FLAG_* bits of the column that block its voxels */
+    int32_t inflate;      /* voxels of x/y clearance around a blocked0 voxel, 0..8 */
+    int32_t max_rounds;   /* 0 = nx*ny*nz */
+    double agl;           /* metres a layer centre must lie above the terrain; finite, >= 0 */
+    double z_scale;       /* kappa, km of path length per metre of altitude; finite, > 0 */
+} uam_route3d_params;
+int64_t uam_route3d_workspace_bytes(const uam_volume_desc* desc,
+                                    const uam_route3d_params* params);
+int uam_route3d_field(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol_dev,
+                      const uam_route3d_params* params, const double* goals_dev, int32_t n_goals,
+                      double* dist_dev, uint8_t* next_dev, void* workspace_dev,
+                      int64_t workspace_bytes, int32_t* rounds_out, uam_stream stream);
+int64_t uam_route3d_visits(const uam_ctx* ctx);
+int uam_route3d_paths(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol_dev,
+                      const uam_route3d_params* params, const uint8_t* next_dev,
+                      const double* goals_dev, int32_t n_goals, const double* starts_dev,
+                      const int32_t* goal_idx_dev, int64_t n_queries, double* wp3_dev,
+                      int32_t* status_dev, int32_t* steps_dev, uam_stream stream);
+int uam_route3d_field_host(const uam_volume_desc* desc, const void* vol,
+                           const uam_route3d_params* params, const double* goals,
+                           int32_t n_goals, double* dist, uint8_t* next);
+int uam_route3d_paths_host(const uam_volume_desc* desc, const void* vol,
+                           const uam_route3d_params* params, const uint8_t* next,
+                           const double* goals, int32_t n_goals, const double* starts,
+                           const int32_t* goal_idx, int64_t n_queries, int32_t N, double* wp3,
+                           int32_t* status, int32_t* steps);
 
 /* Workspace bytes uam_refine needs for n_paths (after uam_set_geometry/uam_set_params). */
 int64_t uam_refine_workspace_bytes(uam_ctx* ctx, int64_t n_paths,

@@ -28,6 +28,8 @@ OPTIONS = {"group": 1, "sorted_min_paths": 2, "k2s_segments": 3, "wave_max_paths
            "test_sort_fault": 22, "exact_sum": 23, "exact_sum_volume": 24}
 # the route seeds' options (K9; UAM_OPT_K9_TILE / UAM_OPT_K9_INNER), which no output depends on
 ROUTE_OPTIONS = {"k9_tile": 27, "k9_inner": 28}
+# the volume route seeds' options (K9v; UAM_OPT_K9V_*), which no output depends on either
+ROUTE3D_OPTIONS = {"k9v_tile_xy": 29, "k9v_tile_z": 30, "k9v_inner": 31}
 # uam_route_paths_smooth: the largest span, and the anchors K9s keeps for its resampling pass
 ROUTE_SPAN_MAX, ROUTE_SMOOTH_LIST = 1024, 256
 INEQ_HALFPLANE, INEQ_ELLIPSE, INEQ_AXIS = 0, 1, 2
@@ -88,6 +90,15 @@ class RouteParams(ctypes.Structure):
     _fields_ = [("abi_version", ctypes.c_uint32), ("lam", ctypes.c_double),
                 ("block_flags", ctypes.c_uint32), ("inflate", ctypes.c_int32),
                 ("max_rounds", ctypes.c_int32)]
+
+
+class Route3dParams(ctypes.Structure):
+    """uam_route3d_params: the voxel cost, blocking, round bound, clearance above the terrain
+    and vertical unit of the route seeds in the volume (K9v)."""
+    _fields_ = [("abi_version", ctypes.c_uint32), ("lam", ctypes.c_double),
+                ("block_flags", ctypes.c_uint32), ("inflate", ctypes.c_int32),
+                ("max_rounds", ctypes.c_int32), ("agl", ctypes.c_double),
+                ("z_scale", ctypes.c_double)]
 
 
 class RefineParams(ctypes.Structure):
@@ -249,6 +260,22 @@ SIGNATURES = {
                                                    _vp]),
     "uam_route_visible_host": (ctypes.c_int, [ctypes.POINTER(RasterDesc), _vp, ctypes.c_int64,
                                               _vp, _vp, _vp]),
+    "uam_route3d_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(VolumeDesc),
+                                                     ctypes.POINTER(Route3dParams)]),
+    "uam_route3d_field": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp,
+                                         ctypes.POINTER(Route3dParams), _vp, ctypes.c_int32, _vp,
+                                         _vp, _vp, ctypes.c_int64, _i32p, _vp]),
+    "uam_route3d_visits": (ctypes.c_int64, [_vp]),
+    "uam_route3d_paths": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp,
+                                         ctypes.POINTER(Route3dParams), _vp, _vp, ctypes.c_int32,
+                                         _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "uam_route3d_field_host": (ctypes.c_int, [ctypes.POINTER(VolumeDesc), _vp,
+                                              ctypes.POINTER(Route3dParams), _vp, ctypes.c_int32,
+                                              _vp, _vp]),
+    "uam_route3d_paths_host": (ctypes.c_int, [ctypes.POINTER(VolumeDesc), _vp,
+                                              ctypes.POINTER(Route3dParams), _vp, _vp,
+                                              ctypes.c_int32, _vp, _vp, ctypes.c_int64,
+                                              ctypes.c_int32, _vp, _vp, _vp]),
     "uam_refine_workspace_bytes": (ctypes.c_int64, [_vp, ctypes.c_int64,
                                                     ctypes.POINTER(RefineParams)]),
     "uam_refine": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.POINTER(RefineParams), _vp,

@@ -6144,6 +6144,9 @@ __global__ __launch_bounds__(1024) void k_g_final(KParams p, KGrp kg, KOut out,
 #include "k9_route.inc"
 // K9b / K9s: any-angle shortcuts on the traced route, k_route_free_bits, k_route_smooth
 #include "k9_smooth.inc"
+// K9v: route seeds in the volume, k_route3_cost, k_route3_mask, k_route3_init, k_route3_relax,
+// k_route3_next, k_route3_trace
+#include "k9v_route.inc"
 
 // closes the anonymous namespace opened above the device-side tables
 }  // namespace
@@ -6249,6 +6252,13 @@ struct uam_ctx {
                                 // 16 65 / 40, 32 69 / 42, 64 76 / 48)
     int32_t* h_route = nullptr; // page-locked words the active-tile counts are copied to
     int64_t route_visits = 0;   // uam_route_visits: tiles the last uam_route_field visited
+    int k9v_tile_xy = 8;        // K9v tile edge in x/y (UAM_OPT_K9V_TILE_XY: 8, 16)
+    int k9v_tile_z = 4;         // K9v tile edge in z (UAM_OPT_K9V_TILE_Z: 4, 8)
+    int k9v_inner = 64;         // K9v sweeps inside a tile per round (UAM_OPT_K9V_INNER: 1..256;
+                                // cfg5 1024^2 x 64 at tile 8 x 8 x 4, centre / corner goal:
+                                // 4 115 / 65 ms, 16 109 / 47, 64 105 / 49; at 16 x 16 x 8
+                                // 252-296 / 124-173)
+    int64_t route3d_visits = 0; // uam_route3d_visits: tiles the last uam_route3d_field visited
 
 };
 
@@ -7056,6 +7066,12 @@ static const OptDef kOptions[] = {
      "UAM_OPT_K9_TILE %lld not 16, 32 or 64"},
     {UAM_OPT_K9_INNER, UAM_OPT_MEMBER(k9_inner), [](int64_t v) { return v >= 1 && v <= 256; },
      "UAM_OPT_K9_INNER %lld outside [1, 256]"},
+    {UAM_OPT_K9V_TILE_XY, UAM_OPT_MEMBER(k9v_tile_xy),
+     [](int64_t v) { return v == 8 || v == 16; }, "UAM_OPT_K9V_TILE_XY %lld not 8 or 16"},
+    {UAM_OPT_K9V_TILE_Z, UAM_OPT_MEMBER(k9v_tile_z), [](int64_t v) { return v == 4 || v == 8; },
+     "UAM_OPT_K9V_TILE_Z %lld not 4 or 8"},
+    {UAM_OPT_K9V_INNER, UAM_OPT_MEMBER(k9v_inner), [](int64_t v) { return v >= 1 && v <= 256; },
+     "UAM_OPT_K9V_INNER %lld outside [1, 256]"},
 };
 #undef UAM_OPT_MEMBER
 
@@ -9165,6 +9181,206 @@ int uam_route_paths_host(const uam_raster_desc* desc, const void* rec,
     for (int64_t q = 0; q < n_queries; ++q)
         r9_trace(g, (const uint4*)rec, next, goals, n_goals, starts, goal_idx, q, N, wp, status,
                  steps);
+    return UAM_OK;
+}
+
+// ---- K9v: route seeds in the volume (k9v_route.inc) --------------------------------------------
+// the descriptor and the parameters checked and folded into the kernels' KRoute3
+static int route3d_setup(const uam_volume_desc* desc, const uam_route3d_params* p, KRoute3* g) {
+    if (!p) return fail(UAM_E_INVALID, "route3d params is NULL");
+    if (p->abi_version != UAM_ABI_VERSION)
+        return fail(UAM_E_VERSION, "route3d params abi_version %u != %d", p->abi_version,
+                    UAM_ABI_VERSION);
+    KVolume kv;
+    const int st = make_kvolume(desc, &kv);
+    if (st) return st;
+    if (!(p->lambda >= 0.0) || !(p->lambda < r9_inf()))
+        return fail(UAM_E_INVALID, "route3d lambda must be finite and >= 0");
+    if (p->inflate < 0 || p->inflate > R9_INFLATE_MAX)
+        return fail(UAM_E_INVALID, "route3d inflate %d outside [0, %d]", p->inflate,
+                    R9_INFLATE_MAX);
+    if (p->max_rounds < 0)
+        return fail(UAM_E_INVALID, "route3d max_rounds %d < 0", p->max_rounds);
+    if (!(p->agl >= 0.0) || !(p->agl < r9_inf()))
+        return fail(UAM_E_INVALID, "route3d agl must be finite and >= 0");
+    if (!(p->z_scale > 0.0) || !(p->z_scale < r9_inf()))
+        return fail(UAM_E_INVALID, "route3d z_scale must be finite and > 0");
+    g->nx = kv.nx, g->ny = kv.ny, g->nz = kv.nz;
+    g->x0 = kv.x0, g->y_top = kv.y_top, g->dx = desc->dx, g->dy = desc->dy;
+    g->inv_dx = kv.inv_dx, g->inv_dy = kv.inv_dy;
+    g->z0 = kv.z0, g->dz = kv.dz, g->inv_dz = kv.inv_dz;
+    g->lambda = p->lambda, g->agl = p->agl, g->kappa = p->z_scale;
+    g->block_flags = p->block_flags;
+    g->inflate = p->inflate;
+    r9v_set_lengths(g);
+    return UAM_OK;
+}
+
+static int route3d_goals_ok(const KRoute3& g, int32_t n_goals) {
+    if (n_goals < 1) return fail(UAM_E_INVALID, "route3d n_goals %d < 1", n_goals);
+    if ((int64_t)n_goals * r9v_voxels(g) >= ((int64_t)1 << 40))
+        return fail(UAM_E_INVALID, "route3d fields of 2^40 or more voxels");
+    return UAM_OK;
+}
+
+int64_t uam_route3d_workspace_bytes(const uam_volume_desc* desc,
+                                    const uam_route3d_params* params) {
+    KRoute3 g{};
+    if (route3d_setup(desc, params, &g)) return -1;
+    return r9v_workspace(g).bytes;
+}
+
+int64_t uam_route3d_visits(const uam_ctx* ctx) { return ctx ? ctx->route3d_visits : 0; }
+
+int uam_route3d_field(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol,
+                      const uam_route3d_params* params, const double* goals, int32_t n_goals,
+                      double* dist, uint8_t* next, void* workspace, int64_t workspace_bytes,
+                      int32_t* rounds_out, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route3d_goals_ok(g, n_goals))) return st;
+    if (!vol || !goals || !dist || !next || !workspace)
+        return fail(UAM_E_INVALID,
+                    "uam_route3d_field: vol / goals / dist / next / workspace is NULL");
+    const R9vWs ws = r9v_workspace(g);
+    if (workspace_bytes < ws.bytes)
+        return fail(UAM_E_INVALID, "route3d workspace %lld bytes < %lld",
+                    (long long)workspace_bytes, (long long)ws.bytes);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)vol & 255) || ((uintptr_t)dist & 7))
+        return fail(UAM_E_INVALID,
+                    "route3d workspace or volume not 256-B or dist not 8-B aligned");
+    DeviceGuard dg(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int TXY = ctx->k9v_tile_xy, TZ = ctx->k9v_tile_z, inner = ctx->k9v_inner;
+    if (!ctx->h_route) HIP_TRY(hipHostMalloc((void**)&ctx->h_route, 64, hipHostMallocDefault));
+    const uint2* vox = (const uint2*)vol;
+    const uint2* col = (const uint2*)((const char*)vol + vol_col_offset(desc));
+    char* base = (char*)workspace;
+    double* c = (double*)(base + ws.c_off);
+    uint32_t* mask = (uint32_t*)(base + ws.mask_off);
+    uint32_t* flags = (uint32_t*)(base + ws.flags_off);
+    int32_t* lists = (int32_t*)(base + ws.lists_off);
+    int32_t* ctl = (int32_t*)(base + ws.ctl_off);
+    const int ntx = r9_tiles(g.nx, TXY), nty = r9_tiles(g.ny, TXY), ntz = r9_tiles(g.nz, TZ);
+    const int nt = ntx * nty * ntz;
+    const int64_t voxels = r9v_voxels(g);
+    const int64_t max_rounds = params->max_rounds ? params->max_rounds : voxels;
+    const int grid = grid_for(voxels, R9_THREADS, 1 << 16);
+    ctx->last_kernel = "K9v";
+    ctx->route3d_visits = 0;
+    hipLaunchKernelGGL(k_route3_cost, dim3(grid), dim3(R9_THREADS), 0, s, vox, col, g, c);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route3_mask, dim3(grid), dim3(R9_THREADS), 0, s, c, g, mask);
+    HIP_TRY(hipGetLastError());
+    int64_t rounds = 0;
+    for (int32_t gi = 0; gi < n_goals; ++gi) {
+        double* d = dist + (int64_t)gi * voxels;
+        const double* goal = goals + 3 * (int64_t)gi;
+        hipLaunchKernelGGL(k_route3_init, dim3(grid), dim3(R9_THREADS), 0, s, c, g, goal, d, TXY,
+                           TZ, ntx, ntz, nt, flags, lists, ctl);
+        HIP_TRY(hipGetLastError());
+        int cur = 0;
+        for (int64_t r = 0;; ++r) {
+            // the active tiles of this round (the one word the host waits for)
+            HIP_TRY(hipMemcpyAsync(ctx->h_route, ctl + cur, sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            const int32_t n = *(volatile int32_t*)ctx->h_route;
+            if (n < 0 || n > nt)
+                return fail(UAM_E_HIP, "route3d field: active-tile count %d outside [0, %d]", n,
+                            nt);
+            if (n == 0) break;
+            if (r >= max_rounds)
+                return fail(UAM_E_STATE,
+                            "route3d field of goal %d has not converged within max_rounds = %lld "
+                            "rounds (%d tiles still active)", gi, (long long)max_rounds, n);
+            if (TXY == 8 && TZ == 4)
+                route3_relax_launch<8, 4>(n, s, c, mask, d, g, ntx, nty, ntz, flags, lists, ctl,
+                                          cur, inner);
+            else if (TXY == 8)
+                route3_relax_launch<8, 8>(n, s, c, mask, d, g, ntx, nty, ntz, flags, lists, ctl,
+                                          cur, inner);
+            else if (TZ == 4)
+                route3_relax_launch<16, 4>(n, s, c, mask, d, g, ntx, nty, ntz, flags, lists, ctl,
+                                           cur, inner);
+            else
+                route3_relax_launch<16, 8>(n, s, c, mask, d, g, ntx, nty, ntz, flags, lists, ctl,
+                                           cur, inner);
+            HIP_TRY(hipGetLastError());
+            ++rounds;
+            ctx->route3d_visits += n;
+            cur ^= 1;
+        }
+        hipLaunchKernelGGL(k_route3_next, dim3(grid), dim3(R9_THREADS), 0, s, c, mask, d, g, goal,
+                           next + (int64_t)gi * voxels);
+        HIP_TRY(hipGetLastError());
+    }
+    if (rounds_out) *rounds_out = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
+    return UAM_OK;
+}
+
+int uam_route3d_paths(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol,
+                      const uam_route3d_params* params, const uint8_t* next, const double* goals,
+                      int32_t n_goals, const double* starts, const int32_t* goal_idx,
+                      int64_t n_queries, double* wp3, int32_t* status, int32_t* steps,
+                      uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route3d_goals_ok(g, n_goals))) return st;
+    if (n_queries < 0) return fail(UAM_E_INVALID, "route3d n_queries < 0");
+    if (n_queries == 0) return UAM_OK;
+    if (!vol || !next || !goals || !starts || !goal_idx || !wp3 || !status)
+        return fail(UAM_E_INVALID, "uam_route3d_paths: a buffer is NULL");
+    if ((uintptr_t)vol & 255) return fail(UAM_E_INVALID, "route3d volume not 256-B aligned");
+    if (n_queries >= ((int64_t)1 << 31) * R9_THREADS)
+        return fail(UAM_E_INVALID, "route3d n_queries too large");
+    DeviceGuard dg(ctx->device);
+    const int64_t blocks = (n_queries + R9_THREADS - 1) / R9_THREADS;
+    hipLaunchKernelGGL(k_route3_trace, dim3((unsigned)blocks), dim3(R9_THREADS), 0,
+                       (hipStream_t)stream, g, (const uint2*)vol,
+                       (const uint2*)((const char*)vol + vol_col_offset(desc)), next, goals,
+                       n_goals, starts, goal_idx, n_queries, ctx->kp.N, wp3, status, steps);
+    HIP_TRY(hipGetLastError());
+    ctx->last_kernel = "K9vt";
+    return UAM_OK;
+}
+
+int uam_route3d_field_host(const uam_volume_desc* desc, const void* vol,
+                           const uam_route3d_params* params, const double* goals,
+                           int32_t n_goals, double* dist, uint8_t* next) {
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route3d_goals_ok(g, n_goals))) return st;
+    if (!vol || !goals || !dist || !next)
+        return fail(UAM_E_INVALID, "uam_route3d_field_host: vol / goals / dist / next is NULL");
+    r9v_field_host(g, (const uint2*)vol, (const uint2*)((const char*)vol + vol_col_offset(desc)),
+                   goals, n_goals, dist, next);
+    return UAM_OK;
+}
+
+int uam_route3d_paths_host(const uam_volume_desc* desc, const void* vol,
+                           const uam_route3d_params* params, const uint8_t* next,
+                           const double* goals, int32_t n_goals, const double* starts,
+                           const int32_t* goal_idx, int64_t n_queries, int32_t N, double* wp3,
+                           int32_t* status, int32_t* steps) {
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route3d_goals_ok(g, n_goals))) return st;
+    if (n_queries < 0 || N < 0) return fail(UAM_E_INVALID, "route3d n_queries or N < 0");
+    if (n_queries == 0) return UAM_OK;
+    if (!vol || !next || !goals || !starts || !goal_idx || !wp3 || !status)
+        return fail(UAM_E_INVALID, "uam_route3d_paths_host: a buffer is NULL");
+    const uint2* vox = (const uint2*)vol;
+    const uint2* col = (const uint2*)((const char*)vol + vol_col_offset(desc));
+    for (int64_t q = 0; q < n_queries; ++q)
+        r9v_trace(g, vox, col, next, goals, n_goals, starts, goal_idx, q, N, wp3, status, steps);
     return UAM_OK;
 }
 

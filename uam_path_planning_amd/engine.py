@@ -181,6 +181,56 @@ def _route_params(lam, block_flags, inflate, max_rounds):
                             int(max_rounds))
 
 
+@dataclass
+class RouteField3D:
+    """The cost-to-go fields of some goals over a risk volume's voxels (Engine.route_field3d,
+    K9v; include/uampath.h "Route seeds in the volume"): dist [G, ny, nx, nz] float64 (+inf:
+    blocked or unreachable), next [G, ny, nx, nz] uint8 (direction 0..25; 26 = the goal voxel;
+    255 = no route), goals [G, 3], rounds / visits as RouteField's.  vol (the volume buffer)
+    and the parameters are kept for route_paths3d (the start's blocking is derived from them).
+    Device tensors from route_field3d, numpy arrays from route_field3d_host.  A derived,
+    untracked product of the volume: rebuild it when the voxels or columns change."""
+    geo: VolumeGeo
+    goals: object = field(repr=False)
+    dist: object = field(repr=False)
+    next: object = field(repr=False)
+    rounds: int = 0
+    visits: int = 0
+    vol: object = field(default=None, repr=False)
+    lam: float = 1.0
+    block_flags: int = _lib.FLAG_NFZ
+    inflate: int = 0
+    agl: float = 0.0
+    z_scale: float = 1e-3
+
+    def params(self, max_rounds=0):
+        return _route3d_params(self.lam, self.block_flags, self.inflate, self.agl,
+                               self.z_scale, max_rounds)
+
+
+def _route3d_params(lam, block_flags, inflate, agl, z_scale, max_rounds):
+    return _lib.Route3dParams(_lib.ABI_VERSION, float(lam), int(block_flags), int(inflate),
+                              int(max_rounds), float(agl), float(z_scale))
+
+
+def _option_key(name):
+    for table in (_lib.ROUTE_OPTIONS, _lib.ROUTE3D_OPTIONS):
+        if name in table:
+            return table[name]
+    return _lib.OPTIONS[name]
+
+
+def _host_vol(vol, geo):
+    """A volume buffer as contiguous 32-bit words on the host: the voxels and, at the 256-B
+    aligned column offset, the column plane (include/uampath.h uam_volume_desc)."""
+    v = np.ascontiguousarray(vol).reshape(-1)
+    col_off = (geo.nx * geo.ny * geo.nz * 8 + 255) // 256 * 256
+    if v.dtype.itemsize != 4 or v.size * 4 < col_off + geo.nx * geo.ny * 8:
+        raise ValueError(f"vol must hold 32-bit words: {geo.ny}x{geo.nx}x{geo.nz} 8-B voxels "
+                         f"and, at byte {col_off}, {geo.ny}x{geo.nx} 8-B columns")
+    return v
+
+
 def _host_rec(rec, geo):
     """A record raster as contiguous 16-B records on the host ([ny, nx, 4] 32-bit words)."""
     r = np.ascontiguousarray(rec)
@@ -446,8 +496,9 @@ class Engine:
         exact integers, independent of the group length -- "K2hx+pack") and "exact_sum_volume"
         (1: the same for K4h's voxel sums in eval_generated3d -- "K4hx+pack"); "k9_tile" (16,
         32, 64) and "k9_inner" (1..256; _lib.ROUTE_OPTIONS): route_field's tile edge and sweeps
-        per round, which its outputs do not depend on."""
-        key = _lib.ROUTE_OPTIONS[name] if name in _lib.ROUTE_OPTIONS else _lib.OPTIONS[name]
+        per round, which its outputs do not depend on; "k9v_tile_xy" (8, 16), "k9v_tile_z"
+        (4, 8) and "k9v_inner" (1..256; _lib.ROUTE3D_OPTIONS): route_field3d's likewise."""
+        key = _option_key(name)
         _lib.check(self.lib.uam_set_option(self._ctx, key, int(value)), "uam_set_option")
         if name == "exact_sum":
             self._exact_sum = bool(int(value))
@@ -456,7 +507,7 @@ class Engine:
 
     def get_option(self, name):
         v = ctypes.c_int64()
-        key = _lib.ROUTE_OPTIONS[name] if name in _lib.ROUTE_OPTIONS else _lib.OPTIONS[name]
+        key = _option_key(name)
         _lib.check(self.lib.uam_get_option(self._ctx, key, ctypes.byref(v)), "uam_get_option")
         return v.value
 
@@ -984,6 +1035,99 @@ class Engine:
             ctypes.byref(rp), nxt.ctypes.data, goals.ctypes.data, goals.shape[0], s.ctypes.data,
             gi.ctypes.data, Q, N, out["wp"].ctypes.data, out["status"].ctypes.data,
             out["steps"].ctypes.data), "uam_route_paths_host")
+        return out
+
+    # -- route seeds in the volume (K9v) ------------------------------------------------------
+    def route_field3d(self, volume, goals, lam=1.0, block_flags=_lib.FLAG_NFZ, inflate=0,
+                      agl=0.0, z_scale=1e-3, max_rounds=0):
+        """The cost-to-go fields of goals [G, 3] (x km, y km, z m) over volume's voxels
+        (uam_route3d_field): a per-goal setup product like route_field's.  Voxel cost 1 + lam *
+        risk; voxels of a column with a block_flags bit, with a non-finite or non-positive cost
+        or whose layer centre lies less than agl metres above the terrain are blocked, inflate
+        voxels of x/y clearance around them; z_scale is Vertical's unit (km per metre of
+        altitude), so the field's metric is the one eval_waypoints3d(..., vertical=) charges;
+        max_rounds 0 = nx*ny*nz.  Returns a RouteField3D; raises UamError when a field has not
+        converged within max_rounds."""
+        torch = _torch()
+        geo = volume.geo
+        g = self.tensor(goals, torch.float64).reshape(-1, 3)
+        G = g.shape[0]
+        rp = _route3d_params(lam, block_flags, inflate, agl, z_scale, max_rounds)
+        gs = geo.as_struct()
+        nbytes = self.lib.uam_route3d_workspace_bytes(ctypes.byref(gs), ctypes.byref(rp))
+        ws = None if nbytes < 0 else self.empty(((nbytes + 255) // 256, 256), torch.uint8)
+        dist = self.empty((G, geo.ny, geo.nx, geo.nz), torch.float64)
+        nxt = self.empty((G, geo.ny, geo.nx, geo.nz), torch.uint8)
+        rounds = ctypes.c_int32()
+        _lib.check(self.lib.uam_route3d_field(
+            self._ctx, ctypes.byref(gs), _ptr(volume.buf), ctypes.byref(rp), _ptr(g), G,
+            _ptr(dist), _ptr(nxt), _ptr(ws), max(nbytes, 0), ctypes.byref(rounds), self.stream),
+            "uam_route3d_field")
+        return RouteField3D(geo, g, dist, nxt, rounds.value,
+                            int(self.lib.uam_route3d_visits(self._ctx)), volume.buf, float(lam),
+                            int(block_flags), int(inflate), float(agl), float(z_scale))
+
+    def route_paths3d(self, field, starts, goal_idx):
+        """Seed paths through a RouteField3D (uam_route3d_paths): starts [Q, 3], goal_idx [Q]
+        into field.goals.  Returns {"wp3" [Q, N+2, 3], "status" [Q], "steps" [Q]} (device
+        tensors); status as route_paths' -- a nonzero status leaves the straight line in wp3.
+        wp3 is what eval_waypoints3d(..., vertical=Vertical(field.z_scale, ...)) takes."""
+        torch = _torch()
+        s = self.tensor(starts, torch.float64).reshape(-1, 3)
+        gi = self.tensor(goal_idx, torch.int32).reshape(-1)
+        Q = s.shape[0]
+        if gi.shape[0] != Q:
+            raise ValueError(f"{Q} starts but {gi.shape[0]} goal indices")
+        N = self.params.N
+        out = {"wp3": self.empty((Q, N + 2, 3), torch.float64),
+               "status": self.empty((Q,), torch.int32), "steps": self.empty((Q,), torch.int32)}
+        rp = field.params()
+        _lib.check(self.lib.uam_route3d_paths(
+            self._ctx, ctypes.byref(field.geo.as_struct()), _ptr(field.vol), ctypes.byref(rp),
+            _ptr(field.next), _ptr(field.goals), field.goals.shape[0], _ptr(s), _ptr(gi), Q,
+            _ptr(out["wp3"]), _ptr(out["status"]), _ptr(out["steps"]), self.stream),
+            "uam_route3d_paths")
+        return out
+
+    @staticmethod
+    def route_field3d_host(geo, vol, goals, lam=1.0, block_flags=_lib.FLAG_NFZ, inflate=0,
+                           agl=0.0, z_scale=1e-3):
+        """route_field3d on the host (uam_route3d_field_host; needs no GPU).  vol: the volume
+        buffer as numpy 32-bit words in the header's layout (8-B voxels {risk, psi}
+        [ny][nx][nz], then at the 256-B aligned offset the 8-B columns {terrain, flags}
+        [ny][nx]).  Returns a RouteField3D of numpy arrays (rounds 0)."""
+        v = _host_vol(vol, geo)
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        G = g.shape[0]
+        dist = np.empty((G, geo.ny, geo.nx, geo.nz), dtype=np.float64)
+        nxt = np.empty((G, geo.ny, geo.nx, geo.nz), dtype=np.uint8)
+        rp = _route3d_params(lam, block_flags, inflate, agl, z_scale, 0)
+        _lib.check(_lib.load().uam_route3d_field_host(
+            ctypes.byref(geo.as_struct()), v.ctypes.data, ctypes.byref(rp), g.ctypes.data, G,
+            dist.ctypes.data, nxt.ctypes.data), "uam_route3d_field_host")
+        return RouteField3D(geo, g, dist, nxt, 0, 0, v, float(lam), int(block_flags),
+                            int(inflate), float(agl), float(z_scale))
+
+    @staticmethod
+    def route_paths3d_host(field, starts, goal_idx, N):
+        """route_paths3d on the host (uam_route3d_paths_host; needs no GPU) for a RouteField3D
+        of numpy arrays; N interior waypoints.  Returns {"wp3", "status", "steps"}."""
+        s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        gi = np.ascontiguousarray(goal_idx, dtype=np.int32).reshape(-1)
+        Q = s.shape[0]
+        if gi.shape[0] != Q:
+            raise ValueError(f"{Q} starts but {gi.shape[0]} goal indices")
+        N = int(N)
+        out = {"wp3": np.empty((Q, max(N, 0) + 2, 3), dtype=np.float64),
+               "status": np.empty((Q,), dtype=np.int32), "steps": np.empty((Q,), dtype=np.int32)}
+        rp = field.params()
+        nxt = np.ascontiguousarray(field.next, dtype=np.uint8)
+        goals = np.ascontiguousarray(field.goals, dtype=np.float64)
+        _lib.check(_lib.load().uam_route3d_paths_host(
+            ctypes.byref(field.geo.as_struct()), _host_vol(field.vol, field.geo).ctypes.data,
+            ctypes.byref(rp), nxt.ctypes.data, goals.ctypes.data, goals.shape[0], s.ctypes.data,
+            gi.ctypes.data, Q, N, out["wp3"].ctypes.data, out["status"].ctypes.data,
+            out["steps"].ctypes.data), "uam_route3d_paths_host")
         return out
 
     # -- coordinate reference systems (K7; SURVEY §8(f) ranks 3-4) --------------------------

@@ -577,7 +577,8 @@ int uam_kernel_time(uam_ctx* ctx, double* ms_total, int64_t* launches);
  * (uam_eval_generated3d_profiles), "K4e+v" / "K4ew+v" / "K4p+v" (their _v forms with the
  * vertical terms); "K9" (uam_route_field) / "K9t" (uam_route_paths) / "K9b"
  * (uam_route_free_bits) / "K9s" (uam_route_paths_smooth); "K9v" (uam_route3d_field) / "K9vt"
- * (uam_route3d_paths); "" before the first call.
+ * (uam_route3d_paths) / "K9vb" (uam_route3d_free_bits) / "K9vs" (uam_route3d_paths_smooth); ""
+ * before the first call.
  * The string is static (never freed).  For benchmarks and tests:
  * which kernel a number belongs to. */
 const char* uam_last_kernel(const uam_ctx* ctx);
@@ -1191,6 +1192,95 @@ int uam_route3d_paths_host(const uam_volume_desc* desc, const void* vol,
                            const double* goals, int32_t n_goals, const double* starts,
                            const int32_t* goal_idx, int64_t n_queries, int32_t N, double* wp3,
                            int32_t* status, int32_t* steps);
+
+/* Route seeds in the volume, smoothing (K9vb / K9vs): any-angle shortcuts on the traced 3-D
+ * path.  A 26-connected route turns by 45 degrees per kink in plan view and flies every altitude
+ * change at the grid's own angle, one layer per voxel step; these calls keep of the traced voxel
+ * chain only the voxels from which the next one kept is no longer in straight sight, and
+ * resample that polyline.  "Route seeds, smoothing" above, restated over voxels.
+ *
+ * Definition (normative; independent statement: tests/route3d_smooth_ref.py).  The trace is
+ * uam_route3d_paths': the status rules, steps and the voxel chain c_0 = s, c_1, .., c_{n-1} = g
+ * along next (n = steps) are unchanged.  Smoothing chooses a subsequence of the interior voxels;
+ * the vertices and the resampling are uam_route3d_paths' own rules applied to that subsequence.
+ * Integer arithmetic alone decides every visibility; the float64 operations are
+ * uam_route3d_paths', in its order, each rounded separately.
+ *   touched    for voxels A, B (integer triples), d = B - A, and a voxel p with r = p - A:
+ *              T3(A, B) is the set of voxels in the integer bounding box of A and B with
+ *                  2*|dx*ry - dy*rx| <= |dx| + |dy|,
+ *                  2*|dx*rz - dz*rx| <= |dx| + |dz| and
+ *                  2*|dy*rz - dz*ry| <= |dy| + |dz|:
+ *              the closed supercover of the segment between the two voxel centres (as
+ *              separating axes of a segment against a box, the bounding box is the three face
+ *              axes and the inequalities are the three edge-cross-direction axes; a segment
+ *              through a voxel corner touches all eight voxels around it).  For a single
+ *              direction step T3 is the 2-, 4- or 8-voxel box of the edge rule; with dz = 0 it
+ *              is T.  Integers only; |dx|, |dy|, |dz| <= span <= 1024, every product < 2^22.
+ *   visible    LOS3(A, B) holds iff every voxel of T3(A, B) is free (not blocked in
+ *              uam_route3d_field's sense, inflation included).  Adjacent chain voxels are
+ *              always visible, by the edge rule.
+ *   anchors    none for n <= 2.  Otherwise a_0 = 1; a_{k+1} = the largest j <= min(a_k + span,
+ *              n - 2) such that LOS3(c_{a_k}, c_i) holds for every i in (a_k, j] ("advance
+ *              while visible", not "the farthest visible"; never less than a_k + 1); stop at
+ *              a_k = n - 2.  c_1 and c_{n-2} are always kept: the start and goal points are no
+ *              voxel centres, so the first and last segments stay the ones uam_route3d_paths
+ *              flies.
+ *   vertices   V_0 = the start point, the centres of c_{a_0}, c_{a_1}, .., V_m = the goal
+ *              point.  S_i (ez = (z_i - z_{i-1}) * kappa, the difference first), the waypoints
+ *              p_j in all three components, the straight line of a nonzero status and the
+ *              status values: uam_route3d_paths' text, word for word.  vertices[q] = m + 1 (2 +
+ *              the number of anchors); 0 for a nonzero status.
+ *   guarantee  every point of a segment lies in a closed voxel of its T3, all free: every
+ *              waypoint of a status-0 path lies in a free voxel.
+ *   bridge     span = 1 keeps every interior voxel: wp3, status and steps are
+ *              uam_route3d_paths' bits.
+ *   second bridge
+ *              nz = 1, the layer centre above every terrain value, agl = 0, start and goal z at
+ *              the layer centre: status, steps, vertices and the x/y of wp3 equal
+ *              uam_route_paths_smooth's on the equivalent raster bit for bit (ez = 0, and
+ *              sqrt((ex*ex + ey*ey) + 0) = sqrt(ex*ex + ey*ey)).
+ * The shortcut test is geometric: it does not weigh the risk along the segment, so a shortcut may
+ * cut a climb to cheaper layers away; span bounds how far a shortcut may leave the field's route.
+ *
+ * uam_route3d_free_bits: the free voxels of (desc, vol_dev, params) as one bit per voxel, set =
+ * free: bit v & 31 of word v >> 5, v = (iy*nx + ix)*nz + iz the voxel index (layer fastest: a
+ * column's layers sit in one or two words), 4 * ((nx*ny*nz + 31) / 32) =
+ * uam_route3d_free_bits_bytes(desc) bytes (-1 for a bad descriptor), 4-B aligned, the unused
+ * bits of the last word 0.  uam_last_kernel: "K9vb".  Failures as uam_route3d_field's for ctx /
+ * desc / params / a NULL or misaligned buffer.
+ * uam_route3d_paths_smooth: uam_route3d_paths with shortcuts of at most span chain voxels, 1 <=
+ * span <= UAM_ROUTE_SPAN_MAX, against bits_dev and next_dev of the same desc, vol and params
+ * (the start's blocking is read from the bits; params is validated as in uam_route3d_field, but
+ * only z_scale is used); steps_dev and vertices_dev may be NULL.  One wave per query; a query
+ * with more than UAM_ROUTE_SMOOTH_LIST anchors is smoothed twice (no output depends on that).
+ * Asynchronous.  uam_last_kernel: "K9vs".  UAM_E_INVALID before any launch for ctx / desc /
+ * params / a required buffer NULL, a bad descriptor or parameter, span outside the range,
+ * n_goals < 1 or too many voxels, nx*ny*nz > 2^31 - 1 - UAM_ROUTE_SPAN_MAX (voxel and chain
+ * indices are int32), n_queries < 0 or too large; UAM_E_VERSION for a wrong abi_version;
+ * UAM_E_STATE without uam_set_params.
+ * The _host calls run the same inline functions without a GPU.  uam_route3d_visible_host: the
+ * library's LOS3 on n pairs of voxel indices (UAM_E_INVALID for one off the volume) into out_u8
+ * (1 = visible). */
+int64_t uam_route3d_free_bits_bytes(const uam_volume_desc* desc);
+int uam_route3d_free_bits(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol_dev,
+                          const uam_route3d_params* params, uint32_t* bits_dev,
+                          uam_stream stream);
+int uam_route3d_paths_smooth(uam_ctx* ctx, const uam_volume_desc* desc,
+                             const uam_route3d_params* params, const uint32_t* bits_dev,
+                             const uint8_t* next_dev, const double* goals_dev, int32_t n_goals,
+                             const double* starts_dev, const int32_t* goal_idx_dev,
+                             int64_t n_queries, int32_t span, double* wp3_dev,
+                             int32_t* status_dev, int32_t* steps_dev, int32_t* vertices_dev,
+                             uam_stream stream);
+int uam_route3d_free_bits_host(const uam_volume_desc* desc, const void* vol,
+                               const uam_route3d_params* params, uint32_t* bits);
+int uam_route3d_paths_smooth_host(const uam_volume_desc* desc, const uam_route3d_params* params,
+                                  const uint32_t* bits, const uint8_t* next, const double* goals,
+                                  int32_t n_goals, const double* starts, const int32_t* goal_idx,
+                                  int64_t n_queries, int32_t N, int32_t span, double* wp3,
+                                  int32_t* status, int32_t* steps, int32_t* vertices);
+int uam_route3d_visible_host(const uam_volume_desc* desc, const uint32_t* bits, int64_t n,
+                             const int32_t* a_vox, const int32_t* b_vox, uint8_t* out_u8);
 
 /* Workspace bytes uam_refine needs for n_paths (after uam_set_geometry/uam_set_params). */
 int64_t uam_refine_workspace_bytes(uam_ctx* ctx, int64_t n_paths,

@@ -3,9 +3,13 @@ bench.py builds it): uam_route3d_field per UAM_OPT_K9V_TILE_XY x UAM_OPT_K9V_TIL
 UAM_OPT_K9V_INNER (host wall ms of the whole call, --reps samples per row, rounds, tile visits,
 visits per tile) for a goal near the centre and one in a corner, both at mid altitude; every row
 must give the first row's dist and next bits (asserted).  Then uam_route3d_paths at --queries
-random starts.  One JSON line per measurement.
+random starts.  With --smooth SPAN [SPAN ...]: uam_route3d_free_bits once per field and
+uam_route3d_paths_smooth at each span (device ms between two events, three calls after one
+untimed), and per span the seeds' shape: vertices per status-0 seed, the share of status-0 seeds
+with climb_sum == 0 and the mean cost under eval_waypoints3d with a 10 degree climb limit, beside
+span 0's.  One JSON line per measurement.
 usage: python tools/time_route3d.py [--R R] [--nz NZ] [--queries Q] [--lam L] [--reps K]
-       [--tile-xy T ..] [--tile-z T ..] [--inner I ..]"""
+       [--tile-xy T ..] [--tile-z T ..] [--inner I ..] [--smooth SPAN ..]"""
 import argparse
 import json
 import os
@@ -27,11 +31,13 @@ def main():
     ap.add_argument("--tile-xy", type=int, nargs="*", default=[8, 16])
     ap.add_argument("--tile-z", type=int, nargs="*", default=[4, 8])
     ap.add_argument("--inner", type=int, nargs="*", default=[4, 16, 64])
+    ap.add_argument("--smooth", type=int, nargs="+", default=[])
     a = ap.parse_args()
     import numpy as np
     import torch
 
-    from uam_path_planning_amd.engine import Engine
+    from uam_path_planning_amd import profiles
+    from uam_path_planning_amd.engine import Engine, Vertical
     from uam_path_planning_amd.geometry import compile_map
     from uam_path_planning_amd.scenario import (CONFIGS, build_region_map, canonical_params,
                                                 canonical_spec, layer_weights, raster_geo)
@@ -93,22 +99,57 @@ def main():
     s = eng.tensor(random_pairs3d(a.queries, seed=5, zmin=cfg["z0"],
                                   zmax=cfg["z0"] + a.nz * cfg["dz"])[:, :3], torch.float64)
     gi = eng.tensor(np.zeros(a.queries, dtype=np.int32), torch.int32)
-    eng.route_paths3d(f, s, gi)
-    torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ms = []
-    for _ in range(3):
-        e0.record()
-        o = eng.route_paths3d(f, s, gi)
-        e1.record()
+
+    def timed(call):
+        """(device ms of three calls after one untimed, the last call's result)"""
+        call()
         torch.cuda.synchronize()
-        ms.append(round(e0.elapsed_time(e1), 3))
+        ms = []
+        for _ in range(3):
+            e0.record()
+            out = call()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(round(e0.elapsed_time(e1), 3))
+        return ms, out
+
+    ms, o = timed(lambda: eng.route_paths3d(f, s, gi))
     st = o["status"].cpu().numpy()
     steps = o["steps"].cpu().numpy()
     print(json.dumps({"route_paths3d_queries": a.queries, "ms_each": ms,
                       "status_counts": {int(k): int((st == k).sum()) for k in np.unique(st)},
                       "steps_mean": float(steps[st == 0].mean()) if (st == 0).any() else None,
                       "steps_max": int(steps.max())}), flush=True)
+    if not a.smooth:
+        return
+
+    def rebuild_bits():
+        f.free_bits = None
+        return eng.route_free_bits3d(f)
+
+    ms, words = timed(rebuild_bits)
+    print(json.dumps({"route_free_bits3d_ms_each": ms, "words": words.numel()}), flush=True)
+    vert = Vertical(f.z_scale, profiles.sin_of_angle(10.0), profiles.sin_of_angle(10.0))
+    ok = st == 0
+
+    def shape(out):
+        ev = eng.eval_waypoints3d(out["wp3"], volume, vertical=vert)
+        climb = ev["climb_sum"].cpu().numpy()[ok]
+        cost = ev["cost"].cpu().numpy()[ok]
+        return {"climb_free_share": round(float((climb == 0).mean()), 4),
+                "climb_sum_mean": float(climb.mean()), "cost_mean": float(cost.mean()),
+                "below_terrain": int((ev["below_terrain"].cpu().numpy()[ok] > 0).sum()),
+                "nfz_hit": int((ev["nfz_hits"].cpu().numpy()[ok] > 0).sum())}
+
+    print(json.dumps({"span": 0, **shape(o)}), flush=True)
+    for span in a.smooth:
+        ms, so = timed(lambda: eng.route_paths3d(f, s, gi, smooth=span))
+        assert bool(torch.equal(so["status"], o["status"]) and torch.equal(so["steps"],
+                                                                           o["steps"]))
+        v = so["vertices"].cpu().numpy()[ok]
+        print(json.dumps({"span": span, "ms_each": ms, "vertices_mean": round(float(v.mean()), 2),
+                          "vertices_max": int(v.max()), **shape(so)}), flush=True)
 
 
 if __name__ == "__main__":

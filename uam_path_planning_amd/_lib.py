@@ -276,6 +276,22 @@ SIGNATURES = {
                                               ctypes.POINTER(Route3dParams), _vp, _vp,
                                               ctypes.c_int32, _vp, _vp, ctypes.c_int64,
                                               ctypes.c_int32, _vp, _vp, _vp]),
+    "uam_route3d_free_bits_bytes": (ctypes.c_int64, [ctypes.POINTER(VolumeDesc)]),
+    "uam_route3d_free_bits": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp,
+                                             ctypes.POINTER(Route3dParams), _vp, _vp]),
+    "uam_route3d_paths_smooth": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc),
+                                                ctypes.POINTER(Route3dParams), _vp, _vp, _vp,
+                                                ctypes.c_int32, _vp, _vp, ctypes.c_int64,
+                                                ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "uam_route3d_free_bits_host": (ctypes.c_int, [ctypes.POINTER(VolumeDesc), _vp,
+                                                  ctypes.POINTER(Route3dParams), _vp]),
+    "uam_route3d_paths_smooth_host": (ctypes.c_int, [ctypes.POINTER(VolumeDesc),
+                                                     ctypes.POINTER(Route3dParams), _vp, _vp,
+                                                     _vp, ctypes.c_int32, _vp, _vp,
+                                                     ctypes.c_int64, ctypes.c_int32,
+                                                     ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    "uam_route3d_visible_host": (ctypes.c_int, [ctypes.POINTER(VolumeDesc), _vp, ctypes.c_int64,
+                                                _vp, _vp, _vp]),
     "uam_refine_workspace_bytes": (ctypes.c_int64, [_vp, ctypes.c_int64,
                                                     ctypes.POINTER(RefineParams)]),
     "uam_refine": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.POINTER(RefineParams), _vp,

@@ -6147,6 +6147,9 @@ __global__ __launch_bounds__(1024) void k_g_final(KParams p, KGrp kg, KOut out,
 // K9v: route seeds in the volume, k_route3_cost, k_route3_mask, k_route3_init, k_route3_relax,
 // k_route3_next, k_route3_trace
 #include "k9v_route.inc"
+// K9vb / K9vs: any-angle shortcuts on the traced route in the volume, k_route3_free_bits,
+// k_route3_smooth
+#include "k9v_smooth.inc"
 
 // closes the anonymous namespace opened above the device-side tables
 }  // namespace
@@ -9518,6 +9521,133 @@ int uam_route_visible_host(const uam_raster_desc* desc, const uint32_t* bits, in
         // the kernel's 32-bit walk wherever a span can reach, 64-bit beyond
         out[i] = far <= UAM_ROUTE_SPAN_MAX ? r9s_visible(bits, g.nx, a_cells[i], b_cells[i])
                                            : r9s_los<int64_t>(bits, wpr, ax, ay, bx, by);
+    }
+    return UAM_OK;
+}
+
+// ---- K9vb / K9vs: shortcuts on the traced route in the volume (k9v_smooth.inc) -----------------
+static int route3d_smooth_ok(const KRoute3& g, int32_t n_goals, int64_t n_queries, int32_t span) {
+    const int st = route3d_goals_ok(g, n_goals);
+    if (st) return st;
+    if (n_queries < 0) return fail(UAM_E_INVALID, "route3d n_queries < 0");
+    if (span < 1 || span > UAM_ROUTE_SPAN_MAX)
+        return fail(UAM_E_INVALID, "route3d span %d outside [1, %d]", span, UAM_ROUTE_SPAN_MAX);
+    // voxel and chain indices are int32 and the kernel forms a + span
+    if (r9v_voxels(g) > (int64_t)INT32_MAX - UAM_ROUTE_SPAN_MAX)
+        return fail(UAM_E_INVALID, "route3d smoothing needs nx*ny*nz <= 2^31 - 1 - %d",
+                    UAM_ROUTE_SPAN_MAX);
+    return UAM_OK;
+}
+
+int64_t uam_route3d_free_bits_bytes(const uam_volume_desc* desc) {
+    KVolume kv;
+    if (make_kvolume(desc, &kv)) return -1;
+    return (((int64_t)kv.nx * kv.ny * kv.nz + 31) >> 5) * 4;
+}
+
+int uam_route3d_free_bits(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol,
+                          const uam_route3d_params* params, uint32_t* bits, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    KRoute3 g{};
+    const int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if (!vol || !bits) return fail(UAM_E_INVALID, "uam_route3d_free_bits: vol / bits is NULL");
+    if (((uintptr_t)vol & 255) || ((uintptr_t)bits & 3))
+        return fail(UAM_E_INVALID, "route3d volume not 256-B or free bits not 4-B aligned");
+    DeviceGuard dg(ctx->device);
+    const int64_t chunks = (r9v_voxels(g) + 63) >> 6;
+    hipLaunchKernelGGL(k_route3_free_bits, dim3(grid_for(chunks * 64, R9_THREADS, 1 << 16)),
+                       dim3(R9_THREADS), 0, (hipStream_t)stream, (const uint2*)vol,
+                       (const uint2*)((const char*)vol + vol_col_offset(desc)), g, bits);
+    HIP_TRY(hipGetLastError());
+    ctx->last_kernel = "K9vb";
+    return UAM_OK;
+}
+
+int uam_route3d_paths_smooth(uam_ctx* ctx, const uam_volume_desc* desc,
+                             const uam_route3d_params* params, const uint32_t* bits,
+                             const uint8_t* next, const double* goals, int32_t n_goals,
+                             const double* starts, const int32_t* goal_idx, int64_t n_queries,
+                             int32_t span, double* wp3, int32_t* status, int32_t* steps,
+                             int32_t* vertices, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route3d_smooth_ok(g, n_goals, n_queries, span))) return st;
+    if (n_queries == 0) return UAM_OK;
+    if (!bits || !next || !goals || !starts || !goal_idx || !wp3 || !status)
+        return fail(UAM_E_INVALID, "uam_route3d_paths_smooth: a buffer is NULL");
+    if (n_queries >= ((int64_t)1 << 31) * R9S_WAVES)
+        return fail(UAM_E_INVALID, "route3d n_queries too large");
+    DeviceGuard dg(ctx->device);
+    const int64_t blocks = (n_queries + R9S_WAVES - 1) / R9S_WAVES;
+    hipLaunchKernelGGL(k_route3_smooth, dim3((unsigned)blocks), dim3(R9S_WAVES * 64), 0,
+                       (hipStream_t)stream, g, bits, next, goals, n_goals, starts, goal_idx,
+                       n_queries, ctx->kp.N, span, wp3, status, steps, vertices);
+    HIP_TRY(hipGetLastError());
+    ctx->last_kernel = "K9vs";
+    return UAM_OK;
+}
+
+int uam_route3d_free_bits_host(const uam_volume_desc* desc, const void* vol,
+                               const uam_route3d_params* params, uint32_t* bits) {
+    KRoute3 g{};
+    const int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if (!vol || !bits)
+        return fail(UAM_E_INVALID, "uam_route3d_free_bits_host: vol / bits is NULL");
+    r9vs_free_bits_host(g, (const uint2*)vol,
+                        (const uint2*)((const char*)vol + vol_col_offset(desc)), bits);
+    return UAM_OK;
+}
+
+int uam_route3d_paths_smooth_host(const uam_volume_desc* desc, const uam_route3d_params* params,
+                                  const uint32_t* bits, const uint8_t* next, const double* goals,
+                                  int32_t n_goals, const double* starts, const int32_t* goal_idx,
+                                  int64_t n_queries, int32_t N, int32_t span, double* wp3,
+                                  int32_t* status, int32_t* steps, int32_t* vertices) {
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route3d_smooth_ok(g, n_goals, n_queries, span))) return st;
+    if (N < 0) return fail(UAM_E_INVALID, "route3d N < 0");
+    if (n_queries == 0) return UAM_OK;
+    if (!bits || !next || !goals || !starts || !goal_idx || !wp3 || !status)
+        return fail(UAM_E_INVALID, "uam_route3d_paths_smooth_host: a buffer is NULL");
+    std::vector<int32_t> cells, anchors;
+    for (int64_t q = 0; q < n_queries; ++q)
+        r9vs_smooth_host(g, bits, next, goals, n_goals, starts, goal_idx, q, N, span, wp3, status,
+                         steps, vertices, cells, anchors);
+    return UAM_OK;
+}
+
+int uam_route3d_visible_host(const uam_volume_desc* desc, const uint32_t* bits, int64_t n,
+                             const int32_t* a_vox, const int32_t* b_vox, uint8_t* out) {
+    KVolume kv;
+    const int st = make_kvolume(desc, &kv);
+    if (st) return st;
+    if (n < 0) return fail(UAM_E_INVALID, "uam_route3d_visible_host: n < 0");
+    if (n == 0) return UAM_OK;
+    if (!bits || !a_vox || !b_vox || !out)
+        return fail(UAM_E_INVALID, "uam_route3d_visible_host: a buffer is NULL");
+    const int64_t nx = kv.nx, nz = kv.nz, voxels = nx * kv.ny * nz;
+    for (int64_t i = 0; i < n; ++i)
+        if (a_vox[i] < 0 || a_vox[i] >= voxels || b_vox[i] < 0 || b_vox[i] >= voxels)
+            return fail(UAM_E_INVALID, "uam_route3d_visible_host: pair %lld is off the volume",
+                        (long long)i);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t ca = a_vox[i] / nz, cb = b_vox[i] / nz;
+        const int64_t ax = ca % nx, ay = ca / nx, az = a_vox[i] % nz;
+        const int64_t bx = cb % nx, by = cb / nx, bz = b_vox[i] % nz;
+        const int64_t far =
+            std::max(std::max(std::llabs(bx - ax), std::llabs(by - ay)), std::llabs(bz - az));
+        // the kernel's 32-bit walk wherever a span can reach, 64-bit beyond
+        out[i] = far <= UAM_ROUTE_SPAN_MAX && voxels <= INT32_MAX
+                     ? r9vs_los<int32_t>(bits, kv.nx, kv.nz, (int32_t)ax, (int32_t)ay, (int32_t)az,
+                                         (int32_t)bx, (int32_t)by, (int32_t)bz)
+                     : r9vs_los<int64_t>(bits, nx, nz, ax, ay, az, bx, by, bz);
     }
     return UAM_OK;
 }

@@ -189,7 +189,10 @@ class RouteField3D:
     255 = no route), goals [G, 3], rounds / visits as RouteField's.  vol (the volume buffer)
     and the parameters are kept for route_paths3d (the start's blocking is derived from them).
     Device tensors from route_field3d, numpy arrays from route_field3d_host.  A derived,
-    untracked product of the volume: rebuild it when the voxels or columns change."""
+    untracked product of the volume: rebuild it when the voxels or columns change.
+    free_bits: the free voxels as one bit per voxel ([(nx*ny*nz + 31) // 32] 32-bit words, bit
+    v & 31 of word v >> 5 for the voxel index v; Engine.route_free_bits3d), built and kept here
+    by the first route_paths3d(..., smooth >= 1)."""
     geo: VolumeGeo
     goals: object = field(repr=False)
     dist: object = field(repr=False)
@@ -202,6 +205,7 @@ class RouteField3D:
     inflate: int = 0
     agl: float = 0.0
     z_scale: float = 1e-3
+    free_bits: object = field(default=None, repr=False)
 
     def params(self, max_rounds=0):
         return _route3d_params(self.lam, self.block_flags, self.inflate, self.agl,
@@ -1067,11 +1071,31 @@ class Engine:
                             int(self.lib.uam_route3d_visits(self._ctx)), volume.buf, float(lam),
                             int(block_flags), int(inflate), float(agl), float(z_scale))
 
-    def route_paths3d(self, field, starts, goal_idx):
+    def route_free_bits3d(self, field):
+        """The free voxels of a RouteField3D's volume and parameters as one bit per voxel
+        (uam_route3d_free_bits, K9vb): [(nx*ny*nz + 31) // 32] int32 words, bit v & 31 of word
+        v >> 5 set = free, v = (iy*nx + ix)*nz + iz.  Computed once and kept on the field."""
+        if field.free_bits is None:
+            torch = _torch()
+            geo = field.geo
+            bits = self.empty(((geo.nx * geo.ny * geo.nz + 31) // 32,), torch.int32)
+            rp = field.params()
+            _lib.check(self.lib.uam_route3d_free_bits(
+                self._ctx, ctypes.byref(geo.as_struct()), _ptr(field.vol), ctypes.byref(rp),
+                _ptr(bits), self.stream), "uam_route3d_free_bits")
+            field.free_bits = bits
+        return field.free_bits
+
+    def route_paths3d(self, field, starts, goal_idx, smooth=0):
         """Seed paths through a RouteField3D (uam_route3d_paths): starts [Q, 3], goal_idx [Q]
         into field.goals.  Returns {"wp3" [Q, N+2, 3], "status" [Q], "steps" [Q]} (device
         tensors); status as route_paths' -- a nonzero status leaves the straight line in wp3.
-        wp3 is what eval_waypoints3d(..., vertical=Vertical(field.z_scale, ...)) takes."""
+        wp3 is what eval_waypoints3d(..., vertical=Vertical(field.z_scale, ...)) takes.
+        smooth >= 1 (uam_route3d_paths_smooth, K9vs): any-angle shortcuts over at most smooth
+        chain voxels (1..1024) wherever the voxels between lie in straight sight, in plan view
+        and in altitude; adds "vertices" [Q] (the polyline's vertices, end points included; 0
+        for a nonzero status).  smooth = 1 keeps every voxel: the bits of smooth = 0.  The test
+        is geometric and does not weigh risk: a long span may cut a climb to cheaper layers."""
         torch = _torch()
         s = self.tensor(starts, torch.float64).reshape(-1, 3)
         gi = self.tensor(goal_idx, torch.int32).reshape(-1)
@@ -1082,6 +1106,15 @@ class Engine:
         out = {"wp3": self.empty((Q, N + 2, 3), torch.float64),
                "status": self.empty((Q,), torch.int32), "steps": self.empty((Q,), torch.int32)}
         rp = field.params()
+        if smooth:
+            out["vertices"] = self.empty((Q,), torch.int32)
+            bits = self.route_free_bits3d(field)
+            _lib.check(self.lib.uam_route3d_paths_smooth(
+                self._ctx, ctypes.byref(field.geo.as_struct()), ctypes.byref(rp), _ptr(bits),
+                _ptr(field.next), _ptr(field.goals), field.goals.shape[0], _ptr(s), _ptr(gi), Q,
+                int(smooth), _ptr(out["wp3"]), _ptr(out["status"]), _ptr(out["steps"]),
+                _ptr(out["vertices"]), self.stream), "uam_route3d_paths_smooth")
+            return out
         _lib.check(self.lib.uam_route3d_paths(
             self._ctx, ctypes.byref(field.geo.as_struct()), _ptr(field.vol), ctypes.byref(rp),
             _ptr(field.next), _ptr(field.goals), field.goals.shape[0], _ptr(s), _ptr(gi), Q,
@@ -1109,9 +1142,24 @@ class Engine:
                             int(inflate), float(agl), float(z_scale))
 
     @staticmethod
-    def route_paths3d_host(field, starts, goal_idx, N):
+    def route_free_bits3d_host(field):
+        """route_free_bits3d on the host (uam_route3d_free_bits_host) for a RouteField3D of
+        numpy arrays: [(nx*ny*nz + 31) // 32] uint32, kept on the field."""
+        if field.free_bits is None:
+            geo = field.geo
+            bits = np.empty(((geo.nx * geo.ny * geo.nz + 31) // 32,), dtype=np.uint32)
+            rp = field.params()
+            _lib.check(_lib.load().uam_route3d_free_bits_host(
+                ctypes.byref(geo.as_struct()), _host_vol(field.vol, geo).ctypes.data,
+                ctypes.byref(rp), bits.ctypes.data), "uam_route3d_free_bits_host")
+            field.free_bits = bits
+        return field.free_bits
+
+    @staticmethod
+    def route_paths3d_host(field, starts, goal_idx, N, smooth=0):
         """route_paths3d on the host (uam_route3d_paths_host; needs no GPU) for a RouteField3D
-        of numpy arrays; N interior waypoints.  Returns {"wp3", "status", "steps"}."""
+        of numpy arrays; N interior waypoints.  Returns {"wp3", "status", "steps"}, and
+        "vertices" for smooth >= 1 (uam_route3d_paths_smooth_host)."""
         s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
         gi = np.ascontiguousarray(goal_idx, dtype=np.int32).reshape(-1)
         Q = s.shape[0]
@@ -1123,6 +1171,16 @@ class Engine:
         rp = field.params()
         nxt = np.ascontiguousarray(field.next, dtype=np.uint8)
         goals = np.ascontiguousarray(field.goals, dtype=np.float64)
+        if smooth:
+            out["vertices"] = np.empty((Q,), dtype=np.int32)
+            bits = Engine.route_free_bits3d_host(field)
+            _lib.check(_lib.load().uam_route3d_paths_smooth_host(
+                ctypes.byref(field.geo.as_struct()), ctypes.byref(rp), bits.ctypes.data,
+                nxt.ctypes.data, goals.ctypes.data, goals.shape[0], s.ctypes.data,
+                gi.ctypes.data, Q, N, int(smooth), out["wp3"].ctypes.data,
+                out["status"].ctypes.data, out["steps"].ctypes.data,
+                out["vertices"].ctypes.data), "uam_route3d_paths_smooth_host")
+            return out
         _lib.check(_lib.load().uam_route3d_paths_host(
             ctypes.byref(field.geo.as_struct()), _host_vol(field.vol, field.geo).ctypes.data,
             ctypes.byref(rp), nxt.ctypes.data, goals.ctypes.data, goals.shape[0], s.ctypes.data,

@@ -1081,6 +1081,105 @@ int uam_route_paths_smooth_host(const uam_raster_desc* desc, const uint32_t* bit
 int uam_route_visible_host(const uam_raster_desc* desc, const uint32_t* bits, int64_t n,
                            const int32_t* a_cells, const int32_t* b_cells, uint8_t* out_u8);
 
+/* Route seeds, joint field (K9j): one field to the nearest of many goals, with an owner map.
+ * uam_route_field answers "what is the cheapest route to that goal?" once per goal.  These calls
+ * answer "which goal is cheapest to reach from here, and how?" for all goals in one relaxation:
+ * the contingency landing site of any point of a route, the service area of each vertiport under
+ * the risk-weighted metric, a start whose goal is not fixed yet.
+ *
+ * Definition (normative; independent statement: tests/route_joint_ref.py).  Cells, directions,
+ * cell cost, blocking, inflation, edges, the corner rule and the edge weight are the "Route
+ * seeds" text, unchanged.  Every float64 operation is rounded separately, with no fused
+ * multiply-add.
+ *   valid goal goal i is valid when its point maps to a cell g_i on the raster and that cell is
+ *              free.  Gc is the set of cells of the valid goals.  Several goals may share a cell.
+ *              Gc may be empty.
+ *   field      dist[v] = 0 for v in Gc; elsewhere the minimum, over edge paths that start in any
+ *              cell of Gc and end in v, of the left fold fl(fl(0 + w_01) + w_12) + ..; +inf for
+ *              blocked and unreachable cells, and everywhere when Gc is empty.  It is the one
+ *              fixed point of d[v] = min(d[v], fl(d[u] + w(u,v))) started from 0 on Gc and +inf
+ *              elsewhere: the bits do not depend on the relaxation order, the tile edge or the
+ *              sweeps per round.
+ *   bridge 1   dist equals the elementwise minimum over i of the planes uam_route_field writes
+ *              for the same goals, bit for bit (the path sets are a union; an invalid goal's
+ *              plane is all +inf).
+ *   bridge 2   with n_goals = 1, dist and next are uam_route_field's bits.
+ *   next hop   uint8 per cell, formed after convergence: 8 at every cell of Gc, 255 where dist is
+ *              +inf, otherwise the lowest k whose neighbour u_k has an edge to v with
+ *              fl(dist[u_k] + w(u_k, v)) == dist[v].  The goal test is membership in Gc, not
+ *              dist == 0.
+ *   owner      int32 per cell: -1 where next is 255; at a cell of Gc the lowest index i with
+ *              g_i = v; otherwise the owner of the first cell of Gc on the chain v -> v +
+ *              dir(next[v]) -> ..; -1 when the chain visits nx*ny cells without reaching Gc
+ *              (only where huge costs absorb small weights and equal dist values form a cycle).
+ *              Owner is defined through the chain, not through a comparison of per-goal
+ *              distances: ties are broken by the next-hop rule alone.
+ *   owner      if owner[v] = i >= 0 then dist[v] == dist_i[v] bit for bit, dist_i being goal i's
+ *   property   own field: the chain realises dist[v] as a fold from g_i, and dist is the minimum
+ *              over all goals.
+ *   path       a query is a start point only.  Status, tested in this order:
+ *                1  the start is off the raster or in a blocked cell;
+ *                2  next[s] = 255 (with no valid goal every free start gets 2);
+ *                3  owner[s] = -1 although dist[s] is finite;
+ *                0  ok.  There is no status 4.
+ *              Status 0: goal_out[q] = o = owner[s], the goal point is goals[o], and the chain,
+ *              steps, vertices, S_i, waypoints and (span >= 1) anchors are uam_route_paths' and
+ *              uam_route_paths_smooth's text word for word, along the joint next from s to g_o.
+ *              vertices[q] at span 0 counts every interior cell: max(steps, 2), span 1's value.
+ *              A nonzero status: goal_out[q] = -1, steps = 0, vertices = 0 and every waypoint is
+ *              the start point (the existing rule for a goal index out of range).
+ *   bridge 3   with n_goals = 1, status, steps and vertices equal uam_route_paths' (span 0) and
+ *              uam_route_paths_smooth's (span >= 1) with goal_idx = 0 for every query whose
+ *              status there is not 4; the waypoints are equal as well for status 0.
+ *   guarantee  every waypoint of a status-0 path lies in a free cell, as for the existing calls.
+ *
+ * uam_route_field_joint: goals_dev [n_goals][2] into dist_dev [ny][nx] f64, next_dev [ny][nx] u8
+ * and owner_dev [ny][nx] int32; workspace_dev holds uam_route_joint_workspace_bytes(desc, params,
+ * n_goals) bytes (-1 for bad arguments), 256-B aligned: uam_route_field's workspace and an int32
+ * parent plane.  One start state for all goals (the distinct tiles of Gc form the first active
+ * set), then uam_route_field's rounds with its kernel, UAM_OPT_K9_TILE / UAM_OPT_K9_INNER and
+ * max_rounds (the call may synchronise the stream between rounds); the owner by pointer jumping
+ * over the parent plane, ceil(log2(nx*ny)) ordinary launches with no host read between them.
+ * rounds_out and uam_route_visits as for uam_route_field.  uam_last_kernel: "K9j".
+ * uam_route_paths_joint: Q start points against next_dev, owner_dev and goals_dev of one
+ * uam_route_field_joint call, into wp_dev [Q][N+2][2], status_dev [Q] and (each may be NULL)
+ * steps_dev, vertices_dev, goal_out_dev [Q].  span = 0: the plain trace, one lane per query, the
+ * start's blocking read from rec_dev, bits_dev may be NULL; uam_last_kernel "K9jt".  1 <= span <=
+ * UAM_ROUTE_SPAN_MAX: shortcuts as uam_route_paths_smooth makes them, one wave per query, the
+ * blocking from bits_dev (uam_route_free_bits of the same desc, rec, params), rec_dev may be
+ * NULL; uam_last_kernel "K9js".  Asynchronous.  N from uam_set_params.
+ * Failures: uam_route_field's and uam_route_paths_smooth's lists, UAM_E_INVALID before any launch
+ * or allocation; in addition n_goals < 1 or > 2^20 and nx*ny > 2^31 - 1 - UAM_ROUTE_SPAN_MAX
+ * (parents and owners are int32), owner_dev not 4-B aligned, span outside [0,
+ * UAM_ROUTE_SPAN_MAX].  UAM_E_STATE, the message naming max_rounds, when the field has not
+ * converged within max_rounds rounds (outputs unspecified, the context stays usable), and for
+ * uam_route_paths_joint without uam_set_params.
+ * The _host calls run the same inline functions without a GPU: the field's minimum by a heap
+ * Dijkstra seeded with all of Gc, the owner by following the chains. */
+int64_t uam_route_joint_workspace_bytes(const uam_raster_desc* desc,
+                                        const uam_route_params* params, int32_t n_goals);
+int uam_route_field_joint(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec_dev,
+                          const uam_route_params* params, const double* goals_dev,
+                          int32_t n_goals, double* dist_dev, uint8_t* next_dev,
+                          int32_t* owner_dev, void* workspace_dev, int64_t workspace_bytes,
+                          int32_t* rounds_out, uam_stream stream);
+int uam_route_paths_joint(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec_dev,
+                          const uam_route_params* params, const uint32_t* bits_dev,
+                          const uint8_t* next_dev, const int32_t* owner_dev,
+                          const double* goals_dev, int32_t n_goals, const double* starts_dev,
+                          int64_t n_queries, int32_t span, double* wp_dev, int32_t* status_dev,
+                          int32_t* steps_dev, int32_t* vertices_dev, int32_t* goal_out_dev,
+                          uam_stream stream);
+int uam_route_field_joint_host(const uam_raster_desc* desc, const void* rec,
+                               const uam_route_params* params, const double* goals,
+                               int32_t n_goals, double* dist, uint8_t* next, int32_t* owner);
+int uam_route_paths_joint_host(const uam_raster_desc* desc, const void* rec,
+                               const uam_route_params* params, const uint32_t* bits,
+                               const uint8_t* next, const int32_t* owner, const double* goals,
+                               int32_t n_goals, const double* starts, int64_t n_queries,
+                               int32_t N, int32_t span, double* wp, int32_t* status,
+                               int32_t* steps, int32_t* vertices, int32_t* goal_out);
+
 /* ---- Route seeds in the volume (K9v): 3-D cost-to-go field and traced 3-D routes --------------
  * The route seeds above are flat: they know neither the terrain nor the altitude layers.  These
  * calls are their counterpart over the risk volume's voxels: the cheapest 26-connected route

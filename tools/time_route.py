@@ -3,9 +3,12 @@ UAM_OPT_K9_INNER (host wall ms of the whole call, rounds, tile visits, visits pe
 goal near the centre and one in a corner, checking that every setting gives the same bits, then
 uam_route_paths at --queries starts, uam_route_free_bits, and uam_route_paths_smooth per
 --smooth SPAN (its bits at span 1 checked against uam_route_paths').  One JSON line per
-measurement.
+measurement.  --joint PORTS adds the joint field (K9j) of PORTS vertiports
+(tools/route_seed_feasibility.py's draw and inflate = 1) next to uam_route_field for the same
+goals -- wall ms, memory, bridge 1 checked -- and route_paths on the joint field (span 0 and 64)
+next to the per-goal calls on the centre goal's own field.
 usage: python tools/time_route.py [--R R] [--queries Q] [--lam L] [--inflate I]
-       [--smooth SPAN ..] [--no-sweep]"""
+       [--smooth SPAN ..] [--no-sweep] [--joint PORTS]"""
 import argparse
 import json
 import os
@@ -28,6 +31,8 @@ def main():
                     help="spans to time uam_route_paths_smooth at")
     ap.add_argument("--no-sweep", action="store_true",
                     help="skip the tile x inner sweep of uam_route_field")
+    ap.add_argument("--joint", type=int, default=0, metavar="PORTS",
+                    help="time the joint field of PORTS vertiports against the per-goal fields")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -93,6 +98,8 @@ def main():
                       "status_counts": {int(k): int((st == k).sum()) for k in np.unique(st)},
                       "steps_mean": float(steps[st == 0].mean()) if (st == 0).any() else None,
                       "steps_max": int(steps.max())}), flush=True)
+    if a.joint:
+        joint_rows(a, eng, raster, f, s, gi, np, torch)
     if not a.smooth:
         return
 
@@ -135,6 +142,71 @@ def main():
                                                         and torch.equal(sm["steps"],
                                                                         o["steps"]))}),
               flush=True)
+
+
+def joint_rows(a, eng, raster, centre, s, gi, np, torch):
+    """The --joint rows: one sample each of the per-goal and the joint field for the same
+    vertiports, twice over (the repeat's spread), then the paths."""
+    from uam_path_planning_amd.synthetic import random_pairs
+
+    cand = random_pairs(8 * a.joint + 64, seed=4)[:, :2]
+    pe = eng.eval_points(torch.tensor(cand, device="cuda"), want=("psi_raw", "collide"))
+    ok = ((pe["psi_raw"] == 0) & (pe["collide"] == 0)).cpu().numpy()
+    ports = cand[ok][:a.joint]
+    cells = a.R * a.R
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, round((time.perf_counter() - t0) * 1e3, 2)
+
+    for rep in range(2):
+        per, ms_per = wall(lambda: eng.route_field(raster, ports, lam=a.lam, inflate=1))
+        jf, ms_joint = wall(lambda: eng.route_field(raster, ports, lam=a.lam, inflate=1,
+                                                    joint=True))
+        owner = jf.owner
+        print(json.dumps({
+            "joint_ports": len(ports), "sample": rep, "per_goal_ms": ms_per,
+            "joint_ms": ms_joint, "ratio": round(ms_per / ms_joint, 2),
+            "per_goal_rounds": per.rounds, "joint_rounds": jf.rounds,
+            "per_goal_visits": per.visits, "joint_visits": jf.visits,
+            "per_goal_bytes": len(ports) * cells * 9, "joint_bytes": cells * 13,
+            "joint_workspace_parent_bytes": cells * 4,
+            "bridge_1": bool(torch.equal(jf.dist[0].view(torch.int64),
+                                         per.dist.min(dim=0).values.view(torch.int64))),
+            "owners": int(torch.unique(owner[owner >= 0]).numel()),
+            "cells_owned": int((owner >= 0).sum()),
+            "cells_with_a_route_but_no_owner": int(((owner < 0) & (jf.next[0] != 255)).sum())}),
+            flush=True)
+        del per
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn, reps=3):
+        out = fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(reps):
+            e0.record()
+            out = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(round(e0.elapsed_time(e1), 3))
+        return out, ms
+
+    for span in (0, 64):
+        o, ms_per = timed(lambda: eng.route_paths(centre, s, gi, smooth=span))
+        j, ms_joint = timed(lambda: eng.route_paths(jf, s, smooth=span))
+        st = j["status"].cpu().numpy()
+        steps = j["steps"].cpu().numpy()
+        print(json.dumps({
+            "joint_paths_span": span, "queries": a.queries, "per_goal_ms_each": ms_per,
+            "joint_ms_each": ms_joint,
+            "status_counts": {int(k): int((st == k).sum()) for k in np.unique(st)},
+            "steps_mean": float(steps[st == 0].mean()) if (st == 0).any() else None,
+            "per_goal_steps_mean": float(o["steps"][o["status"] == 0].double().mean())}),
+            flush=True)
 
 
 if __name__ == "__main__":

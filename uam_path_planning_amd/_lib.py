@@ -260,6 +260,24 @@ SIGNATURES = {
                                                    _vp]),
     "uam_route_visible_host": (ctypes.c_int, [ctypes.POINTER(RasterDesc), _vp, ctypes.c_int64,
                                               _vp, _vp, _vp]),
+    "uam_route_joint_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(RasterDesc),
+                                                         ctypes.POINTER(RouteParams),
+                                                         ctypes.c_int32]),
+    "uam_route_field_joint": (ctypes.c_int, [_vp, ctypes.POINTER(RasterDesc), _vp,
+                                             ctypes.POINTER(RouteParams), _vp, ctypes.c_int32, _vp,
+                                             _vp, _vp, _vp, ctypes.c_int64, _i32p, _vp]),
+    "uam_route_paths_joint": (ctypes.c_int, [_vp, ctypes.POINTER(RasterDesc), _vp,
+                                             ctypes.POINTER(RouteParams), _vp, _vp, _vp, _vp,
+                                             ctypes.c_int32, _vp, ctypes.c_int64, ctypes.c_int32,
+                                             _vp, _vp, _vp, _vp, _vp, _vp]),
+    "uam_route_field_joint_host": (ctypes.c_int, [ctypes.POINTER(RasterDesc), _vp,
+                                                  ctypes.POINTER(RouteParams), _vp,
+                                                  ctypes.c_int32, _vp, _vp, _vp]),
+    "uam_route_paths_joint_host": (ctypes.c_int, [ctypes.POINTER(RasterDesc), _vp,
+                                                  ctypes.POINTER(RouteParams), _vp, _vp, _vp, _vp,
+                                                  ctypes.c_int32, _vp, ctypes.c_int64,
+                                                  ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
+                                                  _vp, _vp]),
     "uam_route3d_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(VolumeDesc),
                                                      ctypes.POINTER(Route3dParams)]),
     "uam_route3d_field": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp,

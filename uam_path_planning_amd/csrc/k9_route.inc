@@ -138,32 +138,57 @@ __host__ __device__ __forceinline__ double r9_seg(double ax, double ay, double b
     return sqrt(ex * ex + ey * ey);
 }
 
+// J (a joint field, k9_joint.inc): next is the one joint plane, goal_idx the owner plane
+// [ny][nx]; the goal is owner[cell(start)], the status tests are 1, 2, 3 (no owner) and every
+// nonzero status leaves the start point in all waypoints.  vertices and goal_out are written
+// for J alone.
+template <bool J = false>
 __host__ __device__ inline void r9_trace(const KRoute& g, const uint4* rec, const uint8_t* next,
                                          const double* goals, int32_t n_goals,
                                          const double* starts, const int32_t* goal_idx,
                                          int64_t q, int32_t N, double* wp, int32_t* status,
-                                         int32_t* steps) {
+                                         int32_t* steps, int32_t* vertices = nullptr,
+                                         int32_t* goal_out = nullptr) {
     const double sx = starts[2 * q], sy = starts[2 * q + 1];
-    const int32_t gi = goal_idx[q];
+    int32_t gi = J ? -1 : goal_idx[q];
     double* out = wp + q * (int64_t)(N + 2) * 2;
     const double dn1 = (double)(N + 1);
     double gx = sx, gy = sy;  // a goal index out of range: every waypoint is the start point
     int st = 0;
     int32_t gcell = -1, scell = -1;
     const uint8_t* nf = next;
-    if (gi < 0 || gi >= n_goals) {
-        st = 4;
-    } else {
-        gx = goals[2 * (int64_t)gi], gy = goals[2 * (int64_t)gi + 1];
-        nf = next + (int64_t)gi * g.nx * g.ny;
-        gcell = r9_cell(g, gx, gy);
-        if (gcell < 0 || nf[gcell] != 8) st = 4;
-    }
-    if (!st) {
+    if (J) {
         scell = r9_cell(g, sx, sy);
-        if (scell < 0 || !(r9_cost(g, rec, scell % g.nx, scell / g.nx) < r9_inf())) st = 1;
+        if (scell < 0 || !(r9_cost(g, rec, scell % g.nx, scell / g.nx) < r9_inf())) {
+            st = 1;
+        } else if (nf[scell] == 255) {
+            st = 2;
+        } else {
+            gi = goal_idx[scell];
+            // an owner that is no goal of this call is no field of uam_route_field_joint
+            gcell = gi < 0 || gi >= n_goals
+                        ? -1
+                        : r9_cell(g, goals[2 * (int64_t)gi], goals[2 * (int64_t)gi + 1]);
+            if (gcell < 0)
+                st = 3;
+            else
+                gx = goals[2 * (int64_t)gi], gy = goals[2 * (int64_t)gi + 1];
+        }
+    } else {
+        if (gi < 0 || gi >= n_goals) {
+            st = 4;
+        } else {
+            gx = goals[2 * (int64_t)gi], gy = goals[2 * (int64_t)gi + 1];
+            nf = next + (int64_t)gi * g.nx * g.ny;
+            gcell = r9_cell(g, gx, gy);
+            if (gcell < 0 || nf[gcell] != 8) st = 4;
+        }
+        if (!st) {
+            scell = r9_cell(g, sx, sy);
+            if (scell < 0 || !(r9_cost(g, rec, scell % g.nx, scell / g.nx) < r9_inf())) st = 1;
+        }
+        if (!st && nf[scell] == 255) st = 2;
     }
-    if (!st && nf[scell] == 255) st = 2;
     double sm = 0.0;
     int32_t count = 0;
     if (!st) {  // first walk: S_m
@@ -177,6 +202,11 @@ __host__ __device__ inline void r9_trace(const KRoute& g, const uint4* rec, cons
         if (r < 0) st = 3;
         sm = w.s + r9_seg(w.vx, w.vy, gx, gy);
         count = w.count;
+    }
+    if (J) {
+        if (st) gx = sx, gy = sy, gi = -1;
+        if (vertices) vertices[q] = st ? 0 : count > 2 ? count : 2;
+        if (goal_out) goal_out[q] = gi;
     }
     out[0] = sx, out[1] = sy;
     out[2 * (N + 1)] = gx, out[2 * (N + 1) + 1] = gy;

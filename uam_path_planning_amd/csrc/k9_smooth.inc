@@ -61,8 +61,11 @@ struct R9sQuery {
     int32_t scell, gcell;
     const uint8_t* nf;
     int st;
+    int32_t gi;  // the goal index (J: the start cell's owner, -1 for a nonzero status)
 };
 
+// J (a joint field): r9_trace<true>'s rules, the start's blocking from the bits
+template <bool J = false>
 __host__ __device__ inline R9sQuery r9s_query(const KRoute& g, const uint32_t* bits,
                                               const uint8_t* next, const double* goals,
                                               int32_t n_goals, const double* starts,
@@ -73,7 +76,28 @@ __host__ __device__ inline R9sQuery r9s_query(const KRoute& g, const uint32_t* b
     u.scell = u.gcell = -1;
     u.nf = next;
     u.st = 0;
+    if (J) {
+        u.gi = -1;
+        u.scell = r9_cell(g, u.sx, u.sy);
+        if (u.scell < 0 || !r9s_free(bits, r9s_wpr(g.nx), u.scell % g.nx, u.scell / g.nx)) {
+            u.st = 1;
+        } else if (u.nf[u.scell] == 255) {
+            u.st = 2;
+        } else {
+            const int32_t o = goal_idx[u.scell];
+            if (o >= 0 && o < n_goals)
+                u.gcell = r9_cell(g, goals[2 * (int64_t)o], goals[2 * (int64_t)o + 1]);
+            if (u.gcell < 0) {
+                u.st = 3;
+            } else {
+                u.gi = o;
+                u.gx = goals[2 * (int64_t)o], u.gy = goals[2 * (int64_t)o + 1];
+            }
+        }
+        return u;
+    }
     const int32_t gi = goal_idx[q];
+    u.gi = gi;
     if (gi < 0 || gi >= n_goals) {
         u.st = 4;
     } else {
@@ -149,12 +173,14 @@ __host__ __device__ __forceinline__ int r9s_hop(const KRoute& g, int k, int32_t*
 }
 
 // ---- host twin ------------------------------------------------------------------------------
+template <bool J = false>
 inline void r9s_smooth_host(const KRoute& g, const uint32_t* bits, const uint8_t* next,
                             const double* goals, int32_t n_goals, const double* starts,
                             const int32_t* goal_idx, int64_t q, int32_t N, int32_t span,
                             double* wp, int32_t* status, int32_t* steps, int32_t* vertices,
-                            std::vector<int32_t>& cells, std::vector<int32_t>& anchors) {
-    R9sQuery u = r9s_query(g, bits, next, goals, n_goals, starts, goal_idx, q);
+                            std::vector<int32_t>& cells, std::vector<int32_t>& anchors,
+                            int32_t* goal_out = nullptr) {
+    R9sQuery u = r9s_query<J>(g, bits, next, goals, n_goals, starts, goal_idx, q);
     double* out = wp + q * (int64_t)(N + 2) * 2;
     cells.clear();
     anchors.clear();
@@ -168,6 +194,10 @@ inline void r9s_smooth_host(const KRoute& g, const uint32_t* bits, const uint8_t
             }
             cells.push_back(cell);
         }
+    }
+    if (J) {
+        if (u.st) u.gx = u.sx, u.gy = u.sy, u.gi = -1;
+        if (goal_out) goal_out[q] = u.gi;
     }
     out[0] = u.sx, out[1] = u.sy;
     out[2 * (N + 1)] = u.gx, out[2 * (N + 1) + 1] = u.gy;
@@ -310,27 +340,27 @@ __device__ inline int32_t r9s_pass(const KRoute& g, const uint32_t* __restrict__
     return na;
 }
 
-__global__ __launch_bounds__(R9S_WAVES * 64) void k_route_smooth(
-    KRoute g, const uint32_t* __restrict__ bits, const uint8_t* __restrict__ next,
+// One wave's query, k_route_smooth's body and (J, a joint field: r9s_query<true>'s rules and
+// goal_out) k_route_joint_smooth's.  ring and list are the wave's LDS.
+template <bool J>
+__device__ __forceinline__ void r9s_smooth_wave(
+    const KRoute& g, const uint32_t* __restrict__ bits, const uint8_t* __restrict__ next,
     const double* __restrict__ goals, int32_t n_goals, const double* __restrict__ starts,
-    const int32_t* __restrict__ goal_idx, int64_t n_queries, int32_t N, int32_t span,
+    const int32_t* __restrict__ goal_idx, int64_t q, int32_t N, int32_t span,
     double* __restrict__ wp, int32_t* __restrict__ status, int32_t* __restrict__ steps,
-    int32_t* __restrict__ vertices) {
-    __shared__ int32_t s_ring[R9S_WAVES][R9S_RING];
-    __shared__ int32_t s_list[R9S_WAVES][R9S_LIST];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    const int64_t q = (int64_t)blockIdx.x * R9S_WAVES + wave;
-    if (q >= n_queries) return;  // whole waves leave; no workgroup barrier below
-    int32_t* ring = s_ring[wave];
-    int32_t* list = s_list[wave];
-    R9sQuery u = r9s_query(g, bits, next, goals, n_goals, starts, goal_idx, q);
+    int32_t* __restrict__ vertices, int32_t* __restrict__ goal_out, int32_t* ring, int32_t* list,
+    int lane) {
+    R9sQuery u = r9s_query<J>(g, bits, next, goals, n_goals, starts, goal_idx, q);
     double* out = wp + q * (int64_t)(N + 2) * 2;
     int32_t n = 0, na = 0;
     R9sPath p{u.sx, u.sy, 0.0, 0.0, (double)(N + 1), 1, N, nullptr, false};
     if (!u.st) {
         na = r9s_pass(g, bits, u, span, ring, list, p, &n, lane);
         if (na < 0) u.st = 3;
+    }
+    if (J) {
+        if (u.st) u.gx = u.sx, u.gy = u.sy, u.gi = -1;
+        if (goal_out && lane == 0) goal_out[q] = u.gi;
     }
     if (lane == 0) {
         out[0] = u.sx, out[1] = u.sy;
@@ -356,4 +386,20 @@ __global__ __launch_bounds__(R9S_WAVES * 64) void k_route_smooth(
         (void)r9s_pass(g, bits, u, span, ring, nullptr, e, &n, lane);
     }
     r9s_vertex(e, u.gx, u.gy, true);
+}
+
+__global__ __launch_bounds__(R9S_WAVES * 64) void k_route_smooth(
+    KRoute g, const uint32_t* __restrict__ bits, const uint8_t* __restrict__ next,
+    const double* __restrict__ goals, int32_t n_goals, const double* __restrict__ starts,
+    const int32_t* __restrict__ goal_idx, int64_t n_queries, int32_t N, int32_t span,
+    double* __restrict__ wp, int32_t* __restrict__ status, int32_t* __restrict__ steps,
+    int32_t* __restrict__ vertices) {
+    __shared__ int32_t s_ring[R9S_WAVES][R9S_RING];
+    __shared__ int32_t s_list[R9S_WAVES][R9S_LIST];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int64_t q = (int64_t)blockIdx.x * R9S_WAVES + wave;
+    if (q >= n_queries) return;  // whole waves leave; no workgroup barrier below
+    r9s_smooth_wave<false>(g, bits, next, goals, n_goals, starts, goal_idx, q, N, span, wp, status,
+                           steps, vertices, nullptr, s_ring[wave], s_list[wave], lane);
 }

@@ -6144,6 +6144,10 @@ __global__ __launch_bounds__(1024) void k_g_final(KParams p, KGrp kg, KOut out,
 #include "k9_route.inc"
 // K9b / K9s: any-angle shortcuts on the traced route, k_route_free_bits, k_route_smooth
 #include "k9_smooth.inc"
+// K9j: the joint route field of many goals, k_route_joint_clear, k_route_joint_seed,
+// k_route_joint_next, k_route_joint_mark, k_route_joint_parent, k_owner_jump, k_owner_final,
+// k_route_joint_trace, k_route_joint_smooth
+#include "k9_joint.inc"
 // K9v: route seeds in the volume, k_route3_cost, k_route3_mask, k_route3_init, k_route3_relax,
 // k_route3_next, k_route3_trace
 #include "k9v_route.inc"
@@ -9050,6 +9054,42 @@ int64_t uam_route_workspace_bytes(const uam_raster_desc* desc, const uam_route_p
 
 int64_t uam_route_visits(const uam_ctx* ctx) { return ctx ? ctx->route_visits : 0; }
 
+// The relaxation rounds of one field from its start state (list 0, ctl[0]) to convergence: one
+// k_route_relax launch per round over the active tiles, the host reading the next round's count
+// after each.  what names the field in the max_rounds message.
+static int route_relax_rounds(uam_ctx* ctx, hipStream_t s, const double* c, double* d,
+                              const KRoute& g, int T, int inner, int ntx, int nty, uint32_t* flags,
+                              int32_t* lists, int32_t* ctl, int64_t max_rounds, const char* what,
+                              int64_t* rounds) {
+    const int nt = ntx * nty;
+    int cur = 0;
+    for (int64_t r = 0;; ++r) {
+        // the active tiles of this round (the one word the host waits for)
+        HIP_TRY(hipMemcpyAsync(ctx->h_route, ctl + cur, sizeof(int32_t), hipMemcpyDeviceToHost,
+                               s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const int32_t n = *(volatile int32_t*)ctx->h_route;
+        if (n < 0 || n > nt)
+            return fail(UAM_E_HIP, "route field: active-tile count %d outside [0, %d]", n, nt);
+        if (n == 0) break;
+        if (r >= max_rounds)
+            return fail(UAM_E_STATE,
+                        "route field %s has not converged within max_rounds = %lld "
+                        "rounds (%d tiles still active)", what, (long long)max_rounds, n);
+        if (T == 16)
+            route_relax_launch<16>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
+        else if (T == 32)
+            route_relax_launch<32>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
+        else
+            route_relax_launch<64>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
+        HIP_TRY(hipGetLastError());
+        ++*rounds;
+        ctx->route_visits += n;
+        cur ^= 1;
+    }
+    return UAM_OK;
+}
+
 int uam_route_field(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
                     const uam_route_params* params, const double* goals, int32_t n_goals,
                     double* dist, uint8_t* next, void* workspace, int64_t workspace_bytes,
@@ -9095,31 +9135,11 @@ int uam_route_field(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
         hipLaunchKernelGGL(k_route_init, dim3(grid), dim3(R9_THREADS), 0, s, c, g, goal, d, T, ntx,
                            nt, flags, lists, ctl);
         HIP_TRY(hipGetLastError());
-        int cur = 0;
-        for (int64_t r = 0;; ++r) {
-            // the active tiles of this round (the one word the host waits for)
-            HIP_TRY(hipMemcpyAsync(ctx->h_route, ctl + cur, sizeof(int32_t),
-                                   hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            const int32_t n = *(volatile int32_t*)ctx->h_route;
-            if (n < 0 || n > nt)
-                return fail(UAM_E_HIP, "route field: active-tile count %d outside [0, %d]", n, nt);
-            if (n == 0) break;
-            if (r >= max_rounds)
-                return fail(UAM_E_STATE,
-                            "route field of goal %d has not converged within max_rounds = %lld "
-                            "rounds (%d tiles still active)", gi, (long long)max_rounds, n);
-            if (T == 16)
-                route_relax_launch<16>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
-            else if (T == 32)
-                route_relax_launch<32>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
-            else
-                route_relax_launch<64>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
-            HIP_TRY(hipGetLastError());
-            ++rounds;
-            ctx->route_visits += n;
-            cur ^= 1;
-        }
+        char what[32];
+        snprintf(what, sizeof what, "of goal %d", gi);
+        if ((st = route_relax_rounds(ctx, s, c, d, g, T, inner, ntx, nty, flags, lists, ctl,
+                                     max_rounds, what, &rounds)))
+            return st;
         hipLaunchKernelGGL(k_route_next, dim3(grid), dim3(R9_THREADS), 0, s, c, d, g, goal,
                            next + (int64_t)gi * cells);
         HIP_TRY(hipGetLastError());
@@ -9184,6 +9204,180 @@ int uam_route_paths_host(const uam_raster_desc* desc, const void* rec,
     for (int64_t q = 0; q < n_queries; ++q)
         r9_trace(g, (const uint4*)rec, next, goals, n_goals, starts, goal_idx, q, N, wp, status,
                  steps);
+    return UAM_OK;
+}
+
+// ---- K9j: the joint route field (k9_joint.inc) ------------------------------------------------
+// parents and owners are int32 and the smoothing kernel forms a + span
+static int route_joint_ok(const KRoute& g, int32_t n_goals) {
+    if (n_goals < 1 || n_goals > R9J_GOALS_MAX)
+        return fail(UAM_E_INVALID, "joint route n_goals %d outside [1, %d]", n_goals,
+                    R9J_GOALS_MAX);
+    if ((int64_t)g.nx * g.ny > (int64_t)INT32_MAX - UAM_ROUTE_SPAN_MAX)
+        return fail(UAM_E_INVALID, "joint route field needs nx*ny <= 2^31 - 1 - %d",
+                    UAM_ROUTE_SPAN_MAX);
+    return UAM_OK;
+}
+
+int64_t uam_route_joint_workspace_bytes(const uam_raster_desc* desc,
+                                        const uam_route_params* params, int32_t n_goals) {
+    KRoute g{};
+    if (route_setup(desc, params, &g) || route_joint_ok(g, n_goals)) return -1;
+    return r9j_workspace(g.nx, g.ny).bytes;
+}
+
+int uam_route_field_joint(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
+                          const uam_route_params* params, const double* goals, int32_t n_goals,
+                          double* dist, uint8_t* next, int32_t* owner, void* workspace,
+                          int64_t workspace_bytes, int32_t* rounds_out, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    KRoute g{};
+    int st = route_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_joint_ok(g, n_goals))) return st;
+    if (!rec || !goals || !dist || !next || !owner || !workspace)
+        return fail(UAM_E_INVALID,
+                    "uam_route_field_joint: rec / goals / dist / next / owner / workspace is NULL");
+    const R9jWs ws = r9j_workspace(g.nx, g.ny);
+    if (workspace_bytes < ws.bytes)
+        return fail(UAM_E_INVALID, "joint route workspace %lld bytes < %lld",
+                    (long long)workspace_bytes, (long long)ws.bytes);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)dist & 7) || ((uintptr_t)owner & 3))
+        return fail(UAM_E_INVALID,
+                    "joint route workspace not 256-B, dist not 8-B or owner not 4-B aligned");
+    DeviceGuard dg(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int T = ctx->k9_tile, inner = ctx->k9_inner;
+    if (T == 64 &&
+        (st = raise_lds(ctx, k_route_relax<64>, 2 * 66 * 66 * (int)sizeof(double))))
+        return st;
+    if (!ctx->h_route) HIP_TRY(hipHostMalloc((void**)&ctx->h_route, 64, hipHostMallocDefault));
+    char* base = (char*)workspace;
+    double* c = (double*)(base + ws.field.c_off);
+    uint32_t* flags = (uint32_t*)(base + ws.field.flags_off);
+    int32_t* lists = (int32_t*)(base + ws.field.lists_off);
+    int32_t* ctl = (int32_t*)(base + ws.field.ctl_off);
+    int32_t* parent = (int32_t*)(base + ws.parent_off);
+    const int ntx = r9_tiles(g.nx, T), nty = r9_tiles(g.ny, T), nt = ntx * nty;
+    const int64_t cells = (int64_t)g.nx * g.ny;
+    const int64_t max_rounds = params->max_rounds ? params->max_rounds : cells;
+    const int grid = grid_for(cells, R9_THREADS, 1 << 16);
+    const int ggrid = (n_goals + R9_THREADS - 1) / R9_THREADS;
+    ctx->last_kernel = "K9j";
+    ctx->route_visits = 0;
+    hipLaunchKernelGGL(k_route_cost, dim3(grid), dim3(R9_THREADS), 0, s, (const uint4*)rec, g, c);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route_joint_clear, dim3(grid), dim3(R9_THREADS), 0, s, g, dist, nt, flags,
+                       ctl);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route_joint_seed, dim3(ggrid), dim3(R9_THREADS), 0, s, c, g, goals,
+                       n_goals, dist, T, ntx, flags, lists, ctl);
+    HIP_TRY(hipGetLastError());
+    int64_t rounds = 0;
+    if ((st = route_relax_rounds(ctx, s, c, dist, g, T, inner, ntx, nty, flags, lists, ctl,
+                                 max_rounds, "of the goals jointly", &rounds)))
+        return st;
+    hipLaunchKernelGGL(k_route_joint_next, dim3(grid), dim3(R9_THREADS), 0, s, c, dist, g, next,
+                       owner);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route_joint_mark, dim3(ggrid), dim3(R9_THREADS), 0, s, c, g, goals,
+                       n_goals, next, owner);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route_joint_parent, dim3(grid), dim3(R9_THREADS), 0, s, g, next, parent,
+                       owner);
+    HIP_TRY(hipGetLastError());
+    for (int r = r9j_jumps(cells); r > 0; --r) {
+        hipLaunchKernelGGL(k_owner_jump, dim3(grid), dim3(R9_THREADS), 0, s, parent, cells);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_owner_final, dim3(grid), dim3(R9_THREADS), 0, s, parent, owner, cells);
+    HIP_TRY(hipGetLastError());
+    if (rounds_out) *rounds_out = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
+    return UAM_OK;
+}
+
+static int route_paths_joint_ok(const KRoute& g, int32_t n_goals, int64_t n_queries,
+                                int32_t span) {
+    const int st = route_joint_ok(g, n_goals);
+    if (st) return st;
+    if (n_queries < 0) return fail(UAM_E_INVALID, "route n_queries < 0");
+    if (span < 0 || span > UAM_ROUTE_SPAN_MAX)
+        return fail(UAM_E_INVALID, "joint route span %d outside [0, %d]", span,
+                    UAM_ROUTE_SPAN_MAX);
+    return UAM_OK;
+}
+
+int uam_route_paths_joint(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
+                          const uam_route_params* params, const uint32_t* bits,
+                          const uint8_t* next, const int32_t* owner, const double* goals,
+                          int32_t n_goals, const double* starts, int64_t n_queries, int32_t span,
+                          double* wp, int32_t* status, int32_t* steps, int32_t* vertices,
+                          int32_t* goal_out, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
+    KRoute g{};
+    int st = route_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_paths_joint_ok(g, n_goals, n_queries, span))) return st;
+    if (n_queries == 0) return UAM_OK;
+    if (!(span ? (const void*)bits : rec) || !next || !owner || !goals || !starts || !wp ||
+        !status)
+        return fail(UAM_E_INVALID, "uam_route_paths_joint: a buffer is NULL");
+    const int per = span ? R9S_WAVES : R9_THREADS;
+    if (n_queries >= ((int64_t)1 << 31) * per)
+        return fail(UAM_E_INVALID, "route n_queries too large");
+    DeviceGuard dg(ctx->device);
+    const int64_t blocks = (n_queries + per - 1) / per;
+    if (span)
+        hipLaunchKernelGGL(k_route_joint_smooth, dim3((unsigned)blocks), dim3(R9S_WAVES * 64), 0,
+                           (hipStream_t)stream, g, bits, next, owner, goals, n_goals, starts,
+                           n_queries, ctx->kp.N, span, wp, status, steps, vertices, goal_out);
+    else
+        hipLaunchKernelGGL(k_route_joint_trace, dim3((unsigned)blocks), dim3(R9_THREADS), 0,
+                           (hipStream_t)stream, g, (const uint4*)rec, next, owner, goals, n_goals,
+                           starts, n_queries, ctx->kp.N, wp, status, steps, vertices, goal_out);
+    HIP_TRY(hipGetLastError());
+    ctx->last_kernel = span ? "K9js" : "K9jt";
+    return UAM_OK;
+}
+
+int uam_route_field_joint_host(const uam_raster_desc* desc, const void* rec,
+                               const uam_route_params* params, const double* goals,
+                               int32_t n_goals, double* dist, uint8_t* next, int32_t* owner) {
+    KRoute g{};
+    int st = route_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_joint_ok(g, n_goals))) return st;
+    if (!rec || !goals || !dist || !next || !owner)
+        return fail(UAM_E_INVALID,
+                    "uam_route_field_joint_host: rec / goals / dist / next / owner is NULL");
+    r9j_field_host(g, (const uint4*)rec, goals, n_goals, dist, next, owner);
+    return UAM_OK;
+}
+
+int uam_route_paths_joint_host(const uam_raster_desc* desc, const void* rec,
+                               const uam_route_params* params, const uint32_t* bits,
+                               const uint8_t* next, const int32_t* owner, const double* goals,
+                               int32_t n_goals, const double* starts, int64_t n_queries,
+                               int32_t N, int32_t span, double* wp, int32_t* status,
+                               int32_t* steps, int32_t* vertices, int32_t* goal_out) {
+    KRoute g{};
+    int st = route_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_paths_joint_ok(g, n_goals, n_queries, span))) return st;
+    if (N < 0) return fail(UAM_E_INVALID, "route N < 0");
+    if (n_queries == 0) return UAM_OK;
+    if (!(span ? (const void*)bits : rec) || !next || !owner || !goals || !starts || !wp ||
+        !status)
+        return fail(UAM_E_INVALID, "uam_route_paths_joint_host: a buffer is NULL");
+    std::vector<int32_t> cells, anchors;
+    for (int64_t q = 0; q < n_queries; ++q)
+        if (span)
+            r9s_smooth_host<true>(g, bits, next, goals, n_goals, starts, owner, q, N, span, wp,
+                                  status, steps, vertices, cells, anchors, goal_out);
+        else
+            r9_trace<true>(g, (const uint4*)rec, next, goals, n_goals, starts, owner, q, N, wp,
+                           status, steps, vertices, goal_out);
     return UAM_OK;
 }
 

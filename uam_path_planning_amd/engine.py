@@ -159,7 +159,10 @@ class RouteField:
     blocking is read from rec).  Device tensors from route_field, numpy arrays from
     route_field_host.  A derived, untracked product of rec: rebuild it when rec changes.
     free_bits: the free cells as one bit per cell ([ny, (nx + 31) // 32] 32-bit words;
-    Engine.route_free_bits), built and kept here by the first route_paths(..., smooth >= 1)."""
+    Engine.route_free_bits), built and kept here by the first route_paths(..., smooth >= 1).
+    joint = True (route_field(..., joint=True), K9j; "Route seeds, joint field"): one field to the
+    nearest of the goals, dist and next [1, ny, nx] (8 at every valid goal's cell), and owner
+    [ny, nx] int32: the index of the goal a cell's route ends at, -1 where there is none."""
     geo: RasterGeo
     goals: object = field(repr=False)
     dist: object = field(repr=False)
@@ -171,6 +174,8 @@ class RouteField:
     block_flags: int = _lib.FLAG_NFZ
     inflate: int = 0
     free_bits: object = field(default=None, repr=False)
+    owner: object = field(default=None, repr=False)
+    joint: bool = False
 
     def params(self, max_rounds=0):
         return _route_params(self.lam, self.block_flags, self.inflate, max_rounds)
@@ -902,18 +907,36 @@ class Engine:
 
     # -- route seeds (K9) -------------------------------------------------------------------
     def route_field(self, raster, goals, lam=1.0, block_flags=_lib.FLAG_NFZ, inflate=0,
-                    max_rounds=0):
+                    max_rounds=0, joint=False):
         """The cost-to-go fields of goals [G, 2] on raster (uam_route_field): a per-goal setup
         product like the packed copy -- the call waits for the stream between its rounds.  Cell
         cost 1 + lam * phi, cells with a block_flags bit (or a non-finite or non-positive cost)
         blocked, inflate cells of clearance around them; max_rounds 0 = nx*ny.  Returns a
-        RouteField; raises UamError when a field has not converged within max_rounds."""
+        RouteField; raises UamError when a field has not converged within max_rounds.
+        joint=True (uam_route_field_joint, K9j): one field to the nearest of the goals in one
+        relaxation -- dist and next [1, ny, nx] and owner [ny, nx], the goal each cell's route
+        ends at -- for the time and memory of about one goal."""
         torch = _torch()
         geo = raster.geo
         g = self.tensor(goals, torch.float64).reshape(-1, 2)
         G = g.shape[0]
         rp = _route_params(lam, block_flags, inflate, max_rounds)
         gs = geo.as_struct()
+        if joint:
+            nbytes = self.lib.uam_route_joint_workspace_bytes(ctypes.byref(gs), ctypes.byref(rp),
+                                                              G)
+            ws = None if nbytes < 0 else self.empty(((nbytes + 255) // 256, 256), torch.uint8)
+            dist = self.empty((1, geo.ny, geo.nx), torch.float64)
+            nxt = self.empty((1, geo.ny, geo.nx), torch.uint8)
+            owner = self.empty((geo.ny, geo.nx), torch.int32)
+            rounds = ctypes.c_int32()
+            _lib.check(self.lib.uam_route_field_joint(
+                self._ctx, ctypes.byref(gs), _ptr(raster.rec), ctypes.byref(rp), _ptr(g), G,
+                _ptr(dist), _ptr(nxt), _ptr(owner), _ptr(ws), max(nbytes, 0),
+                ctypes.byref(rounds), self.stream), "uam_route_field_joint")
+            return RouteField(geo, g, dist, nxt, rounds.value,
+                              int(self.lib.uam_route_visits(self._ctx)), raster.rec, float(lam),
+                              int(block_flags), int(inflate), None, owner, True)
         nbytes = self.lib.uam_route_workspace_bytes(ctypes.byref(gs), ctypes.byref(rp))
         ws = None if nbytes < 0 else self.empty(((nbytes + 255) // 256, 256), torch.uint8)
         dist = self.empty((G, geo.ny, geo.nx), torch.float64)
@@ -942,7 +965,7 @@ class Engine:
             field.free_bits = bits
         return field.free_bits
 
-    def route_paths(self, field, starts, goal_idx, smooth=0):
+    def route_paths(self, field, starts, goal_idx=None, smooth=0):
         """Seed paths through a RouteField (uam_route_paths): starts [Q, 2], goal_idx [Q] into
         field.goals.  Returns {"wp" [Q, N+2, 2], "status" [Q], "steps" [Q]} (device tensors);
         status 0 ok, 1 start off the raster or blocked, 2 goal unreachable, 3 walk too long,
@@ -951,9 +974,32 @@ class Engine:
         smooth >= 1 (uam_route_paths_smooth, K9s): any-angle shortcuts over at most smooth
         chain cells (1..1024) wherever the cells between lie in straight sight; adds "vertices"
         [Q] (the polyline's vertices, end points included; 0 for a nonzero status).  smooth = 1
-        keeps every cell: the bits of smooth = 0."""
+        keeps every cell: the bits of smooth = 0.
+        A joint field (uam_route_paths_joint) takes no goal_idx: every start goes to the goal
+        that owns its cell, returned as "goal" [Q] (-1 for a nonzero status, which is 1, 2 or 3
+        -- no owner -- and leaves the start point in every waypoint); "vertices" for every
+        smooth."""
         torch = _torch()
         s = self.tensor(starts, torch.float64).reshape(-1, 2)
+        if field.joint:
+            if goal_idx is not None:
+                raise ValueError("a joint RouteField takes no goal_idx")
+            Q = s.shape[0]
+            N = self.params.N
+            out = {"wp": self.empty((Q, N + 2, 2), torch.float64)}
+            for k in ("status", "steps", "vertices", "goal"):
+                out[k] = self.empty((Q,), torch.int32)
+            bits = self.route_free_bits(field) if smooth else None
+            rp = field.params()
+            _lib.check(self.lib.uam_route_paths_joint(
+                self._ctx, ctypes.byref(field.geo.as_struct()), _ptr(field.rec), ctypes.byref(rp),
+                _ptr(bits), _ptr(field.next), _ptr(field.owner), _ptr(field.goals),
+                field.goals.shape[0], _ptr(s), Q, int(smooth), _ptr(out["wp"]),
+                _ptr(out["status"]), _ptr(out["steps"]), _ptr(out["vertices"]), _ptr(out["goal"]),
+                self.stream), "uam_route_paths_joint")
+            return out
+        if goal_idx is None:
+            raise ValueError("a per-goal RouteField needs goal_idx")
         gi = self.tensor(goal_idx, torch.int32).reshape(-1)
         Q = s.shape[0]
         if gi.shape[0] != Q:
@@ -979,13 +1025,26 @@ class Engine:
         return out
 
     @staticmethod
-    def route_field_host(geo, rec, goals, lam=1.0, block_flags=_lib.FLAG_NFZ, inflate=0):
+    def route_field_host(geo, rec, goals, lam=1.0, block_flags=_lib.FLAG_NFZ, inflate=0,
+                         joint=False):
         """route_field on the host (uam_route_field_host; needs no GPU): the definition applied
         by the inline functions the kernels run, the minimum by a heap Dijkstra.  rec: numpy
-        [ny, nx, 4] 32-bit words.  Returns a RouteField of numpy arrays (rounds 0)."""
+        [ny, nx, 4] 32-bit words.  Returns a RouteField of numpy arrays (rounds 0).  joint=True:
+        uam_route_field_joint_host, the owner by following the chains."""
         r = _host_rec(rec, geo)
         g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 2)
         G = g.shape[0]
+        if joint:
+            dist = np.empty((1, geo.ny, geo.nx), dtype=np.float64)
+            nxt = np.empty((1, geo.ny, geo.nx), dtype=np.uint8)
+            owner = np.empty((geo.ny, geo.nx), dtype=np.int32)
+            rp = _route_params(lam, block_flags, inflate, 0)
+            _lib.check(_lib.load().uam_route_field_joint_host(
+                ctypes.byref(geo.as_struct()), r.ctypes.data, ctypes.byref(rp), g.ctypes.data, G,
+                dist.ctypes.data, nxt.ctypes.data, owner.ctypes.data),
+                "uam_route_field_joint_host")
+            return RouteField(geo, g, dist, nxt, 0, 0, r, float(lam), int(block_flags),
+                              int(inflate), None, owner, True)
         dist = np.empty((G, geo.ny, geo.nx), dtype=np.float64)
         nxt = np.empty((G, geo.ny, geo.nx), dtype=np.uint8)
         rp = _route_params(lam, block_flags, inflate, 0)
@@ -1009,11 +1068,36 @@ class Engine:
         return field.free_bits
 
     @staticmethod
-    def route_paths_host(field, starts, goal_idx, N, smooth=0):
+    def route_paths_host(field, starts, goal_idx=None, N=None, smooth=0):
         """route_paths on the host (uam_route_paths_host; needs no GPU) for a RouteField of
         numpy arrays; N interior waypoints.  Returns {"wp", "status", "steps"} numpy arrays,
-        and "vertices" for smooth >= 1 (uam_route_paths_smooth_host)."""
+        and "vertices" for smooth >= 1 (uam_route_paths_smooth_host).  A joint field
+        (uam_route_paths_joint_host) takes goal_idx = None and adds "vertices" and "goal"."""
+        if N is None:
+            raise ValueError("route_paths_host needs N")
         s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 2)
+        if field.joint:
+            if goal_idx is not None:
+                raise ValueError("a joint RouteField takes no goal_idx")
+            Q, N = s.shape[0], int(N)
+            out = {"wp": np.empty((Q, max(N, 0) + 2, 2), dtype=np.float64)}
+            for k in ("status", "steps", "vertices", "goal"):
+                out[k] = np.empty((Q,), dtype=np.int32)
+            rp = field.params()
+            nxt = np.ascontiguousarray(field.next, dtype=np.uint8)
+            own = np.ascontiguousarray(field.owner, dtype=np.int32)
+            goals = np.ascontiguousarray(field.goals, dtype=np.float64)
+            bits = Engine.route_free_bits_host(field) if smooth else None
+            _lib.check(_lib.load().uam_route_paths_joint_host(
+                ctypes.byref(field.geo.as_struct()), _host_rec(field.rec, field.geo).ctypes.data,
+                ctypes.byref(rp), bits.ctypes.data if smooth else None, nxt.ctypes.data,
+                own.ctypes.data, goals.ctypes.data, goals.shape[0], s.ctypes.data, Q, N,
+                int(smooth), out["wp"].ctypes.data, out["status"].ctypes.data,
+                out["steps"].ctypes.data, out["vertices"].ctypes.data, out["goal"].ctypes.data),
+                "uam_route_paths_joint_host")
+            return out
+        if goal_idx is None:
+            raise ValueError("a per-goal RouteField needs goal_idx")
         gi = np.ascontiguousarray(goal_idx, dtype=np.int32).reshape(-1)
         Q = s.shape[0]
         if gi.shape[0] != Q:

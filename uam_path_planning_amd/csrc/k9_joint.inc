@@ -159,7 +159,7 @@ __global__ __launch_bounds__(R9_THREADS) void k_route_joint_trace(
                        vertices, goal_out);
 }
 
-// one wave per query: the goal resolved from the owner plane, then K9s' body
+// one wave per query: the goal resolved from the owner plane, then the smoothing's one body
 __global__ __launch_bounds__(R9S_WAVES * 64) void k_route_joint_smooth(
     KRoute g, const uint32_t* __restrict__ bits, const uint8_t* __restrict__ next,
     const int32_t* __restrict__ owner, const double* __restrict__ goals, int32_t n_goals,
@@ -172,8 +172,8 @@ __global__ __launch_bounds__(R9S_WAVES * 64) void k_route_joint_smooth(
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * R9S_WAVES + wave;
     if (q >= n_queries) return;  // whole waves leave; no workgroup barrier below
-    r9s_smooth_wave<true>(g, bits, next, goals, n_goals, starts, owner, q, N, span, wp, status,
-                          steps, vertices, goal_out, s_ring[wave], s_list[wave], lane);
+    r9_smooth_wave<true>(g, bits, next, goals, n_goals, starts, owner, q, N, span, wp, status,
+                         steps, vertices, goal_out, s_ring[wave], s_list[wave], lane);
 }
 
 // ---- host side ------------------------------------------------------------------------------
@@ -197,7 +197,7 @@ inline int r9j_jumps(int64_t n) {
     return r;
 }
 
-// The host twin: the cost plane by r9_cost, a heap Dijkstra seeded with every valid goal's cell,
+// The host twin: the cost plane by r9_cost, r9_dijkstra seeded with every valid goal's cell,
 // r9_next with the goal cells marked afterwards, and the owner by following each chain to its end
 // (a cell met again on the walk under way closes a cycle: -1 for the walk's cells).
 inline void r9j_field_host(const KRoute& g, const uint4* rec, const double* goals, int32_t n_goals,
@@ -210,9 +210,6 @@ inline void r9j_field_host(const KRoute& g, const uint4* rec, const double* goal
         owner[i] = R9J_NO_GOAL;
     }
     std::vector<std::pair<double, int32_t>> heap;
-    auto later = [](const std::pair<double, int32_t>& a, const std::pair<double, int32_t>& b) {
-        return a.first > b.first;
-    };
     for (int32_t gi = 0; gi < n_goals; ++gi) {
         const int32_t gcell = r9j_goal_cell(g, c.data(), goals, gi);
         if (gcell < 0) continue;
@@ -222,27 +219,7 @@ inline void r9j_field_host(const KRoute& g, const uint4* rec, const double* goal
             heap.emplace_back(0.0, gcell);
         }
     }
-    // every entry is 0.0: a heap already
-    while (!heap.empty()) {
-        std::pop_heap(heap.begin(), heap.end(), later);
-        const auto top = heap.back();
-        heap.pop_back();
-        const int32_t u = top.second;
-        if (top.first > dist[u]) continue;
-        const int ux = u % g.nx, uy = u / g.nx;
-        for (int k = 0; k < 8; ++k) {
-            const int vx = ux + r9_dix(k), vy = uy + r9_diy(k);
-            if (vx < 0 || vx >= g.nx || vy < 0 || vy >= g.ny) continue;
-            const int64_t v = (int64_t)vy * g.nx + vx;
-            if (!(c[(size_t)v] < r9_inf())) continue;
-            const double t = r9_candidate(g, c.data(), dist, vx, vy, c[(size_t)v], (k + 4) & 7);
-            if (t < dist[v]) {
-                dist[v] = t;
-                heap.emplace_back(t, (int32_t)v);
-                std::push_heap(heap.begin(), heap.end(), later);
-            }
-        }
-    }
+    r9_dijkstra(heap, dist, [&](int32_t u, auto visit) { r9_edges(g, c.data(), dist, u, visit); });
     for (int64_t i = 0; i < n; ++i)
         next[i] = owner[i] != R9J_NO_GOAL
                       ? (uint8_t)8

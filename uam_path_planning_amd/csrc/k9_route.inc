@@ -2,6 +2,11 @@
 // the seed paths traced through it (include/uampath.h "Route seeds").  k_route_cost,
 // k_route_init, k_route_relax<T>, k_route_next, k_route_trace, and the __host__ __device__
 // pieces of the definition they share with uam_route_field_host / uam_route_paths_host.
+// Also what the whole K9 family shares, written over the grid type G (KRoute here, KRoute3 in
+// k9v_route.inc) and reaching the grid only through the overloads of "the grid vocabulary":
+// the query's status tests, the resampling and the trace (r9_query, r9_vertex, r9_walk,
+// r9_trace) and the host twins' Dijkstra (r9_dijkstra).  The float64 operations are the same
+// for both grids but r9_seg's, in the same order.
 // Included in the anonymous namespace of uampath.hip.
 
 constexpr int R9_THREADS = 256;
@@ -16,6 +21,8 @@ struct KRoute {
     double lambda;
     uint32_t block_flags;
     int32_t inflate;
+    static constexpr int D = 2;     // coordinates of a point
+    static constexpr int GOAL = 8;  // next at the goal's cell
 };
 
 __host__ __device__ __forceinline__ double r9_inf() { return __builtin_huge_val(); }
@@ -105,143 +112,233 @@ __host__ __device__ __forceinline__ uint8_t r9_next(const KRoute& g, const doubl
     return 255;  // not at a fixed point (cannot happen after convergence)
 }
 
-// ---- trace and resample -------------------------------------------------------------------
-// One query: the walk along next from the start's cell to the goal's, twice (the first walk
-// for S_m, the second emits the waypoints; S_i is recomputed identically).
-struct R9Walk {
-    int32_t cell, gcell, count;
-    double vx, vy;  // V_{i-1}
-    double s;       // S_{i-1}
-};
-
-// the next interior vertex of the walk; 0 = the goal cell was reached (no vertex), 1 = a
-// vertex, -1 = the walk left the field (more than nx*ny cells, or a next value that is no
-// direction or leads off the raster: not a field of uam_route_field)
-__host__ __device__ __forceinline__ int r9_step(const KRoute& g, const uint8_t* next, R9Walk& w,
-                                                double* x, double* y) {
-    if (w.cell == w.gcell) return 0;
-    if (w.count >= (int64_t)g.nx * g.ny) return -1;
-    const int k = next[w.cell];
+// ---- the grid vocabulary ---------------------------------------------------------------------
+// What the trace, the smoothing and the host Dijkstra need from a grid, as overloads on KRoute
+// (here and in k9_smooth.inc) and on KRoute3 (k9v_route.inc, k9v_smooth.inc); a cell is the
+// int32 index of a cell or voxel, a point G::D doubles.  G::GOAL is next at the goal's cell.
+__host__ __device__ __forceinline__ int64_t r9_count(const KRoute& g) {
+    return (int64_t)g.nx * g.ny;
+}
+__host__ __device__ __forceinline__ int32_t r9_locate(const KRoute& g, const double* p) {
+    return r9_cell(g, p[0], p[1]);
+}
+// one step of the chain from cell in direction k (count cells visited so far): 1 = moved, -1 =
+// the walk left the field (more than nx*ny cells, or a next value that is no direction or leads
+// off the raster: not a field of uam_route_field)
+__host__ __device__ __forceinline__ int r9_hop(const KRoute& g, int k, int32_t* cell,
+                                               int64_t count) {
+    if (count >= r9_count(g)) return -1;
     if (k > 7) return -1;
-    const int ix = w.cell % g.nx + r9_dix(k), iy = w.cell / g.nx + r9_diy(k);
+    const int ix = *cell % g.nx + r9_dix(k), iy = *cell / g.nx + r9_diy(k);
     if (ix < 0 || ix >= g.nx || iy < 0 || iy >= g.ny) return -1;
-    w.cell = iy * g.nx + ix;
-    ++w.count;
-    if (w.cell == w.gcell) return 0;
-    *x = g.x0 + ((double)ix + 0.5) * g.dx;
-    *y = g.y_top - ((double)iy + 0.5) * g.dy;
+    *cell = iy * g.nx + ix;
     return 1;
 }
-
-__host__ __device__ __forceinline__ double r9_seg(double ax, double ay, double bx, double by) {
-    const double ex = bx - ax, ey = by - ay;
+__host__ __device__ __forceinline__ void r9_centre(const KRoute& g, int32_t cell, double* p) {
+    p[0] = g.x0 + ((double)(cell % g.nx) + 0.5) * g.dx;
+    p[1] = g.y_top - ((double)(cell / g.nx) + 0.5) * g.dy;
+}
+__host__ __device__ __forceinline__ double r9_seg(const KRoute&, const double* a,
+                                                  const double* b) {
+    const double ex = b[0] - a[0], ey = b[1] - a[1];
     return sqrt(ex * ex + ey * ey);
 }
+// the start's blocking as the trace reads it: from the records (the smoothing reads the bits)
+__host__ __device__ __forceinline__ bool r9_start_blocked(const KRoute& g, const uint4* rec,
+                                                          int32_t cell) {
+    return !(r9_cost(g, rec, cell % g.nx, cell / g.nx) < r9_inf());
+}
 
-// J (a joint field, k9_joint.inc): next is the one joint plane, goal_idx the owner plane
-// [ny][nx]; the goal is owner[cell(start)], the status tests are 1, 2, 3 (no owner) and every
-// nonzero status leaves the start point in all waypoints.  vertices and goal_out are written
-// for J alone.
-template <bool J = false>
-__host__ __device__ inline void r9_trace(const KRoute& g, const uint4* rec, const uint8_t* next,
+// ---- trace and resample, on either grid ---------------------------------------------------
+// a query's end points, cells, field and status 4 / 1 / 2 (J: 1 / 2 / 3)
+template <typename G>
+struct R9Query {
+    double s[G::D], t[G::D];  // the start point; the goal point (the start's until one is known)
+    int32_t scell, gcell;
+    const uint8_t* nf;
+    int st;
+    int32_t gi;  // the goal index (J: the start cell's owner, -1 for a nonzero status)
+};
+
+// src says whether the start's cell is blocked (r9_start_blocked): the records or the volume
+// for the trace, the free bits for the smoothing.
+// J (a joint field, k9_joint.inc): next is the one joint plane, goal_idx the owner plane; the
+// goal is owner[cell(start)], the status tests are 1, 2, 3 (no owner: an owner that is no goal
+// of this call is no field of uam_route_field_joint).
+template <bool J = false, typename G, typename Src>
+__host__ __device__ inline R9Query<G> r9_query(const G& g, Src src, const uint8_t* next,
+                                               const double* goals, int32_t n_goals,
+                                               const double* starts, const int32_t* goal_idx,
+                                               int64_t q) {
+    constexpr int D = G::D;
+    R9Query<G> u;
+    // a goal index out of range: every waypoint is the start point
+    for (int i = 0; i < D; ++i) u.s[i] = u.t[i] = starts[D * q + i];
+    u.scell = u.gcell = -1;
+    u.nf = next;
+    u.st = 0;
+    if (J) {
+        u.gi = -1;
+        u.scell = r9_locate(g, u.s);
+        if (u.scell < 0 || r9_start_blocked(g, src, u.scell)) {
+            u.st = 1;
+        } else if (u.nf[u.scell] == 255) {
+            u.st = 2;
+        } else {
+            const int32_t o = goal_idx[u.scell];
+            if (o >= 0 && o < n_goals) u.gcell = r9_locate(g, goals + D * (int64_t)o);
+            if (u.gcell < 0) {
+                u.st = 3;
+            } else {
+                u.gi = o;
+                for (int i = 0; i < D; ++i) u.t[i] = goals[D * (int64_t)o + i];
+            }
+        }
+        return u;
+    }
+    const int32_t gi = goal_idx[q];
+    u.gi = gi;
+    if (gi < 0 || gi >= n_goals) {
+        u.st = 4;
+    } else {
+        for (int i = 0; i < D; ++i) u.t[i] = goals[D * (int64_t)gi + i];
+        u.nf = next + (int64_t)gi * r9_count(g);
+        u.gcell = r9_locate(g, u.t);
+        if (u.gcell < 0 || u.nf[u.gcell] != G::GOAL) u.st = 4;
+    }
+    if (!u.st) {
+        u.scell = r9_locate(g, u.s);
+        if (u.scell < 0 || r9_start_blocked(g, src, u.scell)) u.st = 1;
+    }
+    if (!u.st && u.nf[u.scell] == 255) u.st = 2;
+    return u;
+}
+
+// A query's fixed outputs once its walk is done: J with a nonzero status leaves the start point
+// as the goal and no goal index; then (write: the lane that stores them) the two end points,
+// the status, steps = n and vertices = nv (0 for a nonzero status), the goal index.
+template <bool J, typename G>
+__host__ __device__ inline void r9_ends(R9Query<G>& u, int64_t q, int32_t N, double* out,
+                                        int32_t* status, int32_t* steps, int32_t n,
+                                        int32_t* vertices, int32_t nv, int32_t* goal_out,
+                                        bool write) {
+    constexpr int D = G::D;
+    if (J && u.st) {
+        for (int i = 0; i < D; ++i) u.t[i] = u.s[i];
+        u.gi = -1;
+    }
+    if (!write) return;
+    for (int i = 0; i < D; ++i) out[i] = u.s[i], out[D * (N + 1) + i] = u.t[i];
+    status[q] = u.st;
+    if (steps) steps[q] = u.st ? 0 : n;
+    if (vertices) vertices[q] = u.st ? 0 : nv;
+    if (goal_out) goal_out[q] = u.gi;
+}
+
+// the straight line of a nonzero status: waypoints j0, j0 + stride, ..
+template <typename G>
+__host__ __device__ inline void r9_straight(const R9Query<G>& u, int32_t N, double* out, int j0,
+                                            int stride) {
+    constexpr int D = G::D;
+    const double dn1 = (double)(N + 1);
+    for (int j = j0; j <= N; j += stride) {
+        const double f = (double)j / dn1;
+        for (int i = 0; i < D; ++i) out[D * j + i] = u.s[i] + (u.t[i] - u.s[i]) * f;
+    }
+}
+
+// The vertices V_1, V_2, .. of a path taken one after the other: pass 1 (out NULL) sums S_m,
+// pass 2 (sm known) places the waypoints: waypoint j lies on the first segment i (not before
+// the previous waypoint's) with S_i > t_j, on the last one when there is none.
+template <int D>
+struct R9Path {
+    double v[D];  // V_{i-1}
+    double s;     // S_{i-1}
+    double sm, dn1;
+    int32_t j, N;
+    double* out;  // NULL: pass 1
+    bool write;   // this lane stores the waypoints
+};
+
+template <int D>
+__host__ __device__ __forceinline__ R9Path<D> r9_path(const double* start, double sm, int32_t N,
+                                                      double* out, bool write) {
+    R9Path<D> p;
+    for (int i = 0; i < D; ++i) p.v[i] = start[i];
+    p.s = 0.0, p.sm = sm, p.dn1 = (double)(N + 1);
+    p.j = 1, p.N = N;
+    p.out = out, p.write = write;
+    return p;
+}
+
+template <typename G>
+__host__ __device__ inline void r9_vertex(const G& g, R9Path<G::D>& p, const double* x,
+                                          bool last) {
+    constexpr int D = G::D;
+    const double si = p.s + r9_seg(g, p.v, x);
+    if (p.out) {
+        while (p.j <= p.N) {
+            const double t = p.sm * ((double)p.j / p.dn1);
+            if (!last && !(si > t)) break;
+            const double den = si - p.s;
+            const double u = den > 0.0 ? (t - p.s) / den : 0.0;
+            double w[D];
+            for (int i = 0; i < D; ++i) w[i] = p.v[i] + u * (x[i] - p.v[i]);
+            if (p.write)
+                for (int i = 0; i < D; ++i) p.out[D * p.j + i] = w[i];
+            ++p.j;
+        }
+    }
+    p.s = si;
+    for (int i = 0; i < D; ++i) p.v[i] = x[i];
+}
+
+// the walk along nf from scell to gcell, the centre of every cell between them a vertex of p;
+// the number of cells visited, -1 when the walk left the field
+template <typename G>
+__host__ __device__ inline int64_t r9_walk(const G& g, const uint8_t* nf, int32_t scell,
+                                           int32_t gcell, R9Path<G::D>& p) {
+    int32_t cell = scell;
+    int64_t count = 1;
+    while (cell != gcell) {
+        // the centre and the hop of one cell in one iteration: its index is taken apart once
+        if (count > 1) {
+            double x[G::D];
+            r9_centre(g, cell, x);
+            r9_vertex(g, p, x, false);
+        }
+        if (r9_hop(g, nf[cell], &cell, count) < 0) return -1;
+        ++count;
+    }
+    return count;
+}
+
+// One query: the walk from the start's cell to the goal's, twice (the first for S_m, the second
+// emits the waypoints; S_i is recomputed identically).  vertices and goal_out are written for J
+// alone.
+template <bool J = false, typename G, typename Src>
+__host__ __device__ inline void r9_trace(const G& g, Src src, const uint8_t* next,
                                          const double* goals, int32_t n_goals,
                                          const double* starts, const int32_t* goal_idx,
                                          int64_t q, int32_t N, double* wp, int32_t* status,
                                          int32_t* steps, int32_t* vertices = nullptr,
                                          int32_t* goal_out = nullptr) {
-    const double sx = starts[2 * q], sy = starts[2 * q + 1];
-    int32_t gi = J ? -1 : goal_idx[q];
-    double* out = wp + q * (int64_t)(N + 2) * 2;
-    const double dn1 = (double)(N + 1);
-    double gx = sx, gy = sy;  // a goal index out of range: every waypoint is the start point
-    int st = 0;
-    int32_t gcell = -1, scell = -1;
-    const uint8_t* nf = next;
-    if (J) {
-        scell = r9_cell(g, sx, sy);
-        if (scell < 0 || !(r9_cost(g, rec, scell % g.nx, scell / g.nx) < r9_inf())) {
-            st = 1;
-        } else if (nf[scell] == 255) {
-            st = 2;
-        } else {
-            gi = goal_idx[scell];
-            // an owner that is no goal of this call is no field of uam_route_field_joint
-            gcell = gi < 0 || gi >= n_goals
-                        ? -1
-                        : r9_cell(g, goals[2 * (int64_t)gi], goals[2 * (int64_t)gi + 1]);
-            if (gcell < 0)
-                st = 3;
-            else
-                gx = goals[2 * (int64_t)gi], gy = goals[2 * (int64_t)gi + 1];
-        }
-    } else {
-        if (gi < 0 || gi >= n_goals) {
-            st = 4;
-        } else {
-            gx = goals[2 * (int64_t)gi], gy = goals[2 * (int64_t)gi + 1];
-            nf = next + (int64_t)gi * g.nx * g.ny;
-            gcell = r9_cell(g, gx, gy);
-            if (gcell < 0 || nf[gcell] != 8) st = 4;
-        }
-        if (!st) {
-            scell = r9_cell(g, sx, sy);
-            if (scell < 0 || !(r9_cost(g, rec, scell % g.nx, scell / g.nx) < r9_inf())) st = 1;
-        }
-        if (!st && nf[scell] == 255) st = 2;
-    }
-    double sm = 0.0;
-    int32_t count = 0;
-    if (!st) {  // first walk: S_m
-        R9Walk w{scell, gcell, 1, sx, sy, 0.0};
-        double x, y;
-        int r;
-        while ((r = r9_step(g, nf, w, &x, &y)) == 1) {
-            w.s = w.s + r9_seg(w.vx, w.vy, x, y);
-            w.vx = x, w.vy = y;
-        }
-        if (r < 0) st = 3;
-        sm = w.s + r9_seg(w.vx, w.vy, gx, gy);
-        count = w.count;
-    }
-    if (J) {
-        if (st) gx = sx, gy = sy, gi = -1;
-        if (vertices) vertices[q] = st ? 0 : count > 2 ? count : 2;
-        if (goal_out) goal_out[q] = gi;
-    }
-    out[0] = sx, out[1] = sy;
-    out[2 * (N + 1)] = gx, out[2 * (N + 1) + 1] = gy;
-    status[q] = st;
-    if (steps) steps[q] = st ? 0 : count;
-    if (st) {
-        for (int j = 1; j <= N; ++j) {
-            const double f = (double)j / dn1;
-            out[2 * j] = sx + (gx - sx) * f;
-            out[2 * j + 1] = sy + (gy - sy) * f;
-        }
+    constexpr int D = G::D;
+    R9Query<G> u = r9_query<J>(g, src, next, goals, n_goals, starts, goal_idx, q);
+    double* out = wp + q * (int64_t)(N + 2) * D;
+    R9Path<D> p = r9_path<D>(u.s, 0.0, N, nullptr, true);
+    int64_t count = 0;
+    if (!u.st && (count = r9_walk(g, u.nf, u.scell, u.gcell, p)) < 0) u.st = 3;
+    r9_ends<J>(u, q, N, out, status, steps, (int32_t)count, vertices,
+               (int32_t)(count > 2 ? count : 2), goal_out, true);
+    if (u.st) {
+        r9_straight(u, N, out, 1, 1);
         return;
     }
-    // second walk: waypoint j lies on the first segment i (not before the previous
-    // waypoint's) with S_i > t_j, on the last one when there is none
-    R9Walk w{scell, gcell, 1, sx, sy, 0.0};
-    int j = 1;
-    for (;;) {
-        double x = gx, y = gy;
-        const int r = r9_step(g, nf, w, &x, &y);
-        const bool last = r != 1;
-        const double si = w.s + r9_seg(w.vx, w.vy, x, y);
-        while (j <= N) {
-            const double t = sm * ((double)j / dn1);
-            if (!last && !(si > t)) break;
-            const double den = si - w.s;
-            const double u = den > 0.0 ? (t - w.s) / den : 0.0;
-            out[2 * j] = w.vx + u * (x - w.vx);
-            out[2 * j + 1] = w.vy + u * (y - w.vy);
-            ++j;
-        }
-        if (last) break;
-        w.s = si;
-        w.vx = x, w.vy = y;
-    }
+    r9_vertex(g, p, u.t, true);  // S_m
+    p = r9_path<D>(u.s, p.s, N, out, true);
+    (void)r9_walk(g, u.nf, u.scell, u.gcell, p);
+    r9_vertex(g, p, u.t, true);
 }
 
 // ---- kernels --------------------------------------------------------------------------------
@@ -465,49 +562,63 @@ void route_relax_launch(int n, hipStream_t s, const double* c, double* dist,
                        lists + (cur ^ 1) * nt, ctl, cur, inner);
 }
 
-// the host twin of the field: the cost plane by r9_cost, a heap Dijkstra over r9_weight's
-// edges (the same minimum as any relaxation order: fl(a + w) is monotone in a), r9_next
+// The heap Dijkstra of the host twins, on either grid: from the seeds in heap, each (0.0, cell)
+// with d = 0 there already (all keys equal: a heap as it stands), over the edges that
+// edges(u, visit) names by calling visit(v, fl(d[u] + w(u, v))) for the neighbours v of u.  The
+// same minimum as any relaxation order: fl(a + w) is monotone in a.
+template <typename Edges>
+inline void r9_dijkstra(std::vector<std::pair<double, int32_t>>& heap, double* d, Edges edges) {
+    auto later = [](const std::pair<double, int32_t>& a, const std::pair<double, int32_t>& b) {
+        return a.first > b.first;
+    };
+    while (!heap.empty()) {
+        std::pop_heap(heap.begin(), heap.end(), later);
+        const auto top = heap.back();
+        heap.pop_back();
+        const int32_t u = top.second;
+        if (top.first > d[u]) continue;
+        edges(u, [&](int32_t v, double t) {
+            if (t < d[v]) {
+                d[v] = t;
+                heap.emplace_back(t, v);
+                std::push_heap(heap.begin(), heap.end(), later);
+            }
+        });
+    }
+}
+
+// the raster's edges out of u: the edge u -> v seen from v, v's neighbour in the opposite
+// direction, by r9_candidate
+template <typename Visit>
+inline void r9_edges(const KRoute& g, const double* c, const double* d, int32_t u, Visit visit) {
+    const int ux = u % g.nx, uy = u / g.nx;
+    for (int k = 0; k < 8; ++k) {
+        const int vx = ux + r9_dix(k), vy = uy + r9_diy(k);
+        if (vx < 0 || vx >= g.nx || vy < 0 || vy >= g.ny) continue;
+        const int64_t v = (int64_t)vy * g.nx + vx;
+        if (!(c[v] < r9_inf())) continue;
+        visit((int32_t)v, r9_candidate(g, c, d, vx, vy, c[v], (k + 4) & 7));
+    }
+}
+
+// the host twin of the field: the cost plane by r9_cost, r9_dijkstra over r9_weight's edges,
+// r9_next
 inline void r9_field_host(const KRoute& g, const uint4* rec, const double* goals, int32_t n_goals,
                           double* dist, uint8_t* next) {
-    const int64_t n = (int64_t)g.nx * g.ny;
+    const int64_t n = r9_count(g);
     std::vector<double> c((size_t)n);
     for (int64_t i = 0; i < n; ++i)
         c[(size_t)i] = r9_cost(g, rec, (int)(i % g.nx), (int)(i / g.nx));
     std::vector<std::pair<double, int32_t>> heap;
-    auto later = [](const std::pair<double, int32_t>& a, const std::pair<double, int32_t>& b) {
-        return a.first > b.first;
-    };
     for (int32_t gi = 0; gi < n_goals; ++gi) {
         double* d = dist + (int64_t)gi * n;
         uint8_t* nx = next + (int64_t)gi * n;
         for (int64_t i = 0; i < n; ++i) d[i] = r9_inf();
-        int32_t gcell = r9_cell(g, goals[2 * gi], goals[2 * gi + 1]);
+        const int32_t gcell = r9_cell(g, goals[2 * gi], goals[2 * gi + 1]);
         if (gcell >= 0 && c[(size_t)gcell] < r9_inf()) {
             d[gcell] = 0.0;
-            heap.clear();
-            heap.emplace_back(0.0, gcell);
-            while (!heap.empty()) {
-                std::pop_heap(heap.begin(), heap.end(), later);
-                const auto top = heap.back();
-                heap.pop_back();
-                const int32_t u = top.second;
-                if (top.first > d[u]) continue;
-                const int ux = u % g.nx, uy = u / g.nx;
-                for (int k = 0; k < 8; ++k) {
-                    // the edge u -> v seen from v: v's neighbour in the opposite direction
-                    const int vx = ux + r9_dix(k), vy = uy + r9_diy(k);
-                    if (vx < 0 || vx >= g.nx || vy < 0 || vy >= g.ny) continue;
-                    const int64_t v = (int64_t)vy * g.nx + vx;
-                    if (!(c[(size_t)v] < r9_inf())) continue;
-                    const double t =
-                        r9_candidate(g, c.data(), d, vx, vy, c[(size_t)v], (k + 4) & 7);
-                    if (t < d[v]) {
-                        d[v] = t;
-                        heap.emplace_back(t, (int32_t)v);
-                        std::push_heap(heap.begin(), heap.end(), later);
-                    }
-                }
-            }
+            heap.assign(1, {0.0, gcell});
+            r9_dijkstra(heap, d, [&](int32_t u, auto visit) { r9_edges(g, c.data(), d, u, visit); });
         }
         for (int64_t i = 0; i < n; ++i)
             nx[i] = r9_next(g, c.data(), d, (int)(i % g.nx), (int)(i / g.nx), gcell);

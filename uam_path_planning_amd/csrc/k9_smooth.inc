@@ -1,8 +1,12 @@
 // k9_smooth.inc -- K9b / K9s, any-angle shortcuts on the traced route (include/uampath.h "Route
-// seeds", "smoothing"): k_route_free_bits (one bit per cell, set = free), k_route_smooth (one wave
-// per query: the chain along next, the anchors by "advance while visible", the resampled
-// waypoints), and the __host__ __device__ pieces they share with uam_route_free_bits_host /
-// uam_route_paths_smooth_host / uam_route_visible_host.  Integer arithmetic decides every
+// seeds", "smoothing"): k_route_free_bits (one bit per cell, set = free) with its host twin,
+// k_route_smooth (one wave per query: the chain along next, the anchors by "advance while
+// visible", the resampled waypoints), the raster's sight line r9s_los and its walk along next.
+// The smoothing itself is written once over the grid type G, for this file's kernel, for
+// k_route_joint_smooth (k9_joint.inc) and for k_route3_smooth (k9v_smooth.inc): r9_pass,
+// r9_smooth_wave and the host twin r9_smooth_host, which reach the grid only through the
+// vocabulary of k9_route.inc and the three overloads on the free bits given here and in
+// k9v_smooth.inc (r9_bit_free, r9_visible, r9_advance).  Integer arithmetic decides every
 // visibility; the float64 operations are r9_trace's, in its order.
 // Included in the anonymous namespace of uampath.hip, after k9_route.inc.
 
@@ -48,198 +52,209 @@ __host__ __device__ inline bool r9s_los(const uint32_t* bits, int wpr, I ax, I a
     return true;
 }
 
-// LOS between two cells of the chain (cell indices)
-__host__ __device__ __forceinline__ bool r9s_visible(const uint32_t* bits, int nx, int32_t a,
-                                                     int32_t b) {
-    return r9s_los<int32_t>(bits, r9s_wpr(nx), a % nx, a / nx, b % nx, b / nx);
+// ---- the grid vocabulary on the free bits ---------------------------------------------------
+__host__ __device__ __forceinline__ bool r9_bit_free(const KRoute& g, const uint32_t* bits,
+                                                     int32_t cell) {
+    return r9s_free(bits, r9s_wpr(g.nx), cell % g.nx, cell / g.nx);
 }
 
-// a query's end points, cells, field and status 4 / 1 / 2 (r9_trace's tests in its order; the
-// start's blocking from the bits)
-struct R9sQuery {
-    double sx, sy, gx, gy;
-    int32_t scell, gcell;
-    const uint8_t* nf;
-    int st;
-    int32_t gi;  // the goal index (J: the start cell's owner, -1 for a nonzero status)
+// LOS between two cells of the chain
+__host__ __device__ __forceinline__ bool r9_visible(const KRoute& g, const uint32_t* bits,
+                                                    int32_t a, int32_t b) {
+    return r9s_los<int32_t>(bits, r9s_wpr(g.nx), a % g.nx, a / g.nx, b % g.nx, b / g.nx);
+}
+
+// the start's blocking as the smoothing reads it, on either grid
+template <typename G>
+__host__ __device__ __forceinline__ bool r9_start_blocked(const G& g, const uint32_t* bits,
+                                                          int32_t cell) {
+    return !r9_bit_free(g, bits, cell);
+}
+
+// The walk along next, the same in every lane of the wave; every cell reached goes into the
+// wave's ring (slot = chain index & mask).
+struct R9sWalk {
+    int32_t cell;  // c_idx
+    int32_t idx;   // chain index of cell
+    bool done;     // cell is the goal's: n = idx + 1
+    bool fail;     // status 3
 };
 
-// J (a joint field): r9_trace<true>'s rules, the start's blocking from the bits
-template <bool J = false>
-__host__ __device__ inline R9sQuery r9s_query(const KRoute& g, const uint32_t* bits,
-                                              const uint8_t* next, const double* goals,
-                                              int32_t n_goals, const double* starts,
-                                              const int32_t* goal_idx, int64_t q) {
-    R9sQuery u;
-    u.sx = starts[2 * q], u.sy = starts[2 * q + 1];
-    u.gx = u.sx, u.gy = u.sy;  // a goal index out of range: every waypoint is the start point
-    u.scell = u.gcell = -1;
-    u.nf = next;
-    u.st = 0;
-    if (J) {
-        u.gi = -1;
-        u.scell = r9_cell(g, u.sx, u.sy);
-        if (u.scell < 0 || !r9s_free(bits, r9s_wpr(g.nx), u.scell % g.nx, u.scell / g.nx)) {
-            u.st = 1;
-        } else if (u.nf[u.scell] == 255) {
-            u.st = 2;
-        } else {
-            const int32_t o = goal_idx[u.scell];
-            if (o >= 0 && o < n_goals)
-                u.gcell = r9_cell(g, goals[2 * (int64_t)o], goals[2 * (int64_t)o + 1]);
-            if (u.gcell < 0) {
-                u.st = 3;
-            } else {
-                u.gi = o;
-                u.gx = goals[2 * (int64_t)o], u.gy = goals[2 * (int64_t)o + 1];
+// one hop of the walk taken with direction k; false when the walk ends here
+template <typename G>
+__device__ __forceinline__ bool r9s_hopped(const G& g, int k, int32_t gcell, R9sWalk& w,
+                                           int32_t* ring, int lane) {
+    if (r9_hop(g, k, &w.cell, (int64_t)w.idx + 1) < 0) {
+        w.fail = true;
+        return false;
+    }
+    ++w.idx;
+    if (lane == 0) ring[w.idx & (R9S_RING - 1)] = w.cell;
+    if (w.cell == gcell) w.done = true;
+    return !w.done;
+}
+
+// The raster's walk up to chain index upto: the lanes load the 8 x 8 patch of next around the
+// current cell, and the chain is followed inside it with shuffles until it leaves the patch.
+__device__ inline void r9_advance(const KRoute& g, const uint8_t* __restrict__ nf, int32_t gcell,
+                                  R9sWalk& w, int32_t upto, int32_t* ring, int lane) {
+    while (!w.done && !w.fail && w.idx < upto) {
+        const int ox = w.cell % g.nx - 4, oy = w.cell / g.nx - 4;
+        const int px = ox + (lane & 7), py = oy + (lane >> 3);
+        int mine = 255;
+        if (px >= 0 && px < g.nx && py >= 0 && py < g.ny) mine = nf[(int64_t)py * g.nx + px];
+        for (;;) {
+            const int lx = w.cell % g.nx - ox, ly = w.cell / g.nx - oy;
+            if (lx < 0 || lx > 7 || ly < 0 || ly > 7) break;  // the next patch
+            if (!r9s_hopped(g, __shfl(mine, ly * 8 + lx, 64), gcell, w, ring, lane)) break;
+            if (w.idx >= upto) break;
+        }
+    }
+    wave_sync();
+}
+
+// ---- the smoothing, on either grid ------------------------------------------------------------
+// One pass over a query's chain: anchors by "advance while visible", 64 candidates at a time,
+// one lane each.  Every anchor goes to path (pass 1: S_m; pass 2: the waypoints) and, while
+// there is room, into list.  Returns the number of anchors, -1 for status 3; *n_out = steps.
+template <typename G>
+__device__ inline int32_t r9_pass(const G& g, const uint32_t* __restrict__ bits,
+                                  const R9Query<G>& u, int32_t span, int32_t* ring, int32_t* list,
+                                  R9Path<G::D>& path, int32_t* n_out, int lane) {
+    R9sWalk w{u.scell, 0, u.scell == u.gcell, false};
+    r9_advance(g, u.nf, u.gcell, w, 2, ring, lane);
+    if (w.fail) return -1;
+    int32_t na = 0;
+    if (!(w.done && w.idx < 2)) {  // n > 2
+        int32_t a = 1;
+        int32_t acell = ring[1];
+        for (;;) {
+            double x[G::D];
+            r9_centre(g, acell, x);
+            r9_vertex(g, path, x, false);
+            if (list && na < R9S_LIST && lane == 0) list[na] = acell;
+            ++na;
+            r9_advance(g, u.nf, u.gcell, w, a + span, ring, lane);
+            if (w.fail) return -1;
+            if (w.done && a == w.idx - 1) break;  // a = n - 2
+            const int32_t top = w.done && w.idx - 1 < a + span ? w.idx - 1 : a + span;
+            int32_t j = top;
+            for (int32_t base = a + 1; base <= top; base += 64) {
+                const int32_t i = base + lane;
+                bool blocked = false;
+                if (i <= top && i > a + 1)  // adjacent chain cells are visible
+                    blocked = !r9_visible(g, bits, acell, ring[i & (R9S_RING - 1)]);
+                const uint64_t m = __ballot(blocked);
+                if (m) {
+                    j = base + (__ffsll((unsigned long long)m) - 1) - 1;
+                    break;
+                }
             }
+            a = j;
+            acell = ring[a & (R9S_RING - 1)];
         }
-        return u;
     }
-    const int32_t gi = goal_idx[q];
-    u.gi = gi;
-    if (gi < 0 || gi >= n_goals) {
-        u.st = 4;
-    } else {
-        u.gx = goals[2 * (int64_t)gi], u.gy = goals[2 * (int64_t)gi + 1];
-        u.nf = next + (int64_t)gi * g.nx * g.ny;
-        u.gcell = r9_cell(g, u.gx, u.gy);
-        if (u.gcell < 0 || u.nf[u.gcell] != 8) u.st = 4;
-    }
+    *n_out = w.idx + 1;
+    return na;
+}
+
+// One wave's query, the body of k_route_smooth, k_route3_smooth and (J, a joint field:
+// r9_query<true>'s rules and goal_out) k_route_joint_smooth.  ring and list are the wave's LDS.
+template <bool J, typename G>
+__device__ __forceinline__ void r9_smooth_wave(
+    const G& g, const uint32_t* __restrict__ bits, const uint8_t* __restrict__ next,
+    const double* __restrict__ goals, int32_t n_goals, const double* __restrict__ starts,
+    const int32_t* __restrict__ goal_idx, int64_t q, int32_t N, int32_t span,
+    double* __restrict__ wp, int32_t* __restrict__ status, int32_t* __restrict__ steps,
+    int32_t* __restrict__ vertices, int32_t* __restrict__ goal_out, int32_t* ring, int32_t* list,
+    int lane) {
+    constexpr int D = G::D;
+    R9Query<G> u = r9_query<J>(g, bits, next, goals, n_goals, starts, goal_idx, q);
+    double* out = wp + q * (int64_t)(N + 2) * D;
+    int32_t n = 0, na = 0;
+    R9Path<D> p = r9_path<D>(u.s, 0.0, N, nullptr, false);
     if (!u.st) {
-        u.scell = r9_cell(g, u.sx, u.sy);
-        if (u.scell < 0 || !r9s_free(bits, r9s_wpr(g.nx), u.scell % g.nx, u.scell / g.nx))
-            u.st = 1;
+        na = r9_pass(g, bits, u, span, ring, list, p, &n, lane);
+        if (na < 0) u.st = 3;
     }
-    if (!u.st && u.nf[u.scell] == 255) u.st = 2;
-    return u;
-}
-
-// the straight line of a nonzero status: waypoints j0, j0 + stride, ..
-__host__ __device__ inline void r9s_straight(const R9sQuery& u, int32_t N, double* out, int j0,
-                                             int stride) {
-    const double dn1 = (double)(N + 1);
-    for (int j = j0; j <= N; j += stride) {
-        const double f = (double)j / dn1;
-        out[2 * j] = u.sx + (u.gx - u.sx) * f;
-        out[2 * j + 1] = u.sy + (u.gy - u.sy) * f;
+    r9_ends<J>(u, q, N, out, status, steps, n, vertices, na + 2, goal_out, lane == 0);
+    if (u.st) {
+        r9_straight(u, N, out, 1 + lane, 64);
+        return;
     }
-}
-
-__host__ __device__ __forceinline__ void r9s_centre(const KRoute& g, int32_t cell, double* x,
-                                                    double* y) {
-    *x = g.x0 + ((double)(cell % g.nx) + 0.5) * g.dx;
-    *y = g.y_top - ((double)(cell / g.nx) + 0.5) * g.dy;
-}
-
-// The vertices V_1, V_2, .. of a path taken one after the other: pass 1 sums S_m, pass 2 (sm
-// known) places the waypoints, r9_trace's second walk operation for operation.
-struct R9sPath {
-    double vx, vy;  // V_{i-1}
-    double s;       // S_{i-1}
-    double sm, dn1;
-    int32_t j, N;
-    double* out;    // NULL: pass 1
-    bool write;     // this lane stores the waypoints
-};
-
-__host__ __device__ inline void r9s_vertex(R9sPath& p, double x, double y, bool last) {
-    const double si = p.s + r9_seg(p.vx, p.vy, x, y);
-    if (p.out) {
-        while (p.j <= p.N) {
-            const double t = p.sm * ((double)p.j / p.dn1);
-            if (!last && !(si > t)) break;
-            const double den = si - p.s;
-            const double u = den > 0.0 ? (t - p.s) / den : 0.0;
-            const double wx = p.vx + u * (x - p.vx), wy = p.vy + u * (y - p.vy);
-            if (p.write) p.out[2 * p.j] = wx, p.out[2 * p.j + 1] = wy;
-            ++p.j;
+    r9_vertex(g, p, u.t, true);  // S_m
+    R9Path<D> e = r9_path<D>(u.s, p.s, N, out, lane == 0);
+    if (na <= R9S_LIST) {
+        wave_sync();
+        for (int32_t k = 0; k < na; ++k) {
+            double x[D];
+            r9_centre(g, list[k], x);
+            r9_vertex(g, e, x, false);
         }
+    } else {  // the list overflowed: the same anchors again, placed as they are found
+        (void)r9_pass(g, bits, u, span, ring, nullptr, e, &n, lane);
     }
-    p.s = si;
-    p.vx = x, p.vy = y;
+    r9_vertex(g, e, u.t, true);
 }
 
-// one step of the chain from cell (count cells visited so far): 1 = moved, -1 = the walk left
-// the field (r9_step's rules)
-__host__ __device__ __forceinline__ int r9s_hop(const KRoute& g, int k, int32_t* cell,
-                                                int64_t count) {
-    if (count >= (int64_t)g.nx * g.ny) return -1;
-    if (k > 7) return -1;
-    const int ix = *cell % g.nx + r9_dix(k), iy = *cell / g.nx + r9_diy(k);
-    if (ix < 0 || ix >= g.nx || iy < 0 || iy >= g.ny) return -1;
-    *cell = iy * g.nx + ix;
-    return 1;
-}
-
-// ---- host twin ------------------------------------------------------------------------------
-template <bool J = false>
-inline void r9s_smooth_host(const KRoute& g, const uint32_t* bits, const uint8_t* next,
-                            const double* goals, int32_t n_goals, const double* starts,
-                            const int32_t* goal_idx, int64_t q, int32_t N, int32_t span,
-                            double* wp, int32_t* status, int32_t* steps, int32_t* vertices,
-                            std::vector<int32_t>& cells, std::vector<int32_t>& anchors,
-                            int32_t* goal_out = nullptr) {
-    R9sQuery u = r9s_query<J>(g, bits, next, goals, n_goals, starts, goal_idx, q);
-    double* out = wp + q * (int64_t)(N + 2) * 2;
+// the host twin: the chain in cells, the anchors one candidate at a time, the two passes
+template <bool J = false, typename G>
+inline void r9_smooth_host(const G& g, const uint32_t* bits, const uint8_t* next,
+                           const double* goals, int32_t n_goals, const double* starts,
+                           const int32_t* goal_idx, int64_t q, int32_t N, int32_t span,
+                           double* wp, int32_t* status, int32_t* steps, int32_t* vertices,
+                           std::vector<int32_t>& cells, std::vector<int32_t>& anchors,
+                           int32_t* goal_out = nullptr) {
+    constexpr int D = G::D;
+    R9Query<G> u = r9_query<J>(g, bits, next, goals, n_goals, starts, goal_idx, q);
+    double* out = wp + q * (int64_t)(N + 2) * D;
     cells.clear();
     anchors.clear();
     if (!u.st) {
         int32_t cell = u.scell;
         cells.push_back(cell);
         while (cell != u.gcell) {
-            if (r9s_hop(g, u.nf[cell], &cell, (int64_t)cells.size()) < 0) {
+            if (r9_hop(g, u.nf[cell], &cell, (int64_t)cells.size()) < 0) {
                 u.st = 3;
                 break;
             }
             cells.push_back(cell);
         }
     }
-    if (J) {
-        if (u.st) u.gx = u.sx, u.gy = u.sy, u.gi = -1;
-        if (goal_out) goal_out[q] = u.gi;
-    }
-    out[0] = u.sx, out[1] = u.sy;
-    out[2 * (N + 1)] = u.gx, out[2 * (N + 1) + 1] = u.gy;
-    status[q] = u.st;
-    if (steps) steps[q] = u.st ? 0 : (int32_t)cells.size();
-    if (u.st) {
-        if (vertices) vertices[q] = 0;
-        r9s_straight(u, N, out, 1, 1);
-        return;
-    }
     const int64_t n = (int64_t)cells.size();
-    if (n > 2) {
+    if (!u.st && n > 2) {
         int64_t a = 1;
         anchors.push_back(cells[1]);
         while (a != n - 2) {
             const int64_t jmax = a + span < n - 2 ? a + span : n - 2;
             // advance while visible; c_{a+1} is taken untested (adjacent chain cells are visible)
             int64_t j = a + 1;
-            while (j < jmax && r9s_visible(bits, g.nx, cells[(size_t)a], cells[(size_t)j + 1])) ++j;
+            while (j < jmax && r9_visible(g, bits, cells[(size_t)a], cells[(size_t)j + 1])) ++j;
             a = j;
             anchors.push_back(cells[(size_t)a]);
         }
     }
-    if (vertices) vertices[q] = (int32_t)anchors.size() + 2;
-    R9sPath p{u.sx, u.sy, 0.0, 0.0, (double)(N + 1), 1, N, nullptr, true};
-    double x, y;
-    for (int32_t c : anchors) {
-        r9s_centre(g, c, &x, &y);
-        r9s_vertex(p, x, y, false);
+    r9_ends<J>(u, q, N, out, status, steps, (int32_t)n, vertices, (int32_t)anchors.size() + 2,
+               goal_out, true);
+    if (u.st) {
+        r9_straight(u, N, out, 1, 1);
+        return;
     }
-    r9s_vertex(p, u.gx, u.gy, true);
-    p = R9sPath{u.sx, u.sy, 0.0, p.s, (double)(N + 1), 1, N, out, true};
-    for (int32_t c : anchors) {
-        r9s_centre(g, c, &x, &y);
-        r9s_vertex(p, x, y, false);
+    R9Path<D> p = r9_path<D>(u.s, 0.0, N, nullptr, true);
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int32_t c : anchors) {
+            double x[D];
+            r9_centre(g, c, x);
+            r9_vertex(g, p, x, false);
+        }
+        r9_vertex(g, p, u.t, true);
+        if (pass == 0) p = r9_path<D>(u.s, p.s, N, out, true);
     }
-    r9s_vertex(p, u.gx, u.gy, true);
 }
 
-// ---- kernels --------------------------------------------------------------------------------
-// the free bits: one wave per 64 cells of a row, one lane per cell; lanes 0 and 32 store the
-// two words of the wave's ballot (bits past nx stay 0)
+// ---- the free bits ----------------------------------------------------------------------------
+// one wave per 64 cells of a row, one lane per cell; lanes 0 and 32 store the two words of the
+// wave's ballot (bits past nx stay 0)
 __global__ __launch_bounds__(R9_THREADS) void k_route_free_bits(const uint4* __restrict__ rec,
                                                                 KRoute g,
                                                                 uint32_t* __restrict__ bits) {
@@ -259,135 +274,19 @@ __global__ __launch_bounds__(R9_THREADS) void k_route_free_bits(const uint4* __r
     }
 }
 
-// The walk along next, the same in every lane of the wave: the lanes load the 8 x 8 patch of
-// next around the current cell, and the chain is followed inside it with shuffles until it
-// leaves the patch; every cell reached goes into the wave's ring (slot = chain index & mask).
-struct R9sWalk {
-    int32_t cell;  // c_idx
-    int32_t idx;   // chain index of cell
-    bool done;     // cell is the goal's: n = idx + 1
-    bool fail;     // status 3
-};
-
-__device__ inline void r9s_advance(const KRoute& g, const uint8_t* __restrict__ nf, int32_t gcell,
-                                   R9sWalk& w, int32_t upto, int32_t* ring, int lane) {
-    while (!w.done && !w.fail && w.idx < upto) {
-        const int ox = w.cell % g.nx - 4, oy = w.cell / g.nx - 4;
-        const int px = ox + (lane & 7), py = oy + (lane >> 3);
-        int mine = 255;
-        if (px >= 0 && px < g.nx && py >= 0 && py < g.ny) mine = nf[(int64_t)py * g.nx + px];
-        for (;;) {
-            const int cx = w.cell % g.nx, cy = w.cell / g.nx;
-            const int lx = cx - ox, ly = cy - oy;
-            if (lx < 0 || lx > 7 || ly < 0 || ly > 7) break;  // the next patch
-            const int k = __shfl(mine, ly * 8 + lx, 64);
-            if (r9s_hop(g, k, &w.cell, (int64_t)w.idx + 1) < 0) {
-                w.fail = true;
-                break;
-            }
-            ++w.idx;
-            if (lane == 0) ring[w.idx & (R9S_RING - 1)] = w.cell;
-            if (w.cell == gcell) {
-                w.done = true;
-                break;
-            }
-            if (w.idx >= upto) break;
+inline void r9s_free_bits_host(const KRoute& g, const uint4* rec, uint32_t* bits) {
+    const int wpr = r9s_wpr(g.nx);
+    for (int iy = 0; iy < g.ny; ++iy)
+        for (int w = 0; w < wpr; ++w) {
+            uint32_t m = 0u;
+            for (int b = 0; b < 32 && (int64_t)w * 32 + b < g.nx; ++b)
+                if (r9_cost(g, rec, w * 32 + b, iy) < r9_inf()) m |= 1u << b;
+            bits[(int64_t)iy * wpr + w] = m;
         }
-    }
-    wave_sync();
 }
 
-// One pass over a query's chain: anchors by "advance while visible", 64 candidates at a time,
-// one lane each.  Every anchor goes to path (pass 1: S_m; pass 2: the waypoints) and, while
-// there is room, into list.  Returns the number of anchors, -1 for status 3; *n_out = steps.
-__device__ inline int32_t r9s_pass(const KRoute& g, const uint32_t* __restrict__ bits,
-                                   const R9sQuery& u, int32_t span, int32_t* ring, int32_t* list,
-                                   R9sPath& path, int32_t* n_out, int lane) {
-    R9sWalk w{u.scell, 0, u.scell == u.gcell, false};
-    r9s_advance(g, u.nf, u.gcell, w, 2, ring, lane);
-    if (w.fail) return -1;
-    int32_t na = 0;
-    if (!(w.done && w.idx < 2)) {  // n > 2
-        int32_t a = 1;
-        int32_t acell = ring[1];
-        for (;;) {
-            double x, y;
-            r9s_centre(g, acell, &x, &y);
-            r9s_vertex(path, x, y, false);
-            if (list && na < R9S_LIST && lane == 0) list[na] = acell;
-            ++na;
-            r9s_advance(g, u.nf, u.gcell, w, a + span, ring, lane);
-            if (w.fail) return -1;
-            if (w.done && a == w.idx - 1) break;  // a = n - 2
-            const int32_t top = w.done && w.idx - 1 < a + span ? w.idx - 1 : a + span;
-            int32_t j = top;
-            for (int32_t base = a + 1; base <= top; base += 64) {
-                const int32_t i = base + lane;
-                bool blocked = false;
-                if (i <= top && i > a + 1)  // adjacent chain cells are visible
-                    blocked = !r9s_visible(bits, g.nx, acell, ring[i & (R9S_RING - 1)]);
-                const uint64_t m = __ballot(blocked);
-                if (m) {
-                    j = base + (__ffsll((unsigned long long)m) - 1) - 1;
-                    break;
-                }
-            }
-            a = j;
-            acell = ring[a & (R9S_RING - 1)];
-        }
-    }
-    *n_out = w.idx + 1;
-    return na;
-}
-
-// One wave's query, k_route_smooth's body and (J, a joint field: r9s_query<true>'s rules and
-// goal_out) k_route_joint_smooth's.  ring and list are the wave's LDS.
-template <bool J>
-__device__ __forceinline__ void r9s_smooth_wave(
-    const KRoute& g, const uint32_t* __restrict__ bits, const uint8_t* __restrict__ next,
-    const double* __restrict__ goals, int32_t n_goals, const double* __restrict__ starts,
-    const int32_t* __restrict__ goal_idx, int64_t q, int32_t N, int32_t span,
-    double* __restrict__ wp, int32_t* __restrict__ status, int32_t* __restrict__ steps,
-    int32_t* __restrict__ vertices, int32_t* __restrict__ goal_out, int32_t* ring, int32_t* list,
-    int lane) {
-    R9sQuery u = r9s_query<J>(g, bits, next, goals, n_goals, starts, goal_idx, q);
-    double* out = wp + q * (int64_t)(N + 2) * 2;
-    int32_t n = 0, na = 0;
-    R9sPath p{u.sx, u.sy, 0.0, 0.0, (double)(N + 1), 1, N, nullptr, false};
-    if (!u.st) {
-        na = r9s_pass(g, bits, u, span, ring, list, p, &n, lane);
-        if (na < 0) u.st = 3;
-    }
-    if (J) {
-        if (u.st) u.gx = u.sx, u.gy = u.sy, u.gi = -1;
-        if (goal_out && lane == 0) goal_out[q] = u.gi;
-    }
-    if (lane == 0) {
-        out[0] = u.sx, out[1] = u.sy;
-        out[2 * (N + 1)] = u.gx, out[2 * (N + 1) + 1] = u.gy;
-        status[q] = u.st;
-        if (steps) steps[q] = u.st ? 0 : n;
-        if (vertices) vertices[q] = u.st ? 0 : na + 2;
-    }
-    if (u.st) {
-        r9s_straight(u, N, out, 1 + lane, 64);
-        return;
-    }
-    r9s_vertex(p, u.gx, u.gy, true);  // S_m
-    R9sPath e{u.sx, u.sy, 0.0, p.s, (double)(N + 1), 1, N, out, lane == 0};
-    if (na <= R9S_LIST) {
-        wave_sync();
-        for (int32_t k = 0; k < na; ++k) {
-            double x, y;
-            r9s_centre(g, list[k], &x, &y);
-            r9s_vertex(e, x, y, false);
-        }
-    } else {  // the list overflowed: the same anchors again, placed as they are found
-        (void)r9s_pass(g, bits, u, span, ring, nullptr, e, &n, lane);
-    }
-    r9s_vertex(e, u.gx, u.gy, true);
-}
-
+// ---- the smoothing kernel ----------------------------------------------------------------------
+// (k_route_joint_smooth and k_route3_smooth are these lines again: the kernel owns its LDS)
 __global__ __launch_bounds__(R9S_WAVES * 64) void k_route_smooth(
     KRoute g, const uint32_t* __restrict__ bits, const uint8_t* __restrict__ next,
     const double* __restrict__ goals, int32_t n_goals, const double* __restrict__ starts,
@@ -400,6 +299,6 @@ __global__ __launch_bounds__(R9S_WAVES * 64) void k_route_smooth(
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * R9S_WAVES + wave;
     if (q >= n_queries) return;  // whole waves leave; no workgroup barrier below
-    r9s_smooth_wave<false>(g, bits, next, goals, n_goals, starts, goal_idx, q, N, span, wp, status,
-                           steps, vertices, nullptr, s_ring[wave], s_list[wave], lane);
+    r9_smooth_wave<false>(g, bits, next, goals, n_goals, starts, goal_idx, q, N, span, wp, status,
+                          steps, vertices, nullptr, s_ring[wave], s_list[wave], lane);
 }

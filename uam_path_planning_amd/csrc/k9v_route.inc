@@ -3,7 +3,9 @@
 // the volume").  k_route3_cost, k_route3_mask, k_route3_init, k_route3_relax<TXY, TZ>,
 // k_route3_next, k_route3_trace, and the __host__ __device__ pieces of the definition they share
 // with uam_route3d_field_host / uam_route3d_paths_host.  K9's own helpers (k9_route.inc) are
-// used where the definition is literally K9's: r9_inf, r9_dix, r9_diy, r9_weight.
+// used where the definition is literally K9's: r9_inf, r9_dix, r9_diy, r9_weight.  The trace
+// and the host Dijkstra are k9_route.inc's, written over the grid type: this file gives them
+// KRoute3's overloads of the grid vocabulary.
 // Included in the anonymous namespace of uampath.hip, after k9_route.inc.
 
 constexpr int R9V_DIRS = 26;
@@ -18,6 +20,8 @@ struct KRoute3 {
     double lambda, agl, kappa;
     uint32_t block_flags;
     int32_t inflate;
+    static constexpr int D = 3;            // coordinates of a point
+    static constexpr int GOAL = R9V_GOAL;  // next at the goal's voxel
 };
 
 // direction k = 0..25: K9's eight with diz = 0, the same with diz = +1, with diz = -1, up, down
@@ -133,125 +137,44 @@ __host__ __device__ __forceinline__ uint8_t r9v_next(const KRoute3& g, const dou
     return 255;  // not at a fixed point (cannot happen after convergence)
 }
 
-// ---- trace and resample -------------------------------------------------------------------
-// K9's two walks with a third component
-struct R9vWalk {
-    int32_t vox, gvox;
-    int64_t count;
-    double vx, vy, vz;  // V_{i-1}
-    double s;           // S_{i-1}
-};
-
-// the next interior vertex of the walk; 0 = the goal voxel was reached (no vertex), 1 = a
-// vertex, -1 = the walk left the field (more than nx*ny*nz voxels, or a next value that is no
-// direction or leads outside the volume: not a field of uam_route3d_field)
-__host__ __device__ __forceinline__ int r9v_step(const KRoute3& g, const uint8_t* next,
-                                                 R9vWalk& w, double* x, double* y, double* z) {
-    if (w.vox == w.gvox) return 0;
-    if (w.count >= r9v_voxels(g)) return -1;
-    const int k = next[w.vox];
+// ---- the grid vocabulary (k9_route.inc) -----------------------------------------------------
+__host__ __device__ __forceinline__ int64_t r9_count(const KRoute3& g) { return r9v_voxels(g); }
+__host__ __device__ __forceinline__ int32_t r9_locate(const KRoute3& g, const double* p) {
+    return r9v_voxel(g, p[0], p[1], p[2]);
+}
+// one step of the chain from vox in direction k (count voxels visited so far): 1 = moved, -1 =
+// the walk left the field (more than nx*ny*nz voxels, or a next value that is no direction or
+// leads outside the volume: not a field of uam_route3d_field)
+__host__ __device__ __forceinline__ int r9_hop(const KRoute3& g, int k, int32_t* vox,
+                                               int64_t count) {
+    if (count >= r9v_voxels(g)) return -1;
     if (k >= R9V_DIRS) return -1;
-    const int col = w.vox / g.nz;
+    const int col = *vox / g.nz;
     const int ix = col % g.nx + r9v_dix(k), iy = col / g.nx + r9v_diy(k),
-              iz = w.vox % g.nz + r9v_diz(k);
+              iz = *vox % g.nz + r9v_diz(k);
     if (ix < 0 || ix >= g.nx || iy < 0 || iy >= g.ny || iz < 0 || iz >= g.nz) return -1;
-    w.vox = r9v_index(g, ix, iy, iz);
-    ++w.count;
-    if (w.vox == w.gvox) return 0;
-    *x = g.x0 + ((double)ix + 0.5) * g.dx;
-    *y = g.y_top - ((double)iy + 0.5) * g.dy;
-    *z = g.z0 + ((double)iz + 0.5) * g.dz;
+    *vox = r9v_index(g, ix, iy, iz);
     return 1;
 }
-
-__host__ __device__ __forceinline__ double r9v_seg(const KRoute3& g, double ax, double ay,
-                                                   double az, double bx, double by, double bz) {
-    const double ex = bx - ax, ey = by - ay, ez = (bz - az) * g.kappa;
+__host__ __device__ __forceinline__ void r9_centre(const KRoute3& g, int32_t vox, double* p) {
+    const int32_t col = vox / g.nz;
+    p[0] = g.x0 + ((double)(col % g.nx) + 0.5) * g.dx;
+    p[1] = g.y_top - ((double)(col / g.nx) + 0.5) * g.dy;
+    p[2] = g.z0 + ((double)(vox % g.nz) + 0.5) * g.dz;
+}
+__host__ __device__ __forceinline__ double r9_seg(const KRoute3& g, const double* a,
+                                                  const double* b) {
+    const double ex = b[0] - a[0], ey = b[1] - a[1], ez = (b[2] - a[2]) * g.kappa;
     return sqrt((ex * ex + ey * ey) + ez * ez);
 }
-
-__host__ __device__ inline void r9v_trace(const KRoute3& g, const uint2* vox, const uint2* col,
-                                          const uint8_t* next, const double* goals,
-                                          int32_t n_goals, const double* starts,
-                                          const int32_t* goal_idx, int64_t q, int32_t N,
-                                          double* wp, int32_t* status, int32_t* steps) {
-    const double sx = starts[3 * q], sy = starts[3 * q + 1], sz = starts[3 * q + 2];
-    const int32_t gi = goal_idx[q];
-    double* out = wp + q * (int64_t)(N + 2) * 3;
-    const double dn1 = (double)(N + 1);
-    double gx = sx, gy = sy, gz = sz;  // a goal index out of range: every waypoint is the start
-    int st = 0;
-    int32_t gvox = -1, svox = -1;
-    const uint8_t* nf = next;
-    if (gi < 0 || gi >= n_goals) {
-        st = 4;
-    } else {
-        gx = goals[3 * (int64_t)gi], gy = goals[3 * (int64_t)gi + 1],
-        gz = goals[3 * (int64_t)gi + 2];
-        nf = next + (int64_t)gi * r9v_voxels(g);
-        gvox = r9v_voxel(g, gx, gy, gz);
-        if (gvox < 0 || nf[gvox] != R9V_GOAL) st = 4;
-    }
-    if (!st) {
-        svox = r9v_voxel(g, sx, sy, sz);
-        if (svox < 0) {
-            st = 1;
-        } else {
-            const int c2 = svox / g.nz;
-            if (!(r9v_cost(g, vox, col, c2 % g.nx, c2 / g.nx, svox % g.nz) < r9_inf())) st = 1;
-        }
-    }
-    if (!st && nf[svox] == 255) st = 2;
-    double sm = 0.0;
-    int64_t count = 0;
-    if (!st) {  // first walk: S_m
-        R9vWalk w{svox, gvox, 1, sx, sy, sz, 0.0};
-        double x, y, z;
-        int r;
-        while ((r = r9v_step(g, nf, w, &x, &y, &z)) == 1) {
-            w.s = w.s + r9v_seg(g, w.vx, w.vy, w.vz, x, y, z);
-            w.vx = x, w.vy = y, w.vz = z;
-        }
-        if (r < 0) st = 3;
-        sm = w.s + r9v_seg(g, w.vx, w.vy, w.vz, gx, gy, gz);
-        count = w.count;
-    }
-    out[0] = sx, out[1] = sy, out[2] = sz;
-    out[3 * (N + 1)] = gx, out[3 * (N + 1) + 1] = gy, out[3 * (N + 1) + 2] = gz;
-    status[q] = st;
-    if (steps) steps[q] = st ? 0 : (int32_t)count;
-    if (st) {
-        for (int j = 1; j <= N; ++j) {
-            const double f = (double)j / dn1;
-            out[3 * j] = sx + (gx - sx) * f;
-            out[3 * j + 1] = sy + (gy - sy) * f;
-            out[3 * j + 2] = sz + (gz - sz) * f;
-        }
-        return;
-    }
-    // second walk: waypoint j lies on the first segment i (not before the previous
-    // waypoint's) with S_i > t_j, on the last one when there is none
-    R9vWalk w{svox, gvox, 1, sx, sy, sz, 0.0};
-    int j = 1;
-    for (;;) {
-        double x = gx, y = gy, z = gz;
-        const int r = r9v_step(g, nf, w, &x, &y, &z);
-        const bool last = r != 1;
-        const double si = w.s + r9v_seg(g, w.vx, w.vy, w.vz, x, y, z);
-        while (j <= N) {
-            const double t = sm * ((double)j / dn1);
-            if (!last && !(si > t)) break;
-            const double den = si - w.s;
-            const double u = den > 0.0 ? (t - w.s) / den : 0.0;
-            out[3 * j] = w.vx + u * (x - w.vx);
-            out[3 * j + 1] = w.vy + u * (y - w.vy);
-            out[3 * j + 2] = w.vz + u * (z - w.vz);
-            ++j;
-        }
-        if (last) break;
-        w.s = si;
-        w.vx = x, w.vy = y, w.vz = z;
-    }
+// the start's blocking as the trace reads it: from the volume's voxels and columns
+struct R9vVolume {
+    const uint2 *vox, *col;
+};
+__host__ __device__ __forceinline__ bool r9_start_blocked(const KRoute3& g, R9vVolume v,
+                                                          int32_t vox) {
+    const int c2 = vox / g.nz;
+    return !(r9v_cost(g, v.vox, v.col, c2 % g.nx, c2 / g.nx, vox % g.nz) < r9_inf());
 }
 
 // ---- kernels --------------------------------------------------------------------------------
@@ -451,7 +374,8 @@ __global__ __launch_bounds__(R9_THREADS) void k_route3_trace(
     int32_t* __restrict__ steps) {
     const int64_t q = (int64_t)blockIdx.x * R9_THREADS + threadIdx.x;
     if (q < n_queries)
-        r9v_trace(g, vox, col, next, goals, n_goals, starts, goal_idx, q, N, wp, status, steps);
+        r9_trace(g, R9vVolume{vox, col}, next, goals, n_goals, starts, goal_idx, q, N, wp, status,
+                 steps);
 }
 
 // ---- host side ------------------------------------------------------------------------------
@@ -459,19 +383,20 @@ constexpr int R9V_TXY_MIN = 8, R9V_TZ_MIN = 4;
 // workspace: the cost plane, the mask plane, then the two flag planes, the two lists (sized for
 // the smallest tile) and the two counts
 struct R9vWs {
-    int64_t c_off, mask_off, flags_off, lists_off, ctl_off, bytes;
+    R9Ws field;  // K9's parts, at the volume's offsets; bytes is the whole workspace
+    int64_t mask_off;
 };
 inline R9vWs r9v_workspace(const KRoute3& g) {
     const int64_t nt = (int64_t)r9_tiles(g.nx, R9V_TXY_MIN) * r9_tiles(g.ny, R9V_TXY_MIN) *
                        r9_tiles(g.nz, R9V_TZ_MIN);
     const int64_t n = r9v_voxels(g);
     R9vWs w;
-    w.c_off = 0;
+    w.field.c_off = 0;
     w.mask_off = r9_al256(n * 8);
-    w.flags_off = w.mask_off + r9_al256(n * 4);
-    w.lists_off = w.flags_off + r9_al256(2 * nt * 4);
-    w.ctl_off = w.lists_off + r9_al256(2 * nt * 4);
-    w.bytes = w.ctl_off + 256;
+    w.field.flags_off = w.mask_off + r9_al256(n * 4);
+    w.field.lists_off = w.field.flags_off + r9_al256(2 * nt * 4);
+    w.field.ctl_off = w.field.lists_off + r9_al256(2 * nt * 4);
+    w.field.bytes = w.field.ctl_off + 256;
     return w;
 }
 
@@ -487,9 +412,8 @@ void route3_relax_launch(int n, hipStream_t s, const double* c, const uint32_t* 
                        flags + (cur ^ 1) * nt, lists + (cur ^ 1) * nt, ctl, cur, inner);
 }
 
-// the host twin of the field: the cost plane by r9v_cost, the masks by r9v_mask, a heap
-// Dijkstra over r9_weight's edges (the same minimum as any relaxation order: fl(a + w) is
-// monotone in a), r9v_next
+// the host twin of the field: the cost plane by r9v_cost, the masks by r9v_mask, r9_dijkstra
+// over r9_weight's edges, r9v_next
 inline void r9v_field_host(const KRoute3& g, const uint2* vox, const uint2* col,
                            const double* goals, int32_t n_goals, double* dist, uint8_t* next) {
     const int64_t n = r9v_voxels(g);
@@ -505,9 +429,6 @@ inline void r9v_field_host(const KRoute3& g, const uint2* vox, const uint2* col,
             r9v_mask(g, c.data(), (int)(c2 % g.nx), (int)(c2 / g.nx), (int)(i % g.nz));
     }
     std::vector<std::pair<double, int32_t>> heap;
-    auto later = [](const std::pair<double, int32_t>& a, const std::pair<double, int32_t>& b) {
-        return a.first > b.first;
-    };
     for (int32_t gi = 0; gi < n_goals; ++gi) {
         double* d = dist + (int64_t)gi * n;
         uint8_t* nx = next + (int64_t)gi * n;
@@ -516,29 +437,18 @@ inline void r9v_field_host(const KRoute3& g, const uint2* vox, const uint2* col,
         if (gvox >= 0 && !(c[(size_t)gvox] < r9_inf())) gvox = -1;
         if (gvox >= 0) {
             d[gvox] = 0.0;
-            heap.clear();
-            heap.emplace_back(0.0, gvox);
-            while (!heap.empty()) {
-                std::pop_heap(heap.begin(), heap.end(), later);
-                const auto top = heap.back();
-                heap.pop_back();
-                const int32_t u = top.second;
-                if (top.first > d[u]) continue;
+            heap.assign(1, {0.0, gvox});
+            r9_dijkstra(heap, d, [&](int32_t u, auto visit) {
                 const uint32_t m = mask[(size_t)u];
                 for (int k = 0; k < R9V_DIRS; ++k) {
                     if (!(m >> k & 1u)) continue;
                     // the edge u -> v seen from v: v's neighbour in the opposite direction,
                     // whose weight is the same sum (r9_weight commutes)
                     const int32_t v = u + (r9v_diy(k) * g.nx + r9v_dix(k)) * g.nz + r9v_diz(k);
-                    const double t =
-                        d[u] + r9_weight(c[(size_t)u], c[(size_t)v], g.len[r9v_len_index(k)]);
-                    if (t < d[v]) {
-                        d[v] = t;
-                        heap.emplace_back(t, v);
-                        std::push_heap(heap.begin(), heap.end(), later);
-                    }
+                    visit(v, d[u] + r9_weight(c[(size_t)u], c[(size_t)v],
+                                              g.len[r9v_len_index(k)]));
                 }
-            }
+            });
         }
         for (int64_t i = 0; i < n; ++i)
             nx[i] = r9v_next(g, c.data(), mask.data(), d, (int32_t)i, gvox);

@@ -9013,55 +9013,183 @@ int uam_eval_generated3d_profiles_hv(uam_ctx* ctx, const uam_volume_desc* vd, co
                            out, climb_sum, stream);
 }
 
-// ---- K9: route seeds (k9_route.inc) -----------------------------------------------------------
-// the descriptor and the parameters checked and folded into the kernels' KRoute
-static int route_setup(const uam_raster_desc* desc, const uam_route_params* p, KRoute* g) {
-    if (!p) return fail(UAM_E_INVALID, "route params is NULL");
-    if (p->abi_version != UAM_ABI_VERSION)
-        return fail(UAM_E_VERSION, "route params abi_version %u != %d", p->abi_version,
-                    UAM_ABI_VERSION);
+// ---- K9: route seeds (k9_route.inc, k9_smooth.inc, k9_joint.inc, k9v_route.inc, k9v_smooth.inc)
+// One host plan for the family.  The raster ("route"), the joint field on it ("joint route") and
+// the volume ("route3d") differ in their grids, their kernels and the names in their messages;
+// the checks and their order, the round loop and the launches' shape are written once, first.
+extern "C++" {  // templates among them
+struct RouteNames {
+    const char *what, *cells, *extent;
+};
+static RouteNames route_names(const KRoute&) { return {"route", "cells", "nx*ny"}; }
+static RouteNames route_names(const KRoute3&) { return {"route3d", "voxels", "nx*ny*nz"}; }
+
+// the grid alone (the raster's smoothing calls take no uam_route_params: blocking comes from the
+// bits)
+static int route_grid(const uam_raster_desc* desc, KRoute* g) {
     KRaster kr{};
     const int st = make_kraster(desc, &kr);
     if (st) return st;
-    if (!(p->lambda >= 0.0) || !(p->lambda < r9_inf()))
-        return fail(UAM_E_INVALID, "route lambda must be finite and >= 0");
-    if (p->inflate < 0 || p->inflate > R9_INFLATE_MAX)
-        return fail(UAM_E_INVALID, "route inflate %d outside [0, %d]", p->inflate,
-                    R9_INFLATE_MAX);
-    if (p->max_rounds < 0) return fail(UAM_E_INVALID, "route max_rounds %d < 0", p->max_rounds);
     g->nx = kr.nx, g->ny = kr.ny;
     g->x0 = kr.x0, g->y_top = kr.y_top, g->dx = kr.dx, g->dy = kr.dy;
     g->inv_dx = kr.inv_dx, g->inv_dy = kr.inv_dy;
     r9_set_lengths(g);
+    return UAM_OK;
+}
+
+// The checks of a parameter block that both grids share, in their order: the block and its
+// abi_version, the descriptor (grid() checks it and fills the grid), lambda, inflate, max_rounds.
+template <typename G, typename P, typename Grid>
+static int route_params_ok(const G& g, const P* p, Grid grid) {
+    const char* what = route_names(g).what;
+    if (!p) return fail(UAM_E_INVALID, "%s params is NULL", what);
+    if (p->abi_version != UAM_ABI_VERSION)
+        return fail(UAM_E_VERSION, "%s params abi_version %u != %d", what, p->abi_version,
+                    UAM_ABI_VERSION);
+    const int st = grid();
+    if (st) return st;
+    if (!(p->lambda >= 0.0) || !(p->lambda < r9_inf()))
+        return fail(UAM_E_INVALID, "%s lambda must be finite and >= 0", what);
+    if (p->inflate < 0 || p->inflate > R9_INFLATE_MAX)
+        return fail(UAM_E_INVALID, "%s inflate %d outside [0, %d]", what, p->inflate,
+                    R9_INFLATE_MAX);
+    if (p->max_rounds < 0)
+        return fail(UAM_E_INVALID, "%s max_rounds %d < 0", what, p->max_rounds);
+    return UAM_OK;
+}
+
+// the descriptor and the parameters checked and folded into the kernels' KRoute
+static int route_setup(const uam_raster_desc* desc, const uam_route_params* p, KRoute* g) {
+    const int st = route_params_ok(*g, p, [&] { return route_grid(desc, g); });
+    if (st) return st;
     g->lambda = p->lambda;
     g->block_flags = p->block_flags;
     g->inflate = p->inflate;
     return UAM_OK;
 }
 
-static int route_goals_ok(const KRoute& g, int32_t n_goals) {
-    if (n_goals < 1) return fail(UAM_E_INVALID, "route n_goals %d < 1", n_goals);
-    if ((int64_t)n_goals * g.nx * g.ny >= ((int64_t)1 << 40))
-        return fail(UAM_E_INVALID, "route fields of 2^40 or more cells");
+// the same for the volume and its KRoute3
+static int route3d_setup(const uam_volume_desc* desc, const uam_route3d_params* p, KRoute3* g) {
+    const int st = route_params_ok(*g, p, [&] {
+        KVolume kv;
+        const int sv = make_kvolume(desc, &kv);
+        if (sv) return sv;
+        g->nx = kv.nx, g->ny = kv.ny, g->nz = kv.nz;
+        g->x0 = kv.x0, g->y_top = kv.y_top, g->dx = desc->dx, g->dy = desc->dy;
+        g->inv_dx = kv.inv_dx, g->inv_dy = kv.inv_dy;
+        g->z0 = kv.z0, g->dz = kv.dz, g->inv_dz = kv.inv_dz;
+        return (int)UAM_OK;
+    });
+    if (st) return st;
+    if (!(p->agl >= 0.0) || !(p->agl < r9_inf()))
+        return fail(UAM_E_INVALID, "route3d agl must be finite and >= 0");
+    if (!(p->z_scale > 0.0) || !(p->z_scale < r9_inf()))
+        return fail(UAM_E_INVALID, "route3d z_scale must be finite and > 0");
+    g->lambda = p->lambda, g->agl = p->agl, g->kappa = p->z_scale;
+    g->block_flags = p->block_flags;
+    g->inflate = p->inflate;
+    r9v_set_lengths(g);
     return UAM_OK;
 }
 
-int64_t uam_route_workspace_bytes(const uam_raster_desc* desc, const uam_route_params* params) {
-    KRoute g{};
-    if (route_setup(desc, params, &g)) return -1;
-    return r9_workspace(g.nx, g.ny).bytes;
+static R9vVolume route3d_volume(const uam_volume_desc* desc, const void* vol) {
+    return {(const uint2*)vol, (const uint2*)((const char*)vol + vol_col_offset(desc))};
 }
 
-int64_t uam_route_visits(const uam_ctx* ctx) { return ctx ? ctx->route_visits : 0; }
+template <typename G>
+static int route_goals_ok(const G& g, int32_t n_goals) {
+    const RouteNames nm = route_names(g);
+    if (n_goals < 1) return fail(UAM_E_INVALID, "%s n_goals %d < 1", nm.what, n_goals);
+    if ((int64_t)n_goals * r9_count(g) >= ((int64_t)1 << 40))
+        return fail(UAM_E_INVALID, "%s fields of 2^40 or more %s", nm.what, nm.cells);
+    return UAM_OK;
+}
 
-// The relaxation rounds of one field from its start state (list 0, ctl[0]) to convergence: one
-// k_route_relax launch per round over the active tiles, the host reading the next round's count
-// after each.  what names the field in the max_rounds message.
-static int route_relax_rounds(uam_ctx* ctx, hipStream_t s, const double* c, double* d,
-                              const KRoute& g, int T, int inner, int ntx, int nty, uint32_t* flags,
-                              int32_t* lists, int32_t* ctl, int64_t max_rounds, const char* what,
-                              int64_t* rounds) {
-    const int nt = ntx * nty;
+// parents and owners are int32 and the smoothing kernel forms a + span
+static int route_joint_ok(const KRoute& g, int32_t n_goals) {
+    if (n_goals < 1 || n_goals > R9J_GOALS_MAX)
+        return fail(UAM_E_INVALID, "joint route n_goals %d outside [1, %d]", n_goals,
+                    R9J_GOALS_MAX);
+    if (r9_count(g) > (int64_t)INT32_MAX - UAM_ROUTE_SPAN_MAX)
+        return fail(UAM_E_INVALID, "joint route field needs nx*ny <= 2^31 - 1 - %d",
+                    UAM_ROUTE_SPAN_MAX);
+    return UAM_OK;
+}
+
+template <typename G>
+static int route_smooth_ok(const G& g, int32_t n_goals, int64_t n_queries, int32_t span) {
+    const RouteNames nm = route_names(g);
+    const int st = route_goals_ok(g, n_goals);
+    if (st) return st;
+    if (n_queries < 0) return fail(UAM_E_INVALID, "%s n_queries < 0", nm.what);
+    if (span < 1 || span > UAM_ROUTE_SPAN_MAX)
+        return fail(UAM_E_INVALID, "%s span %d outside [1, %d]", nm.what, span,
+                    UAM_ROUTE_SPAN_MAX);
+    // cell and chain indices are int32 and the kernel forms a + span
+    if (r9_count(g) > (int64_t)INT32_MAX - UAM_ROUTE_SPAN_MAX)
+        return fail(UAM_E_INVALID, "%s smoothing needs %s <= 2^31 - 1 - %d", nm.what, nm.extent,
+                    UAM_ROUTE_SPAN_MAX);
+    return UAM_OK;
+}
+
+static int route_paths_joint_ok(const KRoute& g, int32_t n_goals, int64_t n_queries,
+                                int32_t span) {
+    const int st = route_joint_ok(g, n_goals);
+    if (st) return st;
+    if (n_queries < 0) return fail(UAM_E_INVALID, "route n_queries < 0");
+    if (span < 0 || span > UAM_ROUTE_SPAN_MAX)
+        return fail(UAM_E_INVALID, "joint route span %d outside [0, %d]", span,
+                    UAM_ROUTE_SPAN_MAX);
+    return UAM_OK;
+}
+
+// -- the fields --
+// what a field call carves from its workspace for the relaxation
+struct RouteField {
+    double* c;
+    uint32_t* flags;
+    int32_t* lists;
+    int32_t* ctl;
+};
+
+// A field call's checks after the grid's and the goals', in their order: a NULL buffer (names
+// lists them), the workspace's size, the alignments (misaligned: any but the workspace's own
+// 256 B; align_msg names them all).
+static int route_field_args_ok(const char* what, const char* fn, bool null_arg, const char* names,
+                               const void* workspace, int64_t have, int64_t need,
+                               bool misaligned, const char* align_msg) {
+    if (null_arg) return fail(UAM_E_INVALID, "%s: %s is NULL", fn, names);
+    if (have < need)
+        return fail(UAM_E_INVALID, "%s workspace %lld bytes < %lld", what, (long long)have,
+                    (long long)need);
+    if (((uintptr_t)workspace & 255) || misaligned) return fail(UAM_E_INVALID, "%s", align_msg);
+    return UAM_OK;
+}
+
+// ... and its first steps under the caller's DeviceGuard: the LDS limit of k_route_relax<64>
+// where the call runs that tile, the pinned word of the round loop, the workspace carved
+static int route_field_open(uam_ctx* ctx, bool tile64, void* workspace, const R9Ws& ws,
+                            RouteField* f) {
+    int st;
+    if (tile64 && (st = raise_lds(ctx, k_route_relax<64>, 2 * 66 * 66 * (int)sizeof(double))))
+        return st;
+    if (!ctx->h_route) HIP_TRY(hipHostMalloc((void**)&ctx->h_route, 64, hipHostMallocDefault));
+    char* base = (char*)workspace;
+    f->c = (double*)(base + ws.c_off);
+    f->flags = (uint32_t*)(base + ws.flags_off);
+    f->lists = (int32_t*)(base + ws.lists_off);
+    f->ctl = (int32_t*)(base + ws.ctl_off);
+    return UAM_OK;
+}
+
+// The relaxation rounds of one field from its start state (list 0, ctl[0]) to convergence:
+// launch(n, cur) is one round over the n active tiles of list cur (of nt tiles in all), the
+// host reading the next round's count after each.  what is the grid's name in the messages,
+// which names the field in the max_rounds one; visits is the context's counter of the grid.
+template <typename Launch>
+static int route_relax_rounds(uam_ctx* ctx, hipStream_t s, const int32_t* ctl, int nt,
+                              int64_t max_rounds, const char* what, const char* which,
+                              int64_t* visits, int64_t* rounds, Launch launch) {
     int cur = 0;
     for (int64_t r = 0;; ++r) {
         // the active tiles of this round (the one word the host waits for)
@@ -9070,25 +9198,121 @@ static int route_relax_rounds(uam_ctx* ctx, hipStream_t s, const double* c, doub
         HIP_TRY(hipStreamSynchronize(s));
         const int32_t n = *(volatile int32_t*)ctx->h_route;
         if (n < 0 || n > nt)
-            return fail(UAM_E_HIP, "route field: active-tile count %d outside [0, %d]", n, nt);
+            return fail(UAM_E_HIP, "%s field: active-tile count %d outside [0, %d]", what, n, nt);
         if (n == 0) break;
         if (r >= max_rounds)
             return fail(UAM_E_STATE,
-                        "route field %s has not converged within max_rounds = %lld "
-                        "rounds (%d tiles still active)", what, (long long)max_rounds, n);
-        if (T == 16)
-            route_relax_launch<16>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
-        else if (T == 32)
-            route_relax_launch<32>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
-        else
-            route_relax_launch<64>(n, s, c, d, g, ntx, nty, flags, lists, ctl, cur, inner);
+                        "%s field %s has not converged within max_rounds = %lld "
+                        "rounds (%d tiles still active)", what, which, (long long)max_rounds, n);
+        launch(n, cur);
         HIP_TRY(hipGetLastError());
         ++*rounds;
-        ctx->route_visits += n;
+        *visits += n;
         cur ^= 1;
     }
     return UAM_OK;
 }
+
+// the raster's rounds: k_route_relax<T> at the context's tile
+static int route_relax(uam_ctx* ctx, hipStream_t s, const RouteField& f, double* d,
+                       const KRoute& g, int64_t max_rounds, const char* which, int64_t* rounds) {
+    const int T = ctx->k9_tile, inner = ctx->k9_inner;
+    const int ntx = r9_tiles(g.nx, T), nty = r9_tiles(g.ny, T);
+    return route_relax_rounds(
+        ctx, s, f.ctl, ntx * nty, max_rounds, "route", which, &ctx->route_visits, rounds,
+        [&](int n, int cur) {
+            if (T == 16)
+                route_relax_launch<16>(n, s, f.c, d, g, ntx, nty, f.flags, f.lists, f.ctl, cur,
+                                       inner);
+            else if (T == 32)
+                route_relax_launch<32>(n, s, f.c, d, g, ntx, nty, f.flags, f.lists, f.ctl, cur,
+                                       inner);
+            else
+                route_relax_launch<64>(n, s, f.c, d, g, ntx, nty, f.flags, f.lists, f.ctl, cur,
+                                       inner);
+        });
+}
+
+// -- the paths --
+// a device path call's first two checks
+static int route_paths_ctx_ok(const uam_ctx* ctx) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
+    return UAM_OK;
+}
+
+// A path call's checks after the grid's and the goals', in their order: n_queries, N (a host
+// twin's own argument; the device calls pass 0), then 1 for "nothing to do" (n_queries = 0:
+// the call returns UAM_OK), then a NULL buffer.
+static int route_queries_ok(const char* what, const char* fn, int64_t n_queries, int32_t N,
+                            bool null_arg) {
+    if (n_queries < 0) return fail(UAM_E_INVALID, "%s n_queries < 0", what);
+    if (N < 0) return fail(UAM_E_INVALID, "%s N < 0", what);
+    if (n_queries == 0) return 1;
+    if (null_arg) return fail(UAM_E_INVALID, "%s: a buffer is NULL", fn);
+    return UAM_OK;
+}
+
+// A path kernel's launch, launch(blocks, threads, stream): a lane per query for a trace, a wave
+// per query for a smoothing kernel.  kernel is the name left in the context.
+template <typename Launch>
+static int route_paths_launch(uam_ctx* ctx, const char* what, const char* kernel,
+                              int64_t n_queries, bool smooth, uam_stream stream, Launch launch) {
+    const int per = smooth ? R9S_WAVES : R9_THREADS;
+    if (n_queries >= ((int64_t)1 << 31) * per)
+        return fail(UAM_E_INVALID, "%s n_queries too large", what);
+    DeviceGuard dg(ctx->device);
+    launch(dim3((unsigned)((n_queries + per - 1) / per)),
+           dim3(smooth ? R9S_WAVES * 64 : R9_THREADS), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    ctx->last_kernel = kernel;
+    return UAM_OK;
+}
+
+// the host twin of either smoothing call, after its grid
+template <typename G>
+static int route_paths_smooth_host(const G& g, const char* fn, const uint32_t* bits,
+                                   const uint8_t* next, const double* goals, int32_t n_goals,
+                                   const double* starts, const int32_t* goal_idx,
+                                   int64_t n_queries, int32_t N, int32_t span, double* wp,
+                                   int32_t* status, int32_t* steps, int32_t* vertices) {
+    int st = route_smooth_ok(g, n_goals, n_queries, span);
+    if (st) return st;
+    if ((st = route_queries_ok(route_names(g).what, fn, n_queries, N,
+                               !bits || !next || !goals || !starts || !goal_idx || !wp || !status)))
+        return st < 0 ? st : UAM_OK;
+    std::vector<int32_t> cells, anchors;
+    for (int64_t q = 0; q < n_queries; ++q)
+        r9_smooth_host(g, bits, next, goals, n_goals, starts, goal_idx, q, N, span, wp, status,
+                       steps, vertices, cells, anchors);
+    return UAM_OK;
+}
+
+}  // extern "C++"
+
+// -- the calls: fields, paths, free bits and smoothed paths --
+int64_t uam_route_workspace_bytes(const uam_raster_desc* desc, const uam_route_params* params) {
+    KRoute g{};
+    if (route_setup(desc, params, &g)) return -1;
+    return r9_workspace(g.nx, g.ny).bytes;
+}
+
+int64_t uam_route_joint_workspace_bytes(const uam_raster_desc* desc,
+                                        const uam_route_params* params, int32_t n_goals) {
+    KRoute g{};
+    if (route_setup(desc, params, &g) || route_joint_ok(g, n_goals)) return -1;
+    return r9j_workspace(g.nx, g.ny).bytes;
+}
+
+int64_t uam_route3d_workspace_bytes(const uam_volume_desc* desc,
+                                    const uam_route3d_params* params) {
+    KRoute3 g{};
+    if (route3d_setup(desc, params, &g)) return -1;
+    return r9v_workspace(g).field.bytes;
+}
+
+int64_t uam_route_visits(const uam_ctx* ctx) { return ctx ? ctx->route_visits : 0; }
+int64_t uam_route3d_visits(const uam_ctx* ctx) { return ctx ? ctx->route3d_visits : 0; }
 
 int uam_route_field(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
                     const uam_route_params* params, const double* goals, int32_t n_goals,
@@ -9099,131 +9323,43 @@ int uam_route_field(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
     int st = route_setup(desc, params, &g);
     if (st) return st;
     if ((st = route_goals_ok(g, n_goals))) return st;
-    if (!rec || !goals || !dist || !next || !workspace)
-        return fail(UAM_E_INVALID,
-                    "uam_route_field: rec / goals / dist / next / workspace is NULL");
     const R9Ws ws = r9_workspace(g.nx, g.ny);
-    if (workspace_bytes < ws.bytes)
-        return fail(UAM_E_INVALID, "route workspace %lld bytes < %lld", (long long)workspace_bytes,
-                    (long long)ws.bytes);
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)dist & 7))
-        return fail(UAM_E_INVALID, "route workspace not 256-B or dist not 8-B aligned");
+    if ((st = route_field_args_ok("route", "uam_route_field",
+                                  !rec || !goals || !dist || !next || !workspace,
+                                  "rec / goals / dist / next / workspace", workspace,
+                                  workspace_bytes, ws.bytes, (uintptr_t)dist & 7,
+                                  "route workspace not 256-B or dist not 8-B aligned")))
+        return st;
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    const int T = ctx->k9_tile, inner = ctx->k9_inner;
-    if (T == 64 &&
-        (st = raise_lds(ctx, k_route_relax<64>, 2 * 66 * 66 * (int)sizeof(double))))
-        return st;
-    if (!ctx->h_route) HIP_TRY(hipHostMalloc((void**)&ctx->h_route, 64, hipHostMallocDefault));
-    char* base = (char*)workspace;
-    double* c = (double*)(base + ws.c_off);
-    uint32_t* flags = (uint32_t*)(base + ws.flags_off);
-    int32_t* lists = (int32_t*)(base + ws.lists_off);
-    int32_t* ctl = (int32_t*)(base + ws.ctl_off);
-    const int ntx = r9_tiles(g.nx, T), nty = r9_tiles(g.ny, T), nt = ntx * nty;
-    const int64_t cells = (int64_t)g.nx * g.ny;
+    const int T = ctx->k9_tile;
+    RouteField f;
+    if ((st = route_field_open(ctx, T == 64, workspace, ws, &f))) return st;
+    const int ntx = r9_tiles(g.nx, T), nt = ntx * r9_tiles(g.ny, T);
+    const int64_t cells = r9_count(g);
     const int64_t max_rounds = params->max_rounds ? params->max_rounds : cells;
     const int grid = grid_for(cells, R9_THREADS, 1 << 16);
     ctx->last_kernel = "K9";
     ctx->route_visits = 0;
-    hipLaunchKernelGGL(k_route_cost, dim3(grid), dim3(R9_THREADS), 0, s, (const uint4*)rec, g, c);
+    hipLaunchKernelGGL(k_route_cost, dim3(grid), dim3(R9_THREADS), 0, s, (const uint4*)rec, g,
+                       f.c);
     HIP_TRY(hipGetLastError());
     int64_t rounds = 0;
     for (int32_t gi = 0; gi < n_goals; ++gi) {
         double* d = dist + (int64_t)gi * cells;
         const double* goal = goals + 2 * (int64_t)gi;
-        hipLaunchKernelGGL(k_route_init, dim3(grid), dim3(R9_THREADS), 0, s, c, g, goal, d, T, ntx,
-                           nt, flags, lists, ctl);
+        hipLaunchKernelGGL(k_route_init, dim3(grid), dim3(R9_THREADS), 0, s, f.c, g, goal, d, T,
+                           ntx, nt, f.flags, f.lists, f.ctl);
         HIP_TRY(hipGetLastError());
-        char what[32];
-        snprintf(what, sizeof what, "of goal %d", gi);
-        if ((st = route_relax_rounds(ctx, s, c, d, g, T, inner, ntx, nty, flags, lists, ctl,
-                                     max_rounds, what, &rounds)))
-            return st;
-        hipLaunchKernelGGL(k_route_next, dim3(grid), dim3(R9_THREADS), 0, s, c, d, g, goal,
+        char which[32];
+        snprintf(which, sizeof which, "of goal %d", gi);
+        if ((st = route_relax(ctx, s, f, d, g, max_rounds, which, &rounds))) return st;
+        hipLaunchKernelGGL(k_route_next, dim3(grid), dim3(R9_THREADS), 0, s, f.c, d, g, goal,
                            next + (int64_t)gi * cells);
         HIP_TRY(hipGetLastError());
     }
     if (rounds_out) *rounds_out = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
     return UAM_OK;
-}
-
-int uam_route_paths(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
-                    const uam_route_params* params, const uint8_t* next, const double* goals,
-                    int32_t n_goals, const double* starts, const int32_t* goal_idx,
-                    int64_t n_queries, double* wp, int32_t* status, int32_t* steps,
-                    uam_stream stream) {
-    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
-    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
-    KRoute g{};
-    int st = route_setup(desc, params, &g);
-    if (st) return st;
-    if ((st = route_goals_ok(g, n_goals))) return st;
-    if (n_queries < 0) return fail(UAM_E_INVALID, "route n_queries < 0");
-    if (n_queries == 0) return UAM_OK;
-    if (!rec || !next || !goals || !starts || !goal_idx || !wp || !status)
-        return fail(UAM_E_INVALID, "uam_route_paths: a buffer is NULL");
-    if (n_queries >= ((int64_t)1 << 31) * R9_THREADS)
-        return fail(UAM_E_INVALID, "route n_queries too large");
-    DeviceGuard dg(ctx->device);
-    const int64_t blocks = (n_queries + R9_THREADS - 1) / R9_THREADS;
-    hipLaunchKernelGGL(k_route_trace, dim3((unsigned)blocks), dim3(R9_THREADS), 0,
-                       (hipStream_t)stream, g, (const uint4*)rec, next, goals, n_goals, starts,
-                       goal_idx, n_queries, ctx->kp.N, wp, status, steps);
-    HIP_TRY(hipGetLastError());
-    ctx->last_kernel = "K9t";
-    return UAM_OK;
-}
-
-int uam_route_field_host(const uam_raster_desc* desc, const void* rec,
-                         const uam_route_params* params, const double* goals, int32_t n_goals,
-                         double* dist, uint8_t* next) {
-    KRoute g{};
-    int st = route_setup(desc, params, &g);
-    if (st) return st;
-    if ((st = route_goals_ok(g, n_goals))) return st;
-    if (!rec || !goals || !dist || !next)
-        return fail(UAM_E_INVALID, "uam_route_field_host: rec / goals / dist / next is NULL");
-    r9_field_host(g, (const uint4*)rec, goals, n_goals, dist, next);
-    return UAM_OK;
-}
-
-int uam_route_paths_host(const uam_raster_desc* desc, const void* rec,
-                         const uam_route_params* params, const uint8_t* next,
-                         const double* goals, int32_t n_goals, const double* starts,
-                         const int32_t* goal_idx, int64_t n_queries, int32_t N, double* wp,
-                         int32_t* status, int32_t* steps) {
-    KRoute g{};
-    int st = route_setup(desc, params, &g);
-    if (st) return st;
-    if ((st = route_goals_ok(g, n_goals))) return st;
-    if (n_queries < 0 || N < 0) return fail(UAM_E_INVALID, "route n_queries or N < 0");
-    if (n_queries == 0) return UAM_OK;
-    if (!rec || !next || !goals || !starts || !goal_idx || !wp || !status)
-        return fail(UAM_E_INVALID, "uam_route_paths_host: a buffer is NULL");
-    for (int64_t q = 0; q < n_queries; ++q)
-        r9_trace(g, (const uint4*)rec, next, goals, n_goals, starts, goal_idx, q, N, wp, status,
-                 steps);
-    return UAM_OK;
-}
-
-// ---- K9j: the joint route field (k9_joint.inc) ------------------------------------------------
-// parents and owners are int32 and the smoothing kernel forms a + span
-static int route_joint_ok(const KRoute& g, int32_t n_goals) {
-    if (n_goals < 1 || n_goals > R9J_GOALS_MAX)
-        return fail(UAM_E_INVALID, "joint route n_goals %d outside [1, %d]", n_goals,
-                    R9J_GOALS_MAX);
-    if ((int64_t)g.nx * g.ny > (int64_t)INT32_MAX - UAM_ROUTE_SPAN_MAX)
-        return fail(UAM_E_INVALID, "joint route field needs nx*ny <= 2^31 - 1 - %d",
-                    UAM_ROUTE_SPAN_MAX);
-    return UAM_OK;
-}
-
-int64_t uam_route_joint_workspace_bytes(const uam_raster_desc* desc,
-                                        const uam_route_params* params, int32_t n_goals) {
-    KRoute g{};
-    if (route_setup(desc, params, &g) || route_joint_ok(g, n_goals)) return -1;
-    return r9j_workspace(g.nx, g.ny).bytes;
 }
 
 int uam_route_field_joint(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
@@ -9235,52 +9371,43 @@ int uam_route_field_joint(uam_ctx* ctx, const uam_raster_desc* desc, const void*
     int st = route_setup(desc, params, &g);
     if (st) return st;
     if ((st = route_joint_ok(g, n_goals))) return st;
-    if (!rec || !goals || !dist || !next || !owner || !workspace)
-        return fail(UAM_E_INVALID,
-                    "uam_route_field_joint: rec / goals / dist / next / owner / workspace is NULL");
     const R9jWs ws = r9j_workspace(g.nx, g.ny);
-    if (workspace_bytes < ws.bytes)
-        return fail(UAM_E_INVALID, "joint route workspace %lld bytes < %lld",
-                    (long long)workspace_bytes, (long long)ws.bytes);
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)dist & 7) || ((uintptr_t)owner & 3))
-        return fail(UAM_E_INVALID,
-                    "joint route workspace not 256-B, dist not 8-B or owner not 4-B aligned");
+    if ((st = route_field_args_ok(
+             "joint route", "uam_route_field_joint",
+             !rec || !goals || !dist || !next || !owner || !workspace,
+             "rec / goals / dist / next / owner / workspace", workspace, workspace_bytes, ws.bytes,
+             ((uintptr_t)dist & 7) || ((uintptr_t)owner & 3),
+             "joint route workspace not 256-B, dist not 8-B or owner not 4-B aligned")))
+        return st;
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    const int T = ctx->k9_tile, inner = ctx->k9_inner;
-    if (T == 64 &&
-        (st = raise_lds(ctx, k_route_relax<64>, 2 * 66 * 66 * (int)sizeof(double))))
-        return st;
-    if (!ctx->h_route) HIP_TRY(hipHostMalloc((void**)&ctx->h_route, 64, hipHostMallocDefault));
-    char* base = (char*)workspace;
-    double* c = (double*)(base + ws.field.c_off);
-    uint32_t* flags = (uint32_t*)(base + ws.field.flags_off);
-    int32_t* lists = (int32_t*)(base + ws.field.lists_off);
-    int32_t* ctl = (int32_t*)(base + ws.field.ctl_off);
-    int32_t* parent = (int32_t*)(base + ws.parent_off);
-    const int ntx = r9_tiles(g.nx, T), nty = r9_tiles(g.ny, T), nt = ntx * nty;
-    const int64_t cells = (int64_t)g.nx * g.ny;
+    const int T = ctx->k9_tile;
+    RouteField f;
+    if ((st = route_field_open(ctx, T == 64, workspace, ws.field, &f))) return st;
+    int32_t* parent = (int32_t*)((char*)workspace + ws.parent_off);
+    const int ntx = r9_tiles(g.nx, T), nt = ntx * r9_tiles(g.ny, T);
+    const int64_t cells = r9_count(g);
     const int64_t max_rounds = params->max_rounds ? params->max_rounds : cells;
     const int grid = grid_for(cells, R9_THREADS, 1 << 16);
     const int ggrid = (n_goals + R9_THREADS - 1) / R9_THREADS;
     ctx->last_kernel = "K9j";
     ctx->route_visits = 0;
-    hipLaunchKernelGGL(k_route_cost, dim3(grid), dim3(R9_THREADS), 0, s, (const uint4*)rec, g, c);
+    hipLaunchKernelGGL(k_route_cost, dim3(grid), dim3(R9_THREADS), 0, s, (const uint4*)rec, g,
+                       f.c);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_route_joint_clear, dim3(grid), dim3(R9_THREADS), 0, s, g, dist, nt, flags,
-                       ctl);
+    hipLaunchKernelGGL(k_route_joint_clear, dim3(grid), dim3(R9_THREADS), 0, s, g, dist, nt,
+                       f.flags, f.ctl);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_route_joint_seed, dim3(ggrid), dim3(R9_THREADS), 0, s, c, g, goals,
-                       n_goals, dist, T, ntx, flags, lists, ctl);
+    hipLaunchKernelGGL(k_route_joint_seed, dim3(ggrid), dim3(R9_THREADS), 0, s, f.c, g, goals,
+                       n_goals, dist, T, ntx, f.flags, f.lists, f.ctl);
     HIP_TRY(hipGetLastError());
     int64_t rounds = 0;
-    if ((st = route_relax_rounds(ctx, s, c, dist, g, T, inner, ntx, nty, flags, lists, ctl,
-                                 max_rounds, "of the goals jointly", &rounds)))
+    if ((st = route_relax(ctx, s, f, dist, g, max_rounds, "of the goals jointly", &rounds)))
         return st;
-    hipLaunchKernelGGL(k_route_joint_next, dim3(grid), dim3(R9_THREADS), 0, s, c, dist, g, next,
+    hipLaunchKernelGGL(k_route_joint_next, dim3(grid), dim3(R9_THREADS), 0, s, f.c, dist, g, next,
                        owner);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_route_joint_mark, dim3(ggrid), dim3(R9_THREADS), 0, s, c, g, goals,
+    hipLaunchKernelGGL(k_route_joint_mark, dim3(ggrid), dim3(R9_THREADS), 0, s, f.c, g, goals,
                        n_goals, next, owner);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_route_joint_parent, dim3(grid), dim3(R9_THREADS), 0, s, g, next, parent,
@@ -9296,48 +9423,84 @@ int uam_route_field_joint(uam_ctx* ctx, const uam_raster_desc* desc, const void*
     return UAM_OK;
 }
 
-static int route_paths_joint_ok(const KRoute& g, int32_t n_goals, int64_t n_queries,
-                                int32_t span) {
-    const int st = route_joint_ok(g, n_goals);
+int uam_route3d_field(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol,
+                      const uam_route3d_params* params, const double* goals, int32_t n_goals,
+                      double* dist, uint8_t* next, void* workspace, int64_t workspace_bytes,
+                      int32_t* rounds_out, uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
     if (st) return st;
-    if (n_queries < 0) return fail(UAM_E_INVALID, "route n_queries < 0");
-    if (span < 0 || span > UAM_ROUTE_SPAN_MAX)
-        return fail(UAM_E_INVALID, "joint route span %d outside [0, %d]", span,
-                    UAM_ROUTE_SPAN_MAX);
+    if ((st = route_goals_ok(g, n_goals))) return st;
+    const R9vWs ws = r9v_workspace(g);
+    if ((st = route_field_args_ok(
+             "route3d", "uam_route3d_field", !vol || !goals || !dist || !next || !workspace,
+             "vol / goals / dist / next / workspace", workspace, workspace_bytes, ws.field.bytes,
+             ((uintptr_t)vol & 255) || ((uintptr_t)dist & 7),
+             "route3d workspace or volume not 256-B or dist not 8-B aligned")))
+        return st;
+    DeviceGuard dg(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int TXY = ctx->k9v_tile_xy, TZ = ctx->k9v_tile_z, inner = ctx->k9v_inner;
+    RouteField f;
+    if ((st = route_field_open(ctx, false, workspace, ws.field, &f))) return st;
+    const R9vVolume v = route3d_volume(desc, vol);
+    uint32_t* mask = (uint32_t*)((char*)workspace + ws.mask_off);
+    const int ntx = r9_tiles(g.nx, TXY), nty = r9_tiles(g.ny, TXY), ntz = r9_tiles(g.nz, TZ);
+    const int nt = ntx * nty * ntz;
+    const int64_t voxels = r9_count(g);
+    const int64_t max_rounds = params->max_rounds ? params->max_rounds : voxels;
+    const int grid = grid_for(voxels, R9_THREADS, 1 << 16);
+    ctx->last_kernel = "K9v";
+    ctx->route3d_visits = 0;
+    hipLaunchKernelGGL(k_route3_cost, dim3(grid), dim3(R9_THREADS), 0, s, v.vox, v.col, g, f.c);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route3_mask, dim3(grid), dim3(R9_THREADS), 0, s, f.c, g, mask);
+    HIP_TRY(hipGetLastError());
+    int64_t rounds = 0;
+    for (int32_t gi = 0; gi < n_goals; ++gi) {
+        double* d = dist + (int64_t)gi * voxels;
+        const double* goal = goals + 3 * (int64_t)gi;
+        hipLaunchKernelGGL(k_route3_init, dim3(grid), dim3(R9_THREADS), 0, s, f.c, g, goal, d, TXY,
+                           TZ, ntx, ntz, nt, f.flags, f.lists, f.ctl);
+        HIP_TRY(hipGetLastError());
+        char which[32];
+        snprintf(which, sizeof which, "of goal %d", gi);
+        st = route_relax_rounds(
+            ctx, s, f.ctl, nt, max_rounds, "route3d", which, &ctx->route3d_visits, &rounds,
+            [&](int n, int cur) {
+                if (TXY == 8 && TZ == 4)
+                    route3_relax_launch<8, 4>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags,
+                                              f.lists, f.ctl, cur, inner);
+                else if (TXY == 8)
+                    route3_relax_launch<8, 8>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags,
+                                              f.lists, f.ctl, cur, inner);
+                else if (TZ == 4)
+                    route3_relax_launch<16, 4>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags,
+                                               f.lists, f.ctl, cur, inner);
+                else
+                    route3_relax_launch<16, 8>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags,
+                                               f.lists, f.ctl, cur, inner);
+            });
+        if (st) return st;
+        hipLaunchKernelGGL(k_route3_next, dim3(grid), dim3(R9_THREADS), 0, s, f.c, mask, d, g, goal,
+                           next + (int64_t)gi * voxels);
+        HIP_TRY(hipGetLastError());
+    }
+    if (rounds_out) *rounds_out = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
     return UAM_OK;
 }
 
-int uam_route_paths_joint(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
-                          const uam_route_params* params, const uint32_t* bits,
-                          const uint8_t* next, const int32_t* owner, const double* goals,
-                          int32_t n_goals, const double* starts, int64_t n_queries, int32_t span,
-                          double* wp, int32_t* status, int32_t* steps, int32_t* vertices,
-                          int32_t* goal_out, uam_stream stream) {
-    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
-    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
+int uam_route_field_host(const uam_raster_desc* desc, const void* rec,
+                         const uam_route_params* params, const double* goals, int32_t n_goals,
+                         double* dist, uint8_t* next) {
     KRoute g{};
     int st = route_setup(desc, params, &g);
     if (st) return st;
-    if ((st = route_paths_joint_ok(g, n_goals, n_queries, span))) return st;
-    if (n_queries == 0) return UAM_OK;
-    if (!(span ? (const void*)bits : rec) || !next || !owner || !goals || !starts || !wp ||
-        !status)
-        return fail(UAM_E_INVALID, "uam_route_paths_joint: a buffer is NULL");
-    const int per = span ? R9S_WAVES : R9_THREADS;
-    if (n_queries >= ((int64_t)1 << 31) * per)
-        return fail(UAM_E_INVALID, "route n_queries too large");
-    DeviceGuard dg(ctx->device);
-    const int64_t blocks = (n_queries + per - 1) / per;
-    if (span)
-        hipLaunchKernelGGL(k_route_joint_smooth, dim3((unsigned)blocks), dim3(R9S_WAVES * 64), 0,
-                           (hipStream_t)stream, g, bits, next, owner, goals, n_goals, starts,
-                           n_queries, ctx->kp.N, span, wp, status, steps, vertices, goal_out);
-    else
-        hipLaunchKernelGGL(k_route_joint_trace, dim3((unsigned)blocks), dim3(R9_THREADS), 0,
-                           (hipStream_t)stream, g, (const uint4*)rec, next, owner, goals, n_goals,
-                           starts, n_queries, ctx->kp.N, wp, status, steps, vertices, goal_out);
-    HIP_TRY(hipGetLastError());
-    ctx->last_kernel = span ? "K9js" : "K9jt";
+    if ((st = route_goals_ok(g, n_goals))) return st;
+    if (!rec || !goals || !dist || !next)
+        return fail(UAM_E_INVALID, "uam_route_field_host: rec / goals / dist / next is NULL");
+    r9_field_host(g, (const uint4*)rec, goals, n_goals, dist, next);
     return UAM_OK;
 }
 
@@ -9355,6 +9518,85 @@ int uam_route_field_joint_host(const uam_raster_desc* desc, const void* rec,
     return UAM_OK;
 }
 
+int uam_route3d_field_host(const uam_volume_desc* desc, const void* vol,
+                           const uam_route3d_params* params, const double* goals,
+                           int32_t n_goals, double* dist, uint8_t* next) {
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_goals_ok(g, n_goals))) return st;
+    if (!vol || !goals || !dist || !next)
+        return fail(UAM_E_INVALID, "uam_route3d_field_host: vol / goals / dist / next is NULL");
+    const R9vVolume v = route3d_volume(desc, vol);
+    r9v_field_host(g, v.vox, v.col, goals, n_goals, dist, next);
+    return UAM_OK;
+}
+
+int uam_route_paths(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
+                    const uam_route_params* params, const uint8_t* next, const double* goals,
+                    int32_t n_goals, const double* starts, const int32_t* goal_idx,
+                    int64_t n_queries, double* wp, int32_t* status, int32_t* steps,
+                    uam_stream stream) {
+    KRoute g{};
+    int st = route_paths_ctx_ok(ctx);
+    if (st || (st = route_setup(desc, params, &g)) || (st = route_goals_ok(g, n_goals))) return st;
+    if ((st = route_queries_ok("route", "uam_route_paths", n_queries, 0,
+                               !rec || !next || !goals || !starts || !goal_idx || !wp || !status)))
+        return st < 0 ? st : UAM_OK;
+    return route_paths_launch(
+        ctx, "route", "K9t", n_queries, false, stream, [&](dim3 blocks, dim3 threads, hipStream_t s) {
+            hipLaunchKernelGGL(k_route_trace, blocks, threads, 0, s, g, (const uint4*)rec, next,
+                               goals, n_goals, starts, goal_idx, n_queries, ctx->kp.N, wp, status,
+                               steps);
+        });
+}
+
+int uam_route_paths_host(const uam_raster_desc* desc, const void* rec,
+                         const uam_route_params* params, const uint8_t* next,
+                         const double* goals, int32_t n_goals, const double* starts,
+                         const int32_t* goal_idx, int64_t n_queries, int32_t N, double* wp,
+                         int32_t* status, int32_t* steps) {
+    KRoute g{};
+    int st = route_setup(desc, params, &g);
+    if (st || (st = route_goals_ok(g, n_goals))) return st;
+    if ((st = route_queries_ok("route", "uam_route_paths_host", n_queries, N,
+                               !rec || !next || !goals || !starts || !goal_idx || !wp || !status)))
+        return st < 0 ? st : UAM_OK;
+    for (int64_t q = 0; q < n_queries; ++q)
+        r9_trace(g, (const uint4*)rec, next, goals, n_goals, starts, goal_idx, q, N, wp, status,
+                 steps);
+    return UAM_OK;
+}
+
+int uam_route_paths_joint(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
+                          const uam_route_params* params, const uint32_t* bits,
+                          const uint8_t* next, const int32_t* owner, const double* goals,
+                          int32_t n_goals, const double* starts, int64_t n_queries, int32_t span,
+                          double* wp, int32_t* status, int32_t* steps, int32_t* vertices,
+                          int32_t* goal_out, uam_stream stream) {
+    KRoute g{};
+    int st = route_paths_ctx_ok(ctx);
+    if (st || (st = route_setup(desc, params, &g)) ||
+        (st = route_paths_joint_ok(g, n_goals, n_queries, span)))
+        return st;
+    if ((st = route_queries_ok("route", "uam_route_paths_joint", n_queries, 0,
+                               !(span ? (const void*)bits : rec) || !next || !owner || !goals ||
+                                   !starts || !wp || !status)))
+        return st < 0 ? st : UAM_OK;
+    return route_paths_launch(
+        ctx, "route", span ? "K9js" : "K9jt", n_queries, span != 0, stream,
+        [&](dim3 blocks, dim3 threads, hipStream_t s) {
+            if (span)
+                hipLaunchKernelGGL(k_route_joint_smooth, blocks, threads, 0, s, g, bits, next,
+                                   owner, goals, n_goals, starts, n_queries, ctx->kp.N, span, wp,
+                                   status, steps, vertices, goal_out);
+            else
+                hipLaunchKernelGGL(k_route_joint_trace, blocks, threads, 0, s, g,
+                                   (const uint4*)rec, next, owner, goals, n_goals, starts,
+                                   n_queries, ctx->kp.N, wp, status, steps, vertices, goal_out);
+        });
+}
+
 int uam_route_paths_joint_host(const uam_raster_desc* desc, const void* rec,
                                const uam_route_params* params, const uint32_t* bits,
                                const uint8_t* next, const int32_t* owner, const double* goals,
@@ -9363,158 +9605,19 @@ int uam_route_paths_joint_host(const uam_raster_desc* desc, const void* rec,
                                int32_t* steps, int32_t* vertices, int32_t* goal_out) {
     KRoute g{};
     int st = route_setup(desc, params, &g);
-    if (st) return st;
-    if ((st = route_paths_joint_ok(g, n_goals, n_queries, span))) return st;
-    if (N < 0) return fail(UAM_E_INVALID, "route N < 0");
-    if (n_queries == 0) return UAM_OK;
-    if (!(span ? (const void*)bits : rec) || !next || !owner || !goals || !starts || !wp ||
-        !status)
-        return fail(UAM_E_INVALID, "uam_route_paths_joint_host: a buffer is NULL");
+    if (st || (st = route_paths_joint_ok(g, n_goals, n_queries, span))) return st;
+    if ((st = route_queries_ok("route", "uam_route_paths_joint_host", n_queries, N,
+                               !(span ? (const void*)bits : rec) || !next || !owner || !goals ||
+                                   !starts || !wp || !status)))
+        return st < 0 ? st : UAM_OK;
     std::vector<int32_t> cells, anchors;
     for (int64_t q = 0; q < n_queries; ++q)
         if (span)
-            r9s_smooth_host<true>(g, bits, next, goals, n_goals, starts, owner, q, N, span, wp,
-                                  status, steps, vertices, cells, anchors, goal_out);
+            r9_smooth_host<true>(g, bits, next, goals, n_goals, starts, owner, q, N, span, wp,
+                                 status, steps, vertices, cells, anchors, goal_out);
         else
             r9_trace<true>(g, (const uint4*)rec, next, goals, n_goals, starts, owner, q, N, wp,
                            status, steps, vertices, goal_out);
-    return UAM_OK;
-}
-
-// ---- K9v: route seeds in the volume (k9v_route.inc) --------------------------------------------
-// the descriptor and the parameters checked and folded into the kernels' KRoute3
-static int route3d_setup(const uam_volume_desc* desc, const uam_route3d_params* p, KRoute3* g) {
-    if (!p) return fail(UAM_E_INVALID, "route3d params is NULL");
-    if (p->abi_version != UAM_ABI_VERSION)
-        return fail(UAM_E_VERSION, "route3d params abi_version %u != %d", p->abi_version,
-                    UAM_ABI_VERSION);
-    KVolume kv;
-    const int st = make_kvolume(desc, &kv);
-    if (st) return st;
-    if (!(p->lambda >= 0.0) || !(p->lambda < r9_inf()))
-        return fail(UAM_E_INVALID, "route3d lambda must be finite and >= 0");
-    if (p->inflate < 0 || p->inflate > R9_INFLATE_MAX)
-        return fail(UAM_E_INVALID, "route3d inflate %d outside [0, %d]", p->inflate,
-                    R9_INFLATE_MAX);
-    if (p->max_rounds < 0)
-        return fail(UAM_E_INVALID, "route3d max_rounds %d < 0", p->max_rounds);
-    if (!(p->agl >= 0.0) || !(p->agl < r9_inf()))
-        return fail(UAM_E_INVALID, "route3d agl must be finite and >= 0");
-    if (!(p->z_scale > 0.0) || !(p->z_scale < r9_inf()))
-        return fail(UAM_E_INVALID, "route3d z_scale must be finite and > 0");
-    g->nx = kv.nx, g->ny = kv.ny, g->nz = kv.nz;
-    g->x0 = kv.x0, g->y_top = kv.y_top, g->dx = desc->dx, g->dy = desc->dy;
-    g->inv_dx = kv.inv_dx, g->inv_dy = kv.inv_dy;
-    g->z0 = kv.z0, g->dz = kv.dz, g->inv_dz = kv.inv_dz;
-    g->lambda = p->lambda, g->agl = p->agl, g->kappa = p->z_scale;
-    g->block_flags = p->block_flags;
-    g->inflate = p->inflate;
-    r9v_set_lengths(g);
-    return UAM_OK;
-}
-
-static int route3d_goals_ok(const KRoute3& g, int32_t n_goals) {
-    if (n_goals < 1) return fail(UAM_E_INVALID, "route3d n_goals %d < 1", n_goals);
-    if ((int64_t)n_goals * r9v_voxels(g) >= ((int64_t)1 << 40))
-        return fail(UAM_E_INVALID, "route3d fields of 2^40 or more voxels");
-    return UAM_OK;
-}
-
-int64_t uam_route3d_workspace_bytes(const uam_volume_desc* desc,
-                                    const uam_route3d_params* params) {
-    KRoute3 g{};
-    if (route3d_setup(desc, params, &g)) return -1;
-    return r9v_workspace(g).bytes;
-}
-
-int64_t uam_route3d_visits(const uam_ctx* ctx) { return ctx ? ctx->route3d_visits : 0; }
-
-int uam_route3d_field(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol,
-                      const uam_route3d_params* params, const double* goals, int32_t n_goals,
-                      double* dist, uint8_t* next, void* workspace, int64_t workspace_bytes,
-                      int32_t* rounds_out, uam_stream stream) {
-    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
-    KRoute3 g{};
-    int st = route3d_setup(desc, params, &g);
-    if (st) return st;
-    if ((st = route3d_goals_ok(g, n_goals))) return st;
-    if (!vol || !goals || !dist || !next || !workspace)
-        return fail(UAM_E_INVALID,
-                    "uam_route3d_field: vol / goals / dist / next / workspace is NULL");
-    const R9vWs ws = r9v_workspace(g);
-    if (workspace_bytes < ws.bytes)
-        return fail(UAM_E_INVALID, "route3d workspace %lld bytes < %lld",
-                    (long long)workspace_bytes, (long long)ws.bytes);
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)vol & 255) || ((uintptr_t)dist & 7))
-        return fail(UAM_E_INVALID,
-                    "route3d workspace or volume not 256-B or dist not 8-B aligned");
-    DeviceGuard dg(ctx->device);
-    hipStream_t s = (hipStream_t)stream;
-    const int TXY = ctx->k9v_tile_xy, TZ = ctx->k9v_tile_z, inner = ctx->k9v_inner;
-    if (!ctx->h_route) HIP_TRY(hipHostMalloc((void**)&ctx->h_route, 64, hipHostMallocDefault));
-    const uint2* vox = (const uint2*)vol;
-    const uint2* col = (const uint2*)((const char*)vol + vol_col_offset(desc));
-    char* base = (char*)workspace;
-    double* c = (double*)(base + ws.c_off);
-    uint32_t* mask = (uint32_t*)(base + ws.mask_off);
-    uint32_t* flags = (uint32_t*)(base + ws.flags_off);
-    int32_t* lists = (int32_t*)(base + ws.lists_off);
-    int32_t* ctl = (int32_t*)(base + ws.ctl_off);
-    const int ntx = r9_tiles(g.nx, TXY), nty = r9_tiles(g.ny, TXY), ntz = r9_tiles(g.nz, TZ);
-    const int nt = ntx * nty * ntz;
-    const int64_t voxels = r9v_voxels(g);
-    const int64_t max_rounds = params->max_rounds ? params->max_rounds : voxels;
-    const int grid = grid_for(voxels, R9_THREADS, 1 << 16);
-    ctx->last_kernel = "K9v";
-    ctx->route3d_visits = 0;
-    hipLaunchKernelGGL(k_route3_cost, dim3(grid), dim3(R9_THREADS), 0, s, vox, col, g, c);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_route3_mask, dim3(grid), dim3(R9_THREADS), 0, s, c, g, mask);
-    HIP_TRY(hipGetLastError());
-    int64_t rounds = 0;
-    for (int32_t gi = 0; gi < n_goals; ++gi) {
-        double* d = dist + (int64_t)gi * voxels;
-        const double* goal = goals + 3 * (int64_t)gi;
-        hipLaunchKernelGGL(k_route3_init, dim3(grid), dim3(R9_THREADS), 0, s, c, g, goal, d, TXY,
-                           TZ, ntx, ntz, nt, flags, lists, ctl);
-        HIP_TRY(hipGetLastError());
-        int cur = 0;
-        for (int64_t r = 0;; ++r) {
-            // the active tiles of this round (the one word the host waits for)
-            HIP_TRY(hipMemcpyAsync(ctx->h_route, ctl + cur, sizeof(int32_t),
-                                   hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            const int32_t n = *(volatile int32_t*)ctx->h_route;
-            if (n < 0 || n > nt)
-                return fail(UAM_E_HIP, "route3d field: active-tile count %d outside [0, %d]", n,
-                            nt);
-            if (n == 0) break;
-            if (r >= max_rounds)
-                return fail(UAM_E_STATE,
-                            "route3d field of goal %d has not converged within max_rounds = %lld "
-                            "rounds (%d tiles still active)", gi, (long long)max_rounds, n);
-            if (TXY == 8 && TZ == 4)
-                route3_relax_launch<8, 4>(n, s, c, mask, d, g, ntx, nty, ntz, flags, lists, ctl,
-                                          cur, inner);
-            else if (TXY == 8)
-                route3_relax_launch<8, 8>(n, s, c, mask, d, g, ntx, nty, ntz, flags, lists, ctl,
-                                          cur, inner);
-            else if (TZ == 4)
-                route3_relax_launch<16, 4>(n, s, c, mask, d, g, ntx, nty, ntz, flags, lists, ctl,
-                                           cur, inner);
-            else
-                route3_relax_launch<16, 8>(n, s, c, mask, d, g, ntx, nty, ntz, flags, lists, ctl,
-                                           cur, inner);
-            HIP_TRY(hipGetLastError());
-            ++rounds;
-            ctx->route3d_visits += n;
-            cur ^= 1;
-        }
-        hipLaunchKernelGGL(k_route3_next, dim3(grid), dim3(R9_THREADS), 0, s, c, mask, d, g, goal,
-                           next + (int64_t)gi * voxels);
-        HIP_TRY(hipGetLastError());
-    }
-    if (rounds_out) *rounds_out = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
     return UAM_OK;
 }
 
@@ -9523,42 +9626,21 @@ int uam_route3d_paths(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol
                       int32_t n_goals, const double* starts, const int32_t* goal_idx,
                       int64_t n_queries, double* wp3, int32_t* status, int32_t* steps,
                       uam_stream stream) {
-    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
-    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
     KRoute3 g{};
-    int st = route3d_setup(desc, params, &g);
-    if (st) return st;
-    if ((st = route3d_goals_ok(g, n_goals))) return st;
-    if (n_queries < 0) return fail(UAM_E_INVALID, "route3d n_queries < 0");
-    if (n_queries == 0) return UAM_OK;
-    if (!vol || !next || !goals || !starts || !goal_idx || !wp3 || !status)
-        return fail(UAM_E_INVALID, "uam_route3d_paths: a buffer is NULL");
+    int st = route_paths_ctx_ok(ctx);
+    if (st || (st = route3d_setup(desc, params, &g)) || (st = route_goals_ok(g, n_goals)))
+        return st;
+    if ((st = route_queries_ok("route3d", "uam_route3d_paths", n_queries, 0,
+                               !vol || !next || !goals || !starts || !goal_idx || !wp3 || !status)))
+        return st < 0 ? st : UAM_OK;
     if ((uintptr_t)vol & 255) return fail(UAM_E_INVALID, "route3d volume not 256-B aligned");
-    if (n_queries >= ((int64_t)1 << 31) * R9_THREADS)
-        return fail(UAM_E_INVALID, "route3d n_queries too large");
-    DeviceGuard dg(ctx->device);
-    const int64_t blocks = (n_queries + R9_THREADS - 1) / R9_THREADS;
-    hipLaunchKernelGGL(k_route3_trace, dim3((unsigned)blocks), dim3(R9_THREADS), 0,
-                       (hipStream_t)stream, g, (const uint2*)vol,
-                       (const uint2*)((const char*)vol + vol_col_offset(desc)), next, goals,
-                       n_goals, starts, goal_idx, n_queries, ctx->kp.N, wp3, status, steps);
-    HIP_TRY(hipGetLastError());
-    ctx->last_kernel = "K9vt";
-    return UAM_OK;
-}
-
-int uam_route3d_field_host(const uam_volume_desc* desc, const void* vol,
-                           const uam_route3d_params* params, const double* goals,
-                           int32_t n_goals, double* dist, uint8_t* next) {
-    KRoute3 g{};
-    int st = route3d_setup(desc, params, &g);
-    if (st) return st;
-    if ((st = route3d_goals_ok(g, n_goals))) return st;
-    if (!vol || !goals || !dist || !next)
-        return fail(UAM_E_INVALID, "uam_route3d_field_host: vol / goals / dist / next is NULL");
-    r9v_field_host(g, (const uint2*)vol, (const uint2*)((const char*)vol + vol_col_offset(desc)),
-                   goals, n_goals, dist, next);
-    return UAM_OK;
+    const R9vVolume v = route3d_volume(desc, vol);
+    return route_paths_launch(
+        ctx, "route3d", "K9vt", n_queries, false, stream,
+        [&](dim3 blocks, dim3 threads, hipStream_t s) {
+            hipLaunchKernelGGL(k_route3_trace, blocks, threads, 0, s, g, v.vox, v.col, next, goals,
+                               n_goals, starts, goal_idx, n_queries, ctx->kp.N, wp3, status, steps);
+        });
 }
 
 int uam_route3d_paths_host(const uam_volume_desc* desc, const void* vol,
@@ -9568,42 +9650,13 @@ int uam_route3d_paths_host(const uam_volume_desc* desc, const void* vol,
                            int32_t* status, int32_t* steps) {
     KRoute3 g{};
     int st = route3d_setup(desc, params, &g);
-    if (st) return st;
-    if ((st = route3d_goals_ok(g, n_goals))) return st;
-    if (n_queries < 0 || N < 0) return fail(UAM_E_INVALID, "route3d n_queries or N < 0");
-    if (n_queries == 0) return UAM_OK;
-    if (!vol || !next || !goals || !starts || !goal_idx || !wp3 || !status)
-        return fail(UAM_E_INVALID, "uam_route3d_paths_host: a buffer is NULL");
-    const uint2* vox = (const uint2*)vol;
-    const uint2* col = (const uint2*)((const char*)vol + vol_col_offset(desc));
+    if (st || (st = route_goals_ok(g, n_goals))) return st;
+    if ((st = route_queries_ok("route3d", "uam_route3d_paths_host", n_queries, N,
+                               !vol || !next || !goals || !starts || !goal_idx || !wp3 || !status)))
+        return st < 0 ? st : UAM_OK;
+    const R9vVolume v = route3d_volume(desc, vol);
     for (int64_t q = 0; q < n_queries; ++q)
-        r9v_trace(g, vox, col, next, goals, n_goals, starts, goal_idx, q, N, wp3, status, steps);
-    return UAM_OK;
-}
-
-// ---- K9b / K9s: shortcuts on the traced route (k9_smooth.inc) ---------------------------------
-// the grid alone (the smoothing calls take no uam_route_params: blocking comes from the bits)
-static int route_grid(const uam_raster_desc* desc, KRoute* g) {
-    KRaster kr{};
-    const int st = make_kraster(desc, &kr);
-    if (st) return st;
-    g->nx = kr.nx, g->ny = kr.ny;
-    g->x0 = kr.x0, g->y_top = kr.y_top, g->dx = kr.dx, g->dy = kr.dy;
-    g->inv_dx = kr.inv_dx, g->inv_dy = kr.inv_dy;
-    r9_set_lengths(g);
-    return UAM_OK;
-}
-
-static int route_smooth_ok(const KRoute& g, int32_t n_goals, int64_t n_queries, int32_t span) {
-    const int st = route_goals_ok(g, n_goals);
-    if (st) return st;
-    if (n_queries < 0) return fail(UAM_E_INVALID, "route n_queries < 0");
-    if (span < 1 || span > UAM_ROUTE_SPAN_MAX)
-        return fail(UAM_E_INVALID, "route span %d outside [1, %d]", span, UAM_ROUTE_SPAN_MAX);
-    // chain indices are int32 and the kernel forms a + span
-    if ((int64_t)g.nx * g.ny > (int64_t)INT32_MAX - UAM_ROUTE_SPAN_MAX)
-        return fail(UAM_E_INVALID, "route smoothing needs nx*ny <= 2^31 - 1 - %d",
-                    UAM_ROUTE_SPAN_MAX);
+        r9_trace(g, v, next, goals, n_goals, starts, goal_idx, q, N, wp3, status, steps);
     return UAM_OK;
 }
 
@@ -9611,6 +9664,12 @@ int64_t uam_route_free_bits_bytes(const uam_raster_desc* desc) {
     KRoute g{};
     if (route_grid(desc, &g)) return -1;
     return (int64_t)g.ny * r9s_wpr(g.nx) * 4;
+}
+
+int64_t uam_route3d_free_bits_bytes(const uam_volume_desc* desc) {
+    KVolume kv;
+    if (make_kvolume(desc, &kv)) return -1;
+    return (((int64_t)kv.nx * kv.ny * kv.nz + 31) >> 5) * 4;
 }
 
 int uam_route_free_bits(uam_ctx* ctx, const uam_raster_desc* desc, const void* rec,
@@ -9630,29 +9689,22 @@ int uam_route_free_bits(uam_ctx* ctx, const uam_raster_desc* desc, const void* r
     return UAM_OK;
 }
 
-int uam_route_paths_smooth(uam_ctx* ctx, const uam_raster_desc* desc, const uint32_t* bits,
-                           const uint8_t* next, const double* goals, int32_t n_goals,
-                           const double* starts, const int32_t* goal_idx, int64_t n_queries,
-                           int32_t span, double* wp, int32_t* status, int32_t* steps,
-                           int32_t* vertices, uam_stream stream) {
+int uam_route3d_free_bits(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol,
+                          const uam_route3d_params* params, uint32_t* bits, uam_stream stream) {
     if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
-    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
-    KRoute g{};
-    int st = route_grid(desc, &g);
+    KRoute3 g{};
+    const int st = route3d_setup(desc, params, &g);
     if (st) return st;
-    if ((st = route_smooth_ok(g, n_goals, n_queries, span))) return st;
-    if (n_queries == 0) return UAM_OK;
-    if (!bits || !next || !goals || !starts || !goal_idx || !wp || !status)
-        return fail(UAM_E_INVALID, "uam_route_paths_smooth: a buffer is NULL");
-    if (n_queries >= ((int64_t)1 << 31) * R9S_WAVES)
-        return fail(UAM_E_INVALID, "route n_queries too large");
+    if (!vol || !bits) return fail(UAM_E_INVALID, "uam_route3d_free_bits: vol / bits is NULL");
+    if (((uintptr_t)vol & 255) || ((uintptr_t)bits & 3))
+        return fail(UAM_E_INVALID, "route3d volume not 256-B or free bits not 4-B aligned");
     DeviceGuard dg(ctx->device);
-    const int64_t blocks = (n_queries + R9S_WAVES - 1) / R9S_WAVES;
-    hipLaunchKernelGGL(k_route_smooth, dim3((unsigned)blocks), dim3(R9S_WAVES * 64), 0,
-                       (hipStream_t)stream, g, bits, next, goals, n_goals, starts, goal_idx,
-                       n_queries, ctx->kp.N, span, wp, status, steps, vertices);
+    const R9vVolume v = route3d_volume(desc, vol);
+    const int64_t chunks = (r9_count(g) + 63) >> 6;
+    hipLaunchKernelGGL(k_route3_free_bits, dim3(grid_for(chunks * 64, R9_THREADS, 1 << 16)),
+                       dim3(R9_THREADS), 0, (hipStream_t)stream, v.vox, v.col, g, bits);
     HIP_TRY(hipGetLastError());
-    ctx->last_kernel = "K9s";
+    ctx->last_kernel = "K9vb";
     return UAM_OK;
 }
 
@@ -9662,15 +9714,64 @@ int uam_route_free_bits_host(const uam_raster_desc* desc, const void* rec,
     const int st = route_setup(desc, params, &g);
     if (st) return st;
     if (!rec || !bits) return fail(UAM_E_INVALID, "uam_route_free_bits_host: rec / bits is NULL");
-    const int wpr = r9s_wpr(g.nx);
-    for (int iy = 0; iy < g.ny; ++iy)
-        for (int w = 0; w < wpr; ++w) {
-            uint32_t m = 0u;
-            for (int b = 0; b < 32 && (int64_t)w * 32 + b < g.nx; ++b)
-                if (r9_cost(g, (const uint4*)rec, w * 32 + b, iy) < r9_inf()) m |= 1u << b;
-            bits[(int64_t)iy * wpr + w] = m;
-        }
+    r9s_free_bits_host(g, (const uint4*)rec, bits);
     return UAM_OK;
+}
+
+int uam_route3d_free_bits_host(const uam_volume_desc* desc, const void* vol,
+                               const uam_route3d_params* params, uint32_t* bits) {
+    KRoute3 g{};
+    const int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if (!vol || !bits)
+        return fail(UAM_E_INVALID, "uam_route3d_free_bits_host: vol / bits is NULL");
+    const R9vVolume v = route3d_volume(desc, vol);
+    r9vs_free_bits_host(g, v.vox, v.col, bits);
+    return UAM_OK;
+}
+
+int uam_route_paths_smooth(uam_ctx* ctx, const uam_raster_desc* desc, const uint32_t* bits,
+                           const uint8_t* next, const double* goals, int32_t n_goals,
+                           const double* starts, const int32_t* goal_idx, int64_t n_queries,
+                           int32_t span, double* wp, int32_t* status, int32_t* steps,
+                           int32_t* vertices, uam_stream stream) {
+    KRoute g{};
+    int st = route_paths_ctx_ok(ctx);
+    if (st || (st = route_grid(desc, &g)) ||
+        (st = route_smooth_ok(g, n_goals, n_queries, span)))
+        return st;
+    if ((st = route_queries_ok("route", "uam_route_paths_smooth", n_queries, 0,
+                               !bits || !next || !goals || !starts || !goal_idx || !wp || !status)))
+        return st < 0 ? st : UAM_OK;
+    return route_paths_launch(
+        ctx, "route", "K9s", n_queries, true, stream, [&](dim3 blocks, dim3 threads, hipStream_t s) {
+            hipLaunchKernelGGL(k_route_smooth, blocks, threads, 0, s, g, bits, next, goals, n_goals,
+                               starts, goal_idx, n_queries, ctx->kp.N, span, wp, status, steps,
+                               vertices);
+        });
+}
+
+int uam_route3d_paths_smooth(uam_ctx* ctx, const uam_volume_desc* desc,
+                             const uam_route3d_params* params, const uint32_t* bits,
+                             const uint8_t* next, const double* goals, int32_t n_goals,
+                             const double* starts, const int32_t* goal_idx, int64_t n_queries,
+                             int32_t span, double* wp3, int32_t* status, int32_t* steps,
+                             int32_t* vertices, uam_stream stream) {
+    KRoute3 g{};
+    int st = route_paths_ctx_ok(ctx);
+    if (st || (st = route3d_setup(desc, params, &g)) ||
+        (st = route_smooth_ok(g, n_goals, n_queries, span)))
+        return st;
+    if ((st = route_queries_ok("route3d", "uam_route3d_paths_smooth", n_queries, 0,
+                               !bits || !next || !goals || !starts || !goal_idx || !wp3 || !status)))
+        return st < 0 ? st : UAM_OK;
+    return route_paths_launch(
+        ctx, "route3d", "K9vs", n_queries, true, stream,
+        [&](dim3 blocks, dim3 threads, hipStream_t s) {
+            hipLaunchKernelGGL(k_route3_smooth, blocks, threads, 0, s, g, bits, next, goals,
+                               n_goals, starts, goal_idx, n_queries, ctx->kp.N, span, wp3, status,
+                               steps, vertices);
+        });
 }
 
 int uam_route_paths_smooth_host(const uam_raster_desc* desc, const uint32_t* bits,
@@ -9679,18 +9780,24 @@ int uam_route_paths_smooth_host(const uam_raster_desc* desc, const uint32_t* bit
                                 int64_t n_queries, int32_t N, int32_t span, double* wp,
                                 int32_t* status, int32_t* steps, int32_t* vertices) {
     KRoute g{};
-    int st = route_grid(desc, &g);
+    const int st = route_grid(desc, &g);
     if (st) return st;
-    if ((st = route_smooth_ok(g, n_goals, n_queries, span))) return st;
-    if (N < 0) return fail(UAM_E_INVALID, "route N < 0");
-    if (n_queries == 0) return UAM_OK;
-    if (!bits || !next || !goals || !starts || !goal_idx || !wp || !status)
-        return fail(UAM_E_INVALID, "uam_route_paths_smooth_host: a buffer is NULL");
-    std::vector<int32_t> cells, anchors;
-    for (int64_t q = 0; q < n_queries; ++q)
-        r9s_smooth_host(g, bits, next, goals, n_goals, starts, goal_idx, q, N, span, wp, status,
-                        steps, vertices, cells, anchors);
-    return UAM_OK;
+    return route_paths_smooth_host(g, "uam_route_paths_smooth_host", bits, next, goals, n_goals,
+                                   starts, goal_idx, n_queries, N, span, wp, status, steps,
+                                   vertices);
+}
+
+int uam_route3d_paths_smooth_host(const uam_volume_desc* desc, const uam_route3d_params* params,
+                                  const uint32_t* bits, const uint8_t* next, const double* goals,
+                                  int32_t n_goals, const double* starts, const int32_t* goal_idx,
+                                  int64_t n_queries, int32_t N, int32_t span, double* wp3,
+                                  int32_t* status, int32_t* steps, int32_t* vertices) {
+    KRoute3 g{};
+    const int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    return route_paths_smooth_host(g, "uam_route3d_paths_smooth_host", bits, next, goals, n_goals,
+                                   starts, goal_idx, n_queries, N, span, wp3, status, steps,
+                                   vertices);
 }
 
 int uam_route_visible_host(const uam_raster_desc* desc, const uint32_t* bits, int64_t n,
@@ -9702,7 +9809,7 @@ int uam_route_visible_host(const uam_raster_desc* desc, const uint32_t* bits, in
     if (n == 0) return UAM_OK;
     if (!bits || !a_cells || !b_cells || !out)
         return fail(UAM_E_INVALID, "uam_route_visible_host: a buffer is NULL");
-    const int64_t cells = (int64_t)g.nx * g.ny;
+    const int64_t cells = r9_count(g);
     for (int64_t i = 0; i < n; ++i)
         if (a_cells[i] < 0 || a_cells[i] >= cells || b_cells[i] < 0 || b_cells[i] >= cells)
             return fail(UAM_E_INVALID, "uam_route_visible_host: pair %lld is off the raster",
@@ -9713,107 +9820,9 @@ int uam_route_visible_host(const uam_raster_desc* desc, const uint32_t* bits, in
         const int64_t bx = b_cells[i] % g.nx, by = b_cells[i] / g.nx;
         const int64_t far = std::max(std::llabs(bx - ax), std::llabs(by - ay));
         // the kernel's 32-bit walk wherever a span can reach, 64-bit beyond
-        out[i] = far <= UAM_ROUTE_SPAN_MAX ? r9s_visible(bits, g.nx, a_cells[i], b_cells[i])
+        out[i] = far <= UAM_ROUTE_SPAN_MAX ? r9_visible(g, bits, a_cells[i], b_cells[i])
                                            : r9s_los<int64_t>(bits, wpr, ax, ay, bx, by);
     }
-    return UAM_OK;
-}
-
-// ---- K9vb / K9vs: shortcuts on the traced route in the volume (k9v_smooth.inc) -----------------
-static int route3d_smooth_ok(const KRoute3& g, int32_t n_goals, int64_t n_queries, int32_t span) {
-    const int st = route3d_goals_ok(g, n_goals);
-    if (st) return st;
-    if (n_queries < 0) return fail(UAM_E_INVALID, "route3d n_queries < 0");
-    if (span < 1 || span > UAM_ROUTE_SPAN_MAX)
-        return fail(UAM_E_INVALID, "route3d span %d outside [1, %d]", span, UAM_ROUTE_SPAN_MAX);
-    // voxel and chain indices are int32 and the kernel forms a + span
-    if (r9v_voxels(g) > (int64_t)INT32_MAX - UAM_ROUTE_SPAN_MAX)
-        return fail(UAM_E_INVALID, "route3d smoothing needs nx*ny*nz <= 2^31 - 1 - %d",
-                    UAM_ROUTE_SPAN_MAX);
-    return UAM_OK;
-}
-
-int64_t uam_route3d_free_bits_bytes(const uam_volume_desc* desc) {
-    KVolume kv;
-    if (make_kvolume(desc, &kv)) return -1;
-    return (((int64_t)kv.nx * kv.ny * kv.nz + 31) >> 5) * 4;
-}
-
-int uam_route3d_free_bits(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol,
-                          const uam_route3d_params* params, uint32_t* bits, uam_stream stream) {
-    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
-    KRoute3 g{};
-    const int st = route3d_setup(desc, params, &g);
-    if (st) return st;
-    if (!vol || !bits) return fail(UAM_E_INVALID, "uam_route3d_free_bits: vol / bits is NULL");
-    if (((uintptr_t)vol & 255) || ((uintptr_t)bits & 3))
-        return fail(UAM_E_INVALID, "route3d volume not 256-B or free bits not 4-B aligned");
-    DeviceGuard dg(ctx->device);
-    const int64_t chunks = (r9v_voxels(g) + 63) >> 6;
-    hipLaunchKernelGGL(k_route3_free_bits, dim3(grid_for(chunks * 64, R9_THREADS, 1 << 16)),
-                       dim3(R9_THREADS), 0, (hipStream_t)stream, (const uint2*)vol,
-                       (const uint2*)((const char*)vol + vol_col_offset(desc)), g, bits);
-    HIP_TRY(hipGetLastError());
-    ctx->last_kernel = "K9vb";
-    return UAM_OK;
-}
-
-int uam_route3d_paths_smooth(uam_ctx* ctx, const uam_volume_desc* desc,
-                             const uam_route3d_params* params, const uint32_t* bits,
-                             const uint8_t* next, const double* goals, int32_t n_goals,
-                             const double* starts, const int32_t* goal_idx, int64_t n_queries,
-                             int32_t span, double* wp3, int32_t* status, int32_t* steps,
-                             int32_t* vertices, uam_stream stream) {
-    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
-    if (!ctx->have_params) return fail(UAM_E_STATE, "uam_set_params has not been called");
-    KRoute3 g{};
-    int st = route3d_setup(desc, params, &g);
-    if (st) return st;
-    if ((st = route3d_smooth_ok(g, n_goals, n_queries, span))) return st;
-    if (n_queries == 0) return UAM_OK;
-    if (!bits || !next || !goals || !starts || !goal_idx || !wp3 || !status)
-        return fail(UAM_E_INVALID, "uam_route3d_paths_smooth: a buffer is NULL");
-    if (n_queries >= ((int64_t)1 << 31) * R9S_WAVES)
-        return fail(UAM_E_INVALID, "route3d n_queries too large");
-    DeviceGuard dg(ctx->device);
-    const int64_t blocks = (n_queries + R9S_WAVES - 1) / R9S_WAVES;
-    hipLaunchKernelGGL(k_route3_smooth, dim3((unsigned)blocks), dim3(R9S_WAVES * 64), 0,
-                       (hipStream_t)stream, g, bits, next, goals, n_goals, starts, goal_idx,
-                       n_queries, ctx->kp.N, span, wp3, status, steps, vertices);
-    HIP_TRY(hipGetLastError());
-    ctx->last_kernel = "K9vs";
-    return UAM_OK;
-}
-
-int uam_route3d_free_bits_host(const uam_volume_desc* desc, const void* vol,
-                               const uam_route3d_params* params, uint32_t* bits) {
-    KRoute3 g{};
-    const int st = route3d_setup(desc, params, &g);
-    if (st) return st;
-    if (!vol || !bits)
-        return fail(UAM_E_INVALID, "uam_route3d_free_bits_host: vol / bits is NULL");
-    r9vs_free_bits_host(g, (const uint2*)vol,
-                        (const uint2*)((const char*)vol + vol_col_offset(desc)), bits);
-    return UAM_OK;
-}
-
-int uam_route3d_paths_smooth_host(const uam_volume_desc* desc, const uam_route3d_params* params,
-                                  const uint32_t* bits, const uint8_t* next, const double* goals,
-                                  int32_t n_goals, const double* starts, const int32_t* goal_idx,
-                                  int64_t n_queries, int32_t N, int32_t span, double* wp3,
-                                  int32_t* status, int32_t* steps, int32_t* vertices) {
-    KRoute3 g{};
-    int st = route3d_setup(desc, params, &g);
-    if (st) return st;
-    if ((st = route3d_smooth_ok(g, n_goals, n_queries, span))) return st;
-    if (N < 0) return fail(UAM_E_INVALID, "route3d N < 0");
-    if (n_queries == 0) return UAM_OK;
-    if (!bits || !next || !goals || !starts || !goal_idx || !wp3 || !status)
-        return fail(UAM_E_INVALID, "uam_route3d_paths_smooth_host: a buffer is NULL");
-    std::vector<int32_t> cells, anchors;
-    for (int64_t q = 0; q < n_queries; ++q)
-        r9vs_smooth_host(g, bits, next, goals, n_goals, starts, goal_idx, q, N, span, wp3, status,
-                         steps, vertices, cells, anchors);
     return UAM_OK;
 }
 

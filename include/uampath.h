@@ -577,8 +577,9 @@ int uam_kernel_time(uam_ctx* ctx, double* ms_total, int64_t* launches);
  * (uam_eval_generated3d_profiles), "K4e+v" / "K4ew+v" / "K4p+v" (their _v forms with the
  * vertical terms); "K9" (uam_route_field) / "K9t" (uam_route_paths) / "K9b"
  * (uam_route_free_bits) / "K9s" (uam_route_paths_smooth); "K9v" (uam_route3d_field) / "K9vt"
- * (uam_route3d_paths) / "K9vb" (uam_route3d_free_bits) / "K9vs" (uam_route3d_paths_smooth); ""
- * before the first call.
+ * (uam_route3d_paths) / "K9vb" (uam_route3d_free_bits) / "K9vs" (uam_route3d_paths_smooth);
+ * "K9vj" (uam_route3d_field_joint) / "K9vjt" / "K9vjs" (uam_route3d_paths_joint, span 0 / span
+ * >= 1); "" before the first call.
  * The string is static (never freed).  For benchmarks and tests:
  * which kernel a number belongs to. */
 const char* uam_last_kernel(const uam_ctx* ctx);
@@ -1380,6 +1381,108 @@ int uam_route3d_paths_smooth_host(const uam_volume_desc* desc, const uam_route3d
                                   int32_t* status, int32_t* steps, int32_t* vertices);
 int uam_route3d_visible_host(const uam_volume_desc* desc, const uint32_t* bits, int64_t n,
                              const int32_t* a_vox, const int32_t* b_vox, uint8_t* out_u8);
+
+/* Route seeds in the volume, joint field (K9vj): one 3-D field to the nearest of many goals, with
+ * an owner volume.  "Route seeds, joint field" above, restated over voxels: from this point of
+ * the route, at this altitude, which vertiport is cheapest to reach, and along which 3-D route?
+ * One relaxation, one f64 volume, one u8 volume and one int32 volume whatever the number of goals,
+ * where uam_route3d_field pays a relaxation and a pair of volumes per goal.
+ *
+ * Definition (normative; independent statement: tests/route3d_joint_ref.py).  Voxels, the 26
+ * directions, the step lengths with kappa = z_scale, the voxel cost, blocked0 and blocked (flags,
+ * a non-finite or non-positive cost, agl, the inflation per layer), the box rule for edges and
+ * w(u,v) = (0.5 * (c_u + c_v)) * L_k are the "Route seeds in the volume" text, unchanged.  Every
+ * float64 operation is rounded separately, with no fused multiply-add.
+ *   valid goal goal i is valid when its point maps to a voxel g_i of the volume and that voxel is
+ *              free.  Gc is the set of voxels of the valid goals.  Several goals may share a
+ *              voxel.  Gc may be empty.
+ *   field      dist[v] = 0 for v in Gc; elsewhere the minimum, over edge paths that start in any
+ *              voxel of Gc and end in v, of the left fold fl(fl(0 + w_01) + w_12) + ..; +inf for
+ *              blocked and unreachable voxels, and everywhere when Gc is empty.  It is the one
+ *              fixed point of d[v] = min(d[v], fl(d[u] + w(u,v))) started from 0 on Gc and +inf
+ *              elsewhere: the bits do not depend on the tile shape, the sweeps per round or the
+ *              schedule.
+ *   next hop   uint8 per voxel, formed after convergence: 26 at every voxel of Gc (the test is
+ *              membership in Gc, not dist == 0), 255 where dist is +inf, otherwise the lowest k
+ *              whose neighbour u_k has an edge to v with fl(dist[u_k] + w(u_k, v)) == dist[v].
+ *   owner      int32 per voxel, laid out [ny][nx][nz]: -1 where next is 255; at a voxel of Gc the
+ *              lowest index i with g_i = v; otherwise the owner of the first voxel of Gc on the
+ *              chain v -> v + dir(next[v]) -> ..; -1 when the chain visits nx*ny*nz voxels
+ *              without reaching Gc (only where huge costs absorb small weights and equal dist
+ *              values form a cycle).  Ties between goals are broken by the next-hop rule alone,
+ *              never by a comparison of per-goal distances.
+ *   owner      if owner[v] = i >= 0 then dist[v] == dist_i[v] bit for bit, dist_i being goal i's
+ *   property   own uam_route3d_field volume.
+ *   path       a query is a start point [3] only.  Status, tested in this order:
+ *                1  the start is outside the volume or in a blocked voxel;
+ *                2  next[s] = 255 (with no valid goal every free start gets 2);
+ *                3  owner[s] = -1 although dist[s] is finite;
+ *                0  ok.  There is no status 4.
+ *              Status 0: goal_out[q] = o = owner[s], the goal point is goals[o], and the chain,
+ *              steps, vertices, S_i (ez = (z_i - z_{i-1}) * kappa), waypoints and (span >= 1)
+ *              anchors are uam_route3d_paths' and uam_route3d_paths_smooth's text word for word,
+ *              along the joint next from s to g_o.  vertices[q] at span 0 counts every interior
+ *              voxel: max(steps, 2), span 1's value.  A nonzero status: goal_out[q] = -1, steps =
+ *              0, vertices = 0 and every waypoint is the start point.
+ *   guarantee  every waypoint of a status-0 path lies in a free voxel.
+ *   bridge 1   dist equals the elementwise minimum over i of the volumes uam_route3d_field writes
+ *              for the same goals, bit for bit (an invalid goal's volume is all +inf).
+ *   bridge 2   with n_goals = 1, dist and next are uam_route3d_field's bits.
+ *   bridge 3   with n_goals = 1, status, steps and vertices equal uam_route3d_paths' (span 0) and
+ *              uam_route3d_paths_smooth's (span >= 1) with goal_idx = 0 for every query whose
+ *              status there is not 4; the waypoints are equal as well for status 0.
+ *   bridge 4   nz = 1, a volume built from a raster as in "Route seeds in the volume"'s bridge,
+ *              agl = 0: dist and owner equal uam_route_field_joint's bits on the equivalent
+ *              raster, and next agrees wherever the flat value is < 8.
+ *
+ * uam_route3d_field_joint: goals_dev [n_goals][3] into dist_dev [ny][nx][nz] f64, next_dev
+ * likewise u8 and owner_dev likewise int32; workspace_dev holds
+ * uam_route3d_joint_workspace_bytes(desc, params, n_goals) bytes (-1 for bad arguments), 256-B
+ * aligned: uam_route3d_field's workspace and an int32 parent volume.  One start state for all
+ * goals (the distinct tiles of Gc form the first active set), then uam_route3d_field's rounds with
+ * its kernel, UAM_OPT_K9V_TILE_XY / _TILE_Z / _INNER and max_rounds (the call may synchronise the
+ * stream between rounds); the owner by pointer jumping over the parent volume,
+ * ceil(log2(nx*ny*nz)) ordinary launches with no host read between them.  rounds_out and
+ * uam_route3d_visits as for uam_route3d_field.  uam_last_kernel: "K9vj".
+ * uam_route3d_paths_joint: Q start points against next_dev, owner_dev and goals_dev of one
+ * uam_route3d_field_joint call, into wp3_dev [Q][N+2][3], status_dev [Q] and (each may be NULL)
+ * steps_dev, vertices_dev, goal_out_dev [Q].  span = 0: the plain trace, one lane per query, the
+ * start's blocking derived from vol_dev, bits_dev may be NULL; uam_last_kernel "K9vjt".  1 <= span
+ * <= UAM_ROUTE_SPAN_MAX: shortcuts as uam_route3d_paths_smooth makes them, one wave per query, the
+ * blocking from bits_dev (uam_route3d_free_bits of the same desc, vol, params), vol_dev may be
+ * NULL; uam_last_kernel "K9vjs".  Asynchronous.  N from uam_set_params.
+ * Failures: uam_route3d_field's and uam_route3d_paths_smooth's lists, UAM_E_INVALID before any
+ * launch or allocation; in addition n_goals < 1 or > 2^20, nx*ny*nz > 2^31 - 1 -
+ * UAM_ROUTE_SPAN_MAX (parents and owners are int32), owner_dev NULL or not 4-B aligned, span
+ * outside [0, UAM_ROUTE_SPAN_MAX].  UAM_E_VERSION for a wrong abi_version.  UAM_E_STATE, the
+ * message naming max_rounds, when the field has not converged within max_rounds rounds (outputs
+ * unspecified, the context stays usable), and for uam_route3d_paths_joint without
+ * uam_set_params.
+ * The _host calls run the same inline functions without a GPU: the field's minimum by a heap
+ * Dijkstra seeded with all of Gc, the owner by following the chains. */
+int64_t uam_route3d_joint_workspace_bytes(const uam_volume_desc* desc,
+                                          const uam_route3d_params* params, int32_t n_goals);
+int uam_route3d_field_joint(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol_dev,
+                            const uam_route3d_params* params, const double* goals_dev,
+                            int32_t n_goals, double* dist_dev, uint8_t* next_dev,
+                            int32_t* owner_dev, void* workspace_dev, int64_t workspace_bytes,
+                            int32_t* rounds_out, uam_stream stream);
+int uam_route3d_paths_joint(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol_dev,
+                            const uam_route3d_params* params, const uint32_t* bits_dev,
+                            const uint8_t* next_dev, const int32_t* owner_dev,
+                            const double* goals_dev, int32_t n_goals, const double* starts_dev,
+                            int64_t n_queries, int32_t span, double* wp3_dev,
+                            int32_t* status_dev, int32_t* steps_dev, int32_t* vertices_dev,
+                            int32_t* goal_out_dev, uam_stream stream);
+int uam_route3d_field_joint_host(const uam_volume_desc* desc, const void* vol,
+                                 const uam_route3d_params* params, const double* goals,
+                                 int32_t n_goals, double* dist, uint8_t* next, int32_t* owner);
+int uam_route3d_paths_joint_host(const uam_volume_desc* desc, const void* vol,
+                                 const uam_route3d_params* params, const uint32_t* bits,
+                                 const uint8_t* next, const int32_t* owner, const double* goals,
+                                 int32_t n_goals, const double* starts, int64_t n_queries,
+                                 int32_t N, int32_t span, double* wp3, int32_t* status,
+                                 int32_t* steps, int32_t* vertices, int32_t* goal_out);
 
 /* Workspace bytes uam_refine needs for n_paths (after uam_set_geometry/uam_set_params). */
 int64_t uam_refine_workspace_bytes(uam_ctx* ctx, int64_t n_paths,

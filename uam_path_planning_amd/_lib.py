@@ -310,6 +310,24 @@ SIGNATURES = {
                                                      ctypes.c_int32, _vp, _vp, _vp, _vp]),
     "uam_route3d_visible_host": (ctypes.c_int, [ctypes.POINTER(VolumeDesc), _vp, ctypes.c_int64,
                                                 _vp, _vp, _vp]),
+    "uam_route3d_joint_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(VolumeDesc),
+                                                           ctypes.POINTER(Route3dParams),
+                                                           ctypes.c_int32]),
+    "uam_route3d_field_joint": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp,
+                                               ctypes.POINTER(Route3dParams), _vp, ctypes.c_int32,
+                                               _vp, _vp, _vp, _vp, ctypes.c_int64, _i32p, _vp]),
+    "uam_route3d_paths_joint": (ctypes.c_int, [_vp, ctypes.POINTER(VolumeDesc), _vp,
+                                               ctypes.POINTER(Route3dParams), _vp, _vp, _vp, _vp,
+                                               ctypes.c_int32, _vp, ctypes.c_int64,
+                                               ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "uam_route3d_field_joint_host": (ctypes.c_int, [ctypes.POINTER(VolumeDesc), _vp,
+                                                    ctypes.POINTER(Route3dParams), _vp,
+                                                    ctypes.c_int32, _vp, _vp, _vp]),
+    "uam_route3d_paths_joint_host": (ctypes.c_int, [ctypes.POINTER(VolumeDesc), _vp,
+                                                    ctypes.POINTER(Route3dParams), _vp, _vp, _vp,
+                                                    _vp, ctypes.c_int32, _vp, ctypes.c_int64,
+                                                    ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
+                                                    _vp, _vp]),
     "uam_refine_workspace_bytes": (ctypes.c_int64, [_vp, ctypes.c_int64,
                                                     ctypes.POINTER(RefineParams)]),
     "uam_refine": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.POINTER(RefineParams), _vp,

@@ -6154,6 +6154,10 @@ __global__ __launch_bounds__(1024) void k_g_final(KParams p, KGrp kg, KOut out,
 // K9vb / K9vs: any-angle shortcuts on the traced route in the volume, k_route3_free_bits,
 // k_route3_smooth
 #include "k9v_smooth.inc"
+// K9vj: the joint route field of many goals in the volume, k_route3_joint_clear,
+// k_route3_joint_seed, k_route3_joint_next, k_route3_joint_mark, k_route3_joint_parent,
+// k_route3_joint_trace, k_route3_joint_smooth (the owner stage is K9j's k_owner_jump, k_owner_final)
+#include "k9v_joint.inc"
 
 // closes the anonymous namespace opened above the device-side tables
 }  // namespace
@@ -9013,7 +9017,8 @@ int uam_eval_generated3d_profiles_hv(uam_ctx* ctx, const uam_volume_desc* vd, co
                            out, climb_sum, stream);
 }
 
-// ---- K9: route seeds (k9_route.inc, k9_smooth.inc, k9_joint.inc, k9v_route.inc, k9v_smooth.inc)
+// ---- K9: route seeds (k9_route.inc, k9_smooth.inc, k9_joint.inc, k9v_route.inc, k9v_smooth.inc,
+// k9v_joint.inc)
 // One host plan for the family.  The raster ("route"), the joint field on it ("joint route") and
 // the volume ("route3d") differ in their grids, their kernels and the names in their messages;
 // the checks and their order, the round loop and the launches' shape are written once, first.
@@ -9106,12 +9111,14 @@ static int route_goals_ok(const G& g, int32_t n_goals) {
 }
 
 // parents and owners are int32 and the smoothing kernel forms a + span
-static int route_joint_ok(const KRoute& g, int32_t n_goals) {
+template <typename G>
+static int route_joint_ok(const G& g, int32_t n_goals) {
+    const RouteNames nm = route_names(g);
     if (n_goals < 1 || n_goals > R9J_GOALS_MAX)
-        return fail(UAM_E_INVALID, "joint route n_goals %d outside [1, %d]", n_goals,
+        return fail(UAM_E_INVALID, "joint %s n_goals %d outside [1, %d]", nm.what, n_goals,
                     R9J_GOALS_MAX);
     if (r9_count(g) > (int64_t)INT32_MAX - UAM_ROUTE_SPAN_MAX)
-        return fail(UAM_E_INVALID, "joint route field needs nx*ny <= 2^31 - 1 - %d",
+        return fail(UAM_E_INVALID, "joint %s field needs %s <= 2^31 - 1 - %d", nm.what, nm.extent,
                     UAM_ROUTE_SPAN_MAX);
     return UAM_OK;
 }
@@ -9132,13 +9139,14 @@ static int route_smooth_ok(const G& g, int32_t n_goals, int64_t n_queries, int32
     return UAM_OK;
 }
 
-static int route_paths_joint_ok(const KRoute& g, int32_t n_goals, int64_t n_queries,
-                                int32_t span) {
+template <typename G>
+static int route_paths_joint_ok(const G& g, int32_t n_goals, int64_t n_queries, int32_t span) {
+    const RouteNames nm = route_names(g);
     const int st = route_joint_ok(g, n_goals);
     if (st) return st;
-    if (n_queries < 0) return fail(UAM_E_INVALID, "route n_queries < 0");
+    if (n_queries < 0) return fail(UAM_E_INVALID, "%s n_queries < 0", nm.what);
     if (span < 0 || span > UAM_ROUTE_SPAN_MAX)
-        return fail(UAM_E_INVALID, "joint route span %d outside [0, %d]", span,
+        return fail(UAM_E_INVALID, "joint %s span %d outside [0, %d]", nm.what, span,
                     UAM_ROUTE_SPAN_MAX);
     return UAM_OK;
 }
@@ -9233,6 +9241,30 @@ static int route_relax(uam_ctx* ctx, hipStream_t s, const RouteField& f, double*
         });
 }
 
+// the volume's rounds: k_route3_relax<TXY, TZ> at the context's tile
+static int route3d_relax(uam_ctx* ctx, hipStream_t s, const RouteField& f, const uint32_t* mask,
+                         double* d, const KRoute3& g, int64_t max_rounds, const char* which,
+                         int64_t* rounds) {
+    const int TXY = ctx->k9v_tile_xy, TZ = ctx->k9v_tile_z, inner = ctx->k9v_inner;
+    const int ntx = r9_tiles(g.nx, TXY), nty = r9_tiles(g.ny, TXY), ntz = r9_tiles(g.nz, TZ);
+    return route_relax_rounds(
+        ctx, s, f.ctl, ntx * nty * ntz, max_rounds, "route3d", which, &ctx->route3d_visits, rounds,
+        [&](int n, int cur) {
+            if (TXY == 8 && TZ == 4)
+                route3_relax_launch<8, 4>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags, f.lists,
+                                          f.ctl, cur, inner);
+            else if (TXY == 8)
+                route3_relax_launch<8, 8>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags, f.lists,
+                                          f.ctl, cur, inner);
+            else if (TZ == 4)
+                route3_relax_launch<16, 4>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags, f.lists,
+                                           f.ctl, cur, inner);
+            else
+                route3_relax_launch<16, 8>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags, f.lists,
+                                           f.ctl, cur, inner);
+        });
+}
+
 // -- the paths --
 // a device path call's first two checks
 static int route_paths_ctx_ok(const uam_ctx* ctx) {
@@ -9309,6 +9341,13 @@ int64_t uam_route3d_workspace_bytes(const uam_volume_desc* desc,
     KRoute3 g{};
     if (route3d_setup(desc, params, &g)) return -1;
     return r9v_workspace(g).field.bytes;
+}
+
+int64_t uam_route3d_joint_workspace_bytes(const uam_volume_desc* desc,
+                                          const uam_route3d_params* params, int32_t n_goals) {
+    KRoute3 g{};
+    if (route3d_setup(desc, params, &g) || route_joint_ok(g, n_goals)) return -1;
+    return r9vj_workspace(g).bytes;
 }
 
 int64_t uam_route_visits(const uam_ctx* ctx) { return ctx ? ctx->route_visits : 0; }
@@ -9441,13 +9480,13 @@ int uam_route3d_field(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol
         return st;
     DeviceGuard dg(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    const int TXY = ctx->k9v_tile_xy, TZ = ctx->k9v_tile_z, inner = ctx->k9v_inner;
+    const int TXY = ctx->k9v_tile_xy, TZ = ctx->k9v_tile_z;
     RouteField f;
     if ((st = route_field_open(ctx, false, workspace, ws.field, &f))) return st;
     const R9vVolume v = route3d_volume(desc, vol);
     uint32_t* mask = (uint32_t*)((char*)workspace + ws.mask_off);
-    const int ntx = r9_tiles(g.nx, TXY), nty = r9_tiles(g.ny, TXY), ntz = r9_tiles(g.nz, TZ);
-    const int nt = ntx * nty * ntz;
+    const int ntx = r9_tiles(g.nx, TXY), ntz = r9_tiles(g.nz, TZ);
+    const int nt = ntx * r9_tiles(g.ny, TXY) * ntz;
     const int64_t voxels = r9_count(g);
     const int64_t max_rounds = params->max_rounds ? params->max_rounds : voxels;
     const int grid = grid_for(voxels, R9_THREADS, 1 << 16);
@@ -9466,27 +9505,79 @@ int uam_route3d_field(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol
         HIP_TRY(hipGetLastError());
         char which[32];
         snprintf(which, sizeof which, "of goal %d", gi);
-        st = route_relax_rounds(
-            ctx, s, f.ctl, nt, max_rounds, "route3d", which, &ctx->route3d_visits, &rounds,
-            [&](int n, int cur) {
-                if (TXY == 8 && TZ == 4)
-                    route3_relax_launch<8, 4>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags,
-                                              f.lists, f.ctl, cur, inner);
-                else if (TXY == 8)
-                    route3_relax_launch<8, 8>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags,
-                                              f.lists, f.ctl, cur, inner);
-                else if (TZ == 4)
-                    route3_relax_launch<16, 4>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags,
-                                               f.lists, f.ctl, cur, inner);
-                else
-                    route3_relax_launch<16, 8>(n, s, f.c, mask, d, g, ntx, nty, ntz, f.flags,
-                                               f.lists, f.ctl, cur, inner);
-            });
-        if (st) return st;
+        if ((st = route3d_relax(ctx, s, f, mask, d, g, max_rounds, which, &rounds))) return st;
         hipLaunchKernelGGL(k_route3_next, dim3(grid), dim3(R9_THREADS), 0, s, f.c, mask, d, g, goal,
                            next + (int64_t)gi * voxels);
         HIP_TRY(hipGetLastError());
     }
+    if (rounds_out) *rounds_out = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
+    return UAM_OK;
+}
+
+int uam_route3d_field_joint(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol,
+                            const uam_route3d_params* params, const double* goals,
+                            int32_t n_goals, double* dist, uint8_t* next, int32_t* owner,
+                            void* workspace, int64_t workspace_bytes, int32_t* rounds_out,
+                            uam_stream stream) {
+    if (!ctx) return fail(UAM_E_INVALID, "ctx is NULL");
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_joint_ok(g, n_goals))) return st;
+    const R9vjWs ws = r9vj_workspace(g);
+    if ((st = route_field_args_ok(
+             "joint route3d", "uam_route3d_field_joint",
+             !vol || !goals || !dist || !next || !owner || !workspace,
+             "vol / goals / dist / next / owner / workspace", workspace, workspace_bytes, ws.bytes,
+             ((uintptr_t)vol & 255) || ((uintptr_t)dist & 7) || ((uintptr_t)owner & 3),
+             "joint route3d workspace or volume not 256-B, dist not 8-B or owner not 4-B "
+             "aligned")))
+        return st;
+    DeviceGuard dg(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int TXY = ctx->k9v_tile_xy, TZ = ctx->k9v_tile_z;
+    RouteField f;
+    if ((st = route_field_open(ctx, false, workspace, ws.field.field, &f))) return st;
+    const R9vVolume v = route3d_volume(desc, vol);
+    uint32_t* mask = (uint32_t*)((char*)workspace + ws.field.mask_off);
+    int32_t* parent = (int32_t*)((char*)workspace + ws.parent_off);
+    const int ntx = r9_tiles(g.nx, TXY), ntz = r9_tiles(g.nz, TZ);
+    const int nt = ntx * r9_tiles(g.ny, TXY) * ntz;
+    const int64_t voxels = r9_count(g);
+    const int64_t max_rounds = params->max_rounds ? params->max_rounds : voxels;
+    const int grid = grid_for(voxels, R9_THREADS, 1 << 16);
+    const int ggrid = (n_goals + R9_THREADS - 1) / R9_THREADS;
+    ctx->last_kernel = "K9vj";
+    ctx->route3d_visits = 0;
+    hipLaunchKernelGGL(k_route3_cost, dim3(grid), dim3(R9_THREADS), 0, s, v.vox, v.col, g, f.c);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route3_mask, dim3(grid), dim3(R9_THREADS), 0, s, f.c, g, mask);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route3_joint_clear, dim3(grid), dim3(R9_THREADS), 0, s, g, dist, nt,
+                       f.flags, f.ctl);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route3_joint_seed, dim3(ggrid), dim3(R9_THREADS), 0, s, f.c, g, goals,
+                       n_goals, dist, TXY, TZ, ntx, ntz, f.flags, f.lists, f.ctl);
+    HIP_TRY(hipGetLastError());
+    int64_t rounds = 0;
+    if ((st = route3d_relax(ctx, s, f, mask, dist, g, max_rounds, "of the goals jointly",
+                            &rounds)))
+        return st;
+    hipLaunchKernelGGL(k_route3_joint_next, dim3(grid), dim3(R9_THREADS), 0, s, f.c, mask, dist, g,
+                       next, owner);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route3_joint_mark, dim3(ggrid), dim3(R9_THREADS), 0, s, f.c, g, goals,
+                       n_goals, next, owner);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_route3_joint_parent, dim3(grid), dim3(R9_THREADS), 0, s, g, next, parent,
+                       owner);
+    HIP_TRY(hipGetLastError());
+    for (int r = r9j_jumps(voxels); r > 0; --r) {
+        hipLaunchKernelGGL(k_owner_jump, dim3(grid), dim3(R9_THREADS), 0, s, parent, voxels);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_owner_final, dim3(grid), dim3(R9_THREADS), 0, s, parent, owner, voxels);
+    HIP_TRY(hipGetLastError());
     if (rounds_out) *rounds_out = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
     return UAM_OK;
 }
@@ -9529,6 +9620,21 @@ int uam_route3d_field_host(const uam_volume_desc* desc, const void* vol,
         return fail(UAM_E_INVALID, "uam_route3d_field_host: vol / goals / dist / next is NULL");
     const R9vVolume v = route3d_volume(desc, vol);
     r9v_field_host(g, v.vox, v.col, goals, n_goals, dist, next);
+    return UAM_OK;
+}
+
+int uam_route3d_field_joint_host(const uam_volume_desc* desc, const void* vol,
+                                 const uam_route3d_params* params, const double* goals,
+                                 int32_t n_goals, double* dist, uint8_t* next, int32_t* owner) {
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
+    if (st) return st;
+    if ((st = route_joint_ok(g, n_goals))) return st;
+    if (!vol || !goals || !dist || !next || !owner)
+        return fail(UAM_E_INVALID,
+                    "uam_route3d_field_joint_host: vol / goals / dist / next / owner is NULL");
+    const R9vVolume v = route3d_volume(desc, vol);
+    r9vj_field_host(g, v.vox, v.col, goals, n_goals, dist, next, owner);
     return UAM_OK;
 }
 
@@ -9657,6 +9763,65 @@ int uam_route3d_paths_host(const uam_volume_desc* desc, const void* vol,
     const R9vVolume v = route3d_volume(desc, vol);
     for (int64_t q = 0; q < n_queries; ++q)
         r9_trace(g, v, next, goals, n_goals, starts, goal_idx, q, N, wp3, status, steps);
+    return UAM_OK;
+}
+
+int uam_route3d_paths_joint(uam_ctx* ctx, const uam_volume_desc* desc, const void* vol,
+                            const uam_route3d_params* params, const uint32_t* bits,
+                            const uint8_t* next, const int32_t* owner, const double* goals,
+                            int32_t n_goals, const double* starts, int64_t n_queries,
+                            int32_t span, double* wp3, int32_t* status, int32_t* steps,
+                            int32_t* vertices, int32_t* goal_out, uam_stream stream) {
+    KRoute3 g{};
+    int st = route_paths_ctx_ok(ctx);
+    if (st || (st = route3d_setup(desc, params, &g)) ||
+        (st = route_paths_joint_ok(g, n_goals, n_queries, span)))
+        return st;
+    if ((st = route_queries_ok("route3d", "uam_route3d_paths_joint", n_queries, 0,
+                               !(span ? (const void*)bits : vol) || !next || !owner || !goals ||
+                                   !starts || !wp3 || !status)))
+        return st < 0 ? st : UAM_OK;
+    if (!span && ((uintptr_t)vol & 255))
+        return fail(UAM_E_INVALID, "route3d volume not 256-B aligned");
+    // span >= 1: vol is not read and may be NULL
+    const R9vVolume v = vol ? route3d_volume(desc, vol) : R9vVolume{nullptr, nullptr};
+    return route_paths_launch(
+        ctx, "route3d", span ? "K9vjs" : "K9vjt", n_queries, span != 0, stream,
+        [&](dim3 blocks, dim3 threads, hipStream_t s) {
+            if (span)
+                hipLaunchKernelGGL(k_route3_joint_smooth, blocks, threads, 0, s, g, bits, next,
+                                   owner, goals, n_goals, starts, n_queries, ctx->kp.N, span, wp3,
+                                   status, steps, vertices, goal_out);
+            else
+                hipLaunchKernelGGL(k_route3_joint_trace, blocks, threads, 0, s, g, v.vox, v.col,
+                                   next, owner, goals, n_goals, starts, n_queries, ctx->kp.N, wp3,
+                                   status, steps, vertices, goal_out);
+        });
+}
+
+int uam_route3d_paths_joint_host(const uam_volume_desc* desc, const void* vol,
+                                 const uam_route3d_params* params, const uint32_t* bits,
+                                 const uint8_t* next, const int32_t* owner, const double* goals,
+                                 int32_t n_goals, const double* starts, int64_t n_queries,
+                                 int32_t N, int32_t span, double* wp3, int32_t* status,
+                                 int32_t* steps, int32_t* vertices, int32_t* goal_out) {
+    KRoute3 g{};
+    int st = route3d_setup(desc, params, &g);
+    if (st || (st = route_paths_joint_ok(g, n_goals, n_queries, span))) return st;
+    if ((st = route_queries_ok("route3d", "uam_route3d_paths_joint_host", n_queries, N,
+                               !(span ? (const void*)bits : vol) || !next || !owner || !goals ||
+                                   !starts || !wp3 || !status)))
+        return st < 0 ? st : UAM_OK;
+    // span >= 1: vol is not read and may be NULL
+    const R9vVolume v = vol ? route3d_volume(desc, vol) : R9vVolume{nullptr, nullptr};
+    std::vector<int32_t> cells, anchors;
+    for (int64_t q = 0; q < n_queries; ++q)
+        if (span)
+            r9_smooth_host<true>(g, bits, next, goals, n_goals, starts, owner, q, N, span, wp3,
+                                 status, steps, vertices, cells, anchors, goal_out);
+        else
+            r9_trace<true>(g, v, next, goals, n_goals, starts, owner, q, N, wp3, status, steps,
+                           vertices, goal_out);
     return UAM_OK;
 }
 

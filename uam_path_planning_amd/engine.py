@@ -197,7 +197,11 @@ class RouteField3D:
     untracked product of the volume: rebuild it when the voxels or columns change.
     free_bits: the free voxels as one bit per voxel ([(nx*ny*nz + 31) // 32] 32-bit words, bit
     v & 31 of word v >> 5 for the voxel index v; Engine.route_free_bits3d), built and kept here
-    by the first route_paths3d(..., smooth >= 1)."""
+    by the first route_paths3d(..., smooth >= 1).
+    joint = True (route_field3d(..., joint=True), K9vj; "Route seeds in the volume, joint field"):
+    one field to the nearest of the goals, dist and next [1, ny, nx, nz] (26 at every valid goal's
+    voxel), and owner [ny, nx, nz] int32: the index of the goal a voxel's route ends at, -1 where
+    there is none."""
     geo: VolumeGeo
     goals: object = field(repr=False)
     dist: object = field(repr=False)
@@ -211,6 +215,8 @@ class RouteField3D:
     agl: float = 0.0
     z_scale: float = 1e-3
     free_bits: object = field(default=None, repr=False)
+    owner: object = field(default=None, repr=False)
+    joint: bool = False
 
     def params(self, max_rounds=0):
         return _route3d_params(self.lam, self.block_flags, self.inflate, self.agl,
@@ -1127,7 +1133,7 @@ class Engine:
 
     # -- route seeds in the volume (K9v) ------------------------------------------------------
     def route_field3d(self, volume, goals, lam=1.0, block_flags=_lib.FLAG_NFZ, inflate=0,
-                      agl=0.0, z_scale=1e-3, max_rounds=0):
+                      agl=0.0, z_scale=1e-3, max_rounds=0, joint=False):
         """The cost-to-go fields of goals [G, 3] (x km, y km, z m) over volume's voxels
         (uam_route3d_field): a per-goal setup product like route_field's.  Voxel cost 1 + lam *
         risk; voxels of a column with a block_flags bit, with a non-finite or non-positive cost
@@ -1135,13 +1141,32 @@ class Engine:
         voxels of x/y clearance around them; z_scale is Vertical's unit (km per metre of
         altitude), so the field's metric is the one eval_waypoints3d(..., vertical=) charges;
         max_rounds 0 = nx*ny*nz.  Returns a RouteField3D; raises UamError when a field has not
-        converged within max_rounds."""
+        converged within max_rounds.
+        joint=True (uam_route3d_field_joint, K9vj): one field to the nearest of the goals in one
+        relaxation -- dist and next [1, ny, nx, nz] and owner [ny, nx, nz], the goal each voxel's
+        route ends at -- for the time and memory of about one goal."""
         torch = _torch()
         geo = volume.geo
         g = self.tensor(goals, torch.float64).reshape(-1, 3)
         G = g.shape[0]
         rp = _route3d_params(lam, block_flags, inflate, agl, z_scale, max_rounds)
         gs = geo.as_struct()
+        if joint:
+            nbytes = self.lib.uam_route3d_joint_workspace_bytes(ctypes.byref(gs),
+                                                                ctypes.byref(rp), G)
+            ws = None if nbytes < 0 else self.empty(((nbytes + 255) // 256, 256), torch.uint8)
+            dist = self.empty((1, geo.ny, geo.nx, geo.nz), torch.float64)
+            nxt = self.empty((1, geo.ny, geo.nx, geo.nz), torch.uint8)
+            owner = self.empty((geo.ny, geo.nx, geo.nz), torch.int32)
+            rounds = ctypes.c_int32()
+            _lib.check(self.lib.uam_route3d_field_joint(
+                self._ctx, ctypes.byref(gs), _ptr(volume.buf), ctypes.byref(rp), _ptr(g), G,
+                _ptr(dist), _ptr(nxt), _ptr(owner), _ptr(ws), max(nbytes, 0),
+                ctypes.byref(rounds), self.stream), "uam_route3d_field_joint")
+            return RouteField3D(geo, g, dist, nxt, rounds.value,
+                                int(self.lib.uam_route3d_visits(self._ctx)), volume.buf,
+                                float(lam), int(block_flags), int(inflate), float(agl),
+                                float(z_scale), None, owner, True)
         nbytes = self.lib.uam_route3d_workspace_bytes(ctypes.byref(gs), ctypes.byref(rp))
         ws = None if nbytes < 0 else self.empty(((nbytes + 255) // 256, 256), torch.uint8)
         dist = self.empty((G, geo.ny, geo.nx, geo.nz), torch.float64)
@@ -1170,7 +1195,7 @@ class Engine:
             field.free_bits = bits
         return field.free_bits
 
-    def route_paths3d(self, field, starts, goal_idx, smooth=0):
+    def route_paths3d(self, field, starts, goal_idx=None, smooth=0):
         """Seed paths through a RouteField3D (uam_route3d_paths): starts [Q, 3], goal_idx [Q]
         into field.goals.  Returns {"wp3" [Q, N+2, 3], "status" [Q], "steps" [Q]} (device
         tensors); status as route_paths' -- a nonzero status leaves the straight line in wp3.
@@ -1179,9 +1204,32 @@ class Engine:
         chain voxels (1..1024) wherever the voxels between lie in straight sight, in plan view
         and in altitude; adds "vertices" [Q] (the polyline's vertices, end points included; 0
         for a nonzero status).  smooth = 1 keeps every voxel: the bits of smooth = 0.  The test
-        is geometric and does not weigh risk: a long span may cut a climb to cheaper layers."""
+        is geometric and does not weigh risk: a long span may cut a climb to cheaper layers.
+        A joint field (uam_route3d_paths_joint) takes no goal_idx: every start goes to the goal
+        that owns its voxel, returned as "goal" [Q] (-1 for a nonzero status, which is 1, 2 or 3
+        -- no owner -- and leaves the start point in every waypoint); "vertices" for every
+        smooth."""
         torch = _torch()
         s = self.tensor(starts, torch.float64).reshape(-1, 3)
+        if field.joint:
+            if goal_idx is not None:
+                raise ValueError("a joint RouteField3D takes no goal_idx")
+            Q = s.shape[0]
+            N = self.params.N
+            out = {"wp3": self.empty((Q, N + 2, 3), torch.float64)}
+            for k in ("status", "steps", "vertices", "goal"):
+                out[k] = self.empty((Q,), torch.int32)
+            bits = self.route_free_bits3d(field) if smooth else None
+            rp = field.params()
+            _lib.check(self.lib.uam_route3d_paths_joint(
+                self._ctx, ctypes.byref(field.geo.as_struct()), _ptr(field.vol), ctypes.byref(rp),
+                _ptr(bits), _ptr(field.next), _ptr(field.owner), _ptr(field.goals),
+                field.goals.shape[0], _ptr(s), Q, int(smooth), _ptr(out["wp3"]),
+                _ptr(out["status"]), _ptr(out["steps"]), _ptr(out["vertices"]), _ptr(out["goal"]),
+                self.stream), "uam_route3d_paths_joint")
+            return out
+        if goal_idx is None:
+            raise ValueError("a per-goal RouteField3D needs goal_idx")
         gi = self.tensor(goal_idx, torch.int32).reshape(-1)
         Q = s.shape[0]
         if gi.shape[0] != Q:
@@ -1208,14 +1256,26 @@ class Engine:
 
     @staticmethod
     def route_field3d_host(geo, vol, goals, lam=1.0, block_flags=_lib.FLAG_NFZ, inflate=0,
-                           agl=0.0, z_scale=1e-3):
+                           agl=0.0, z_scale=1e-3, joint=False):
         """route_field3d on the host (uam_route3d_field_host; needs no GPU).  vol: the volume
         buffer as numpy 32-bit words in the header's layout (8-B voxels {risk, psi}
         [ny][nx][nz], then at the 256-B aligned offset the 8-B columns {terrain, flags}
-        [ny][nx]).  Returns a RouteField3D of numpy arrays (rounds 0)."""
+        [ny][nx]).  Returns a RouteField3D of numpy arrays (rounds 0).  joint=True:
+        uam_route3d_field_joint_host, the owner by following the chains."""
         v = _host_vol(vol, geo)
         g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
         G = g.shape[0]
+        if joint:
+            dist = np.empty((1, geo.ny, geo.nx, geo.nz), dtype=np.float64)
+            nxt = np.empty((1, geo.ny, geo.nx, geo.nz), dtype=np.uint8)
+            owner = np.empty((geo.ny, geo.nx, geo.nz), dtype=np.int32)
+            rp = _route3d_params(lam, block_flags, inflate, agl, z_scale, 0)
+            _lib.check(_lib.load().uam_route3d_field_joint_host(
+                ctypes.byref(geo.as_struct()), v.ctypes.data, ctypes.byref(rp), g.ctypes.data, G,
+                dist.ctypes.data, nxt.ctypes.data, owner.ctypes.data),
+                "uam_route3d_field_joint_host")
+            return RouteField3D(geo, g, dist, nxt, 0, 0, v, float(lam), int(block_flags),
+                                int(inflate), float(agl), float(z_scale), None, owner, True)
         dist = np.empty((G, geo.ny, geo.nx, geo.nz), dtype=np.float64)
         nxt = np.empty((G, geo.ny, geo.nx, geo.nz), dtype=np.uint8)
         rp = _route3d_params(lam, block_flags, inflate, agl, z_scale, 0)
@@ -1243,8 +1303,31 @@ class Engine:
     def route_paths3d_host(field, starts, goal_idx, N, smooth=0):
         """route_paths3d on the host (uam_route3d_paths_host; needs no GPU) for a RouteField3D
         of numpy arrays; N interior waypoints.  Returns {"wp3", "status", "steps"}, and
-        "vertices" for smooth >= 1 (uam_route3d_paths_smooth_host)."""
+        "vertices" for smooth >= 1 (uam_route3d_paths_smooth_host).  A joint field
+        (uam_route3d_paths_joint_host) takes goal_idx = None and adds "vertices" and "goal"."""
         s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        if field.joint:
+            if goal_idx is not None:
+                raise ValueError("a joint RouteField3D takes no goal_idx")
+            Q, N = s.shape[0], int(N)
+            out = {"wp3": np.empty((Q, max(N, 0) + 2, 3), dtype=np.float64)}
+            for k in ("status", "steps", "vertices", "goal"):
+                out[k] = np.empty((Q,), dtype=np.int32)
+            rp = field.params()
+            nxt = np.ascontiguousarray(field.next, dtype=np.uint8)
+            own = np.ascontiguousarray(field.owner, dtype=np.int32)
+            goals = np.ascontiguousarray(field.goals, dtype=np.float64)
+            bits = Engine.route_free_bits3d_host(field) if smooth else None
+            _lib.check(_lib.load().uam_route3d_paths_joint_host(
+                ctypes.byref(field.geo.as_struct()), _host_vol(field.vol, field.geo).ctypes.data,
+                ctypes.byref(rp), bits.ctypes.data if smooth else None, nxt.ctypes.data,
+                own.ctypes.data, goals.ctypes.data, goals.shape[0], s.ctypes.data, Q, N,
+                int(smooth), out["wp3"].ctypes.data, out["status"].ctypes.data,
+                out["steps"].ctypes.data, out["vertices"].ctypes.data, out["goal"].ctypes.data),
+                "uam_route3d_paths_joint_host")
+            return out
+        if goal_idx is None:
+            raise ValueError("a per-goal RouteField3D needs goal_idx")
         gi = np.ascontiguousarray(goal_idx, dtype=np.int32).reshape(-1)
         Q = s.shape[0]
         if gi.shape[0] != Q:
